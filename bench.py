@@ -3,6 +3,12 @@
 (wavenumber x layer x line) optical-depth evaluations per second; profiles per second).
 
     python bench.py --gpus N --steps K --warmup W [--workload c4|c4shard|c2|c2lc|c4brd|c2real|c3|c5|c5full] [--real-kind 8|4]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the line (evals/s and ms_per_step of the timed steps).
+--full adds everything else: per-kernel times, the other workloads, counters and rooflines, the drop-in latency, the CPU
+baseline and, with N > 1, the cost of the gather alone.  --dump-outputs DIR writes what the last timed step computed (the
+arrays a caller of the step receives) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array for array.
 
 One process per GPU.  With N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES the N ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, before anything here touches a GPU), relays rank
@@ -25,8 +31,8 @@ Workloads (synthetic, seeded):
            0.6) and downwelling (IRT 3) = 512 runs x 64 layers x 200 channels U(0.3, 6.5) cm-1 (<= 195 GHz, the range of the TKC
            cloud model) x 500 lines, single precision (real_kind 4: the reference's "sgl" build)
   c5       its 8-GPU share: 32 profiles x 2 views
-At N = 1 the line carries the headline plus, under "workloads", c3 / c5 / c2lc / c4brd / the single profile, each timed for
->= --min-seconds with its own kernel split and counter-derived roofline.
+With --full at N = 1 the line carries the headline plus, under "workloads", c3 / c5 / c2lc / c4brd / the single profile, each
+timed for >= --min-seconds with its own kernel split and counter-derived roofline.
 
 Roofline: the line sum is bound by the FP64 vector ALU, not by HBM.  "roofline" prices the FP64
 work the kernel actually issued - SQ_INSTS_VALU_{FMA,ADD,MUL,TRANS}_F64 from rocprofv3 --pmc, collected LIVE by
@@ -271,9 +277,12 @@ def warmup_rounds(step, sync, torch, dist, world, warmup, warm_seconds, device):
             return n_w
 
 
-def timed_steps(torch, dist, res: Resident, steps, warmup, warm_seconds, plan=None, graph=False, events=True, world=1, gather_every=1):
+def timed_steps(torch, dist, res: Resident, steps, warmup, warm_seconds, plan=None, graph=False, events=True, world=1, gather_every=1,
+                kernel_split=True, after_timed=None):
     """W warm-up steps (continued until warm_seconds have passed, so that the clock has settled), then exactly `steps`
-    steps between barrier + synchronize; HIP events around the dominant kernel inside the timed region."""
+    steps between barrier + synchronize; HIP events around the dominant kernel inside the timed region.  after_timed() runs
+    right after the timed steps, while the buffers hold what the last of them computed; kernel_split=False leaves out the
+    per-kernel times (and the untimed steps they take)."""
     batch, rt = res.batch, res.rt
     if graph:
         batch.capture()
@@ -321,6 +330,10 @@ def timed_steps(torch, dist, res: Resident, steps, warmup, warm_seconds, plan=No
     dt = time.perf_counter() - t0
     rt.profile(0)
     batch.check()
+    if after_timed is not None:
+        after_timed()
+    if not kernel_split:
+        return {"dt": dt, "steps": steps, "warmup_steps_run": n_w}
     ms_lines, n_lines = rt.kernel_time(0)
     # the two small kernels (and the line kernel under graph replay) are timed in a few extra untimed steps
     # (three batches of five steps, the quietest batch counts: a single stall of the queue would otherwise sit in a mean of 5)
@@ -638,7 +651,8 @@ def cpu_baseline(rec, profs, nsample: int, sgl: bool = False, census_profile=Non
         if os.path.exists(harness):
             caseio.write_case(cp, sample)
             t0 = time.perf_counter()
-            r = subprocess.run([harness, cp, tp, op], cwd=d, capture_output=True, text=True, preexec_fn=_big_stack)
+            # (file names relative to the run directory: the harness hands MODM at most 80 characters of the TAPE3 path)
+            r = subprocess.run([harness, "case.bin", "TAPE3", "out.bin"], cwd=d, capture_output=True, text=True, preexec_fn=_big_stack)
             wall = time.perf_counter() - t0
             secs = None
             for line in r.stdout.splitlines():
@@ -659,7 +673,7 @@ def cpu_baseline(rec, profs, nsample: int, sgl: bool = False, census_profile=Non
                         for k in range(nc):
                             ck, ok, lk = (os.path.join(d, f"{n}{k}") for n in ("case", "out", "log"))
                             caseio.write_case(ck, sample[k::nc])
-                            procs.append((subprocess.Popen([harness, ck, tp, ok], cwd=d, stdout=open(lk, "w"),
+                            procs.append((subprocess.Popen([harness, f"case{k}", "TAPE3", f"out{k}"], cwd=d, stdout=open(lk, "w"),
                                                            stderr=subprocess.DEVNULL, preexec_fn=_big_stack), lk))
                         rcs = [p.wait() for p, _ in procs]
                         w_all = time.perf_counter() - t1
@@ -704,7 +718,9 @@ def dropin_latency(rec, profs, tmp):
     caseio.write_case(cp, profs)
     best = None
     for _ in range(2):
-        r = subprocess.run([exe, cp, tp, op, "3"], cwd=tmp, capture_output=True, text=True, timeout=300)
+        # (names relative to the run directory: the harness hands MODM at most 80 characters of the TAPE3 path)
+        r = subprocess.run([exe, "case_dropin.bin", "TAPE3_dropin", "out_dropin.bin", "3"], cwd=tmp, capture_output=True, text=True,
+                           timeout=300)
         if r.returncode != 0:
             return {"error": (r.stdout + r.stderr)[-300:]}
         for line in r.stdout.splitlines():
@@ -722,6 +738,58 @@ def dropin_latency(rec, profs, tmp):
             "what": "MODM + CALCTMR + RTM through the ISO_C_BINDING drop-in modules, one profile per call, host arrays in/out "
                     "(PCIe-inclusive, steady state after the first call, the faster of two runs of the program; first_call_ms = device start-up + TAPE3 load + first "
                     "profile); examples/harness.f90 = the call sequence of src/monortm.f90:557-574"}
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path hands its caller, for comparing two builds output for output
+# ------------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT = 60 * 2 ** 20   # bytes of array data in all: the larger arrays are dumped as a seeded sample of their elements
+DUMP_SEED = 20261016
+SPECTRAL_NAMES = ("rad", "tb", "trtot", "tmr", "rup", "rdn")   # the order of DeviceBatch.spectral_block()
+
+
+def output_arrays(res: Resident, plan=None) -> dict:
+    """The device arrays a step leaves its caller: the six spectral outputs [nprof, nwn], the layer optical depths (total,
+    per molecule, per continuum term, cloud liquid) and the surface temperature of this rank's batch; on rank 0 of a sharded
+    job also the spectral outputs of every rank, as the gather delivered them ([nprof_total, nwn] each)."""
+    b = res.batch
+    blk = b.spectral_block()
+    out = {n: blk[k] for k, n in enumerate(SPECTRAL_NAMES)}
+    out.update(od=b.O, od_by_mol=b.OBM, od_cont=b.OC, od_clw=b.OCLW, tmpsfc=b.tmpsfc)
+    if plan is not None and plan.out is not None:
+        g = plan.result()
+        out.update({f"gathered_{n}": g[:, k] for k, n in enumerate(SPECTRAL_NAMES)})
+    return out
+
+
+def snapshot_outputs(arrays: dict, limit: int = DUMP_LIMIT) -> dict:
+    """-> {name: host array}.  Smallest first, every array gets an equal share of what `limit` leaves: an array that fits its
+    share is copied whole, a larger one as `<name>_sample`, the elements at a seeded set of flat indices (the set depends on
+    the array's size only, so two runs with the same arguments sample the same elements)."""
+    import torch
+
+    out, left = {}, limit
+    order = sorted(arrays, key=lambda k: arrays[k].numel() * arrays[k].element_size())
+    for i, name in enumerate(order):
+        v = arrays[name]
+        share = left // (len(order) - i)
+        if v.numel() * v.element_size() <= share:
+            a = v.detach().cpu().numpy().copy()
+        else:
+            rng = np.random.default_rng(DUMP_SEED)
+            idx = np.unique(rng.integers(0, v.numel(), max(1, share // v.element_size())))
+            a = v.reshape(-1)[torch.as_tensor(idx, device=v.device)].cpu().numpy()
+            name = f"{name}_sample"
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        out[name] = a
+        left -= a.nbytes
+    return out
+
+
+def write_outputs(snap: dict, dirpath: str):
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in snap.items():
+        np.save(os.path.join(dirpath, f"{name}.npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -918,6 +986,138 @@ def stub_rank(args, world, rank):
     return 0
 
 
+def full_record(args, torch, res: Resident, m: dict, out: dict, local: int, world: int):
+    """--full: what the line carries besides the headline - the other workloads (N = 1, c4), counters and rooflines, the
+    drop-in latency and the CPU baseline - added to `out` in place."""
+    avg_ms = m["kernel_ms"]["lines"]
+    extra = {}
+    if world == 1 and not (args.no_extra or args.no_single) and args.workload == "c4":
+        # the other BASELINE configurations that fit one GPU, in the same line: each timed for >= min-seconds
+        for name, graph in (("c4shard", False), ("c3", False), ("c5", False), ("c5full", False), ("c2lc", False), ("c4brd", False),
+                            ("c2real", False), ("c2", True)):
+            try:
+                r2 = Resident(name, 0, local, args.profiles_per_gpu, tmp=res.tmp)
+                m2 = measure_by_duration(torch, r2, args.min_seconds, graph=graph)
+                extra[name] = {"config": r2.config(1, graph), "dtype": "f64" if r2.real_kind == 8 else "f32",
+                               "value": r2.e_step * m2["steps"] / m2["dt"], "unit": "evals/s", "steps": m2["steps"],
+                               "ms_per_step": m2["dt"] / m2["steps"] * 1e3, "timed_ms": m2["dt"] * 1e3,
+                               "profiles_per_sec": len(r2.profs) * m2["steps"] / m2["dt"],
+                               "kernel_ms_per_step": m2["kernel_ms"], "_e_step": r2.e_step}
+                if name == "c3" and not args.no_cpu_baseline:
+                    # the reference on a slice of configs[2] in the same run: ONE layer x every third wavenumber of the grid x the
+                    # 100000 lines = 3.3e8 evals, ~25 s on one core (VERDICT r4 item 7: no more extrapolation from the 50-channel
+                    # case; the rate per eval does not depend on the number of wavenumbers - the whole grid takes 72 s, 1.4e7 evals/s:
+                    # half the rate of the 500-line case, the reference's (39, 250000) arrays miss the caches)
+                    from monortm_amd import synth as _synth
+                    p3 = r2.profs[0]
+                    one = _synth.Profile(wn=p3.wn[::3], p=p3.p[:1], t=p3.t[:1], tz=p3.tz[:2], wkl=p3.wkl[:1], wbrodl=p3.wbrodl[:1],
+                                         clw=p3.clw[:1], irt=3, dvset=p3.dvset * 3)
+                    thin = _synth.Profile(wn=p3.wn[::50], p=p3.p[:1], t=p3.t[:1], tz=p3.tz[:2], wkl=p3.wkl[:1], wbrodl=p3.wbrodl[:1],
+                                          clw=p3.clw[:1], irt=3, dvset=p3.dvset * 50)
+                    try:
+                        extra[name]["cpu_baseline"] = cpu_baseline(r2.rec, [one], 1, census_profile=thin)
+                    except Exception as e:
+                        extra[name]["cpu_baseline"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
+                r2.close()
+            except Exception as e:  # a secondary workload never takes the headline down
+                extra[name] = {"error": f"{type(e).__name__}: {e}"}
+    # counters: live child run under rocprofv3 --pmc; else the committed summary if it matches this source tree
+    pmc, source = None, None
+    names = [args.workload] + [k for k in ("c4shard", "c3", "c5", "c5full", "c2lc", "c4brd", "c2real") if k in extra and "error" not in extra[k]]
+    nested = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "") \
+        or "HSA_TOOLS_LIB" in os.environ
+    if world == 1 and not args.no_pmc and not nested:
+        try:
+            t0 = time.perf_counter()
+            pmc = collect_pmc(names, args.profiles_per_gpu)
+            source = f"live: rocprofv3 --pmc child run of this script ({time.perf_counter() - t0:.0f} s, 3 launches per workload)"
+            if args.save_pmc:
+                with open(args.save_pmc, "w") as f:
+                    json.dump({"csrc_hash": csrc_hash(), "profiles_per_gpu": args.profiles_per_gpu, "passes": PMC_PASSES,
+                               "per_launch": pmc}, f, indent=1)
+        except Exception as e:
+            source = f"live collection failed: {type(e).__name__}: {str(e)[:200]}"
+    if pmc is None:
+        for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_per_launch.json")), reverse=True):
+            try:
+                j = json.load(open(f))
+                if j.get("csrc_hash") == csrc_hash() and j.get("profiles_per_gpu") == args.profiles_per_gpu:
+                    pmc = j["per_launch"]
+                    source = (source + "; " if source else "") + f"{os.path.relpath(f, ROOT)} (csrc hash matches)"
+                    break
+            except Exception:
+                pass
+        else:
+            source = (source + "; " if source else "") + "no committed counter summary matches this source tree (stale files are refused)"
+    get = lambda w: (pmc or {}).get(w, {}).get("lines_kernel")  # noqa: E731
+    out["roofline"] = roofline_from_counters(get(args.workload), avg_ms, res.e_step, source, f32=res.real_kind == 4,
+                                             nwn=res.profs[0].nwn)
+    out["roofline"]["launches"] = m["lines_launches"]
+    if out["roofline"]["frac"] is not None:
+        assert 0.0 < out["roofline"]["frac"] <= 1.0, out["roofline"]
+    out["roofline_hbm_model"] = hbm_model(avg_ms, res.e_step)
+    for name, x in extra.items():
+        if "error" in x:
+            continue
+        e2 = x.pop("_e_step")
+        if name != "c2":
+            x["roofline"] = roofline_from_counters(get(name), x["kernel_ms_per_step"]["lines"], e2, source, f32=x["dtype"] == "f32",
+                                                   nwn=x["config"]["wavenumbers"])
+            if name == "c3":
+                x["roofline"]["note"] = ("kernel family = physics_kernel + far_plan_kernel + far_kernel (every level) + lines_kernel, all between the "
+                                         "'lines' events; the counted FP64 work per eval is ~1.4 flop where direct summation needs ~25: far lines are "
+                                         "expanded once per interval of wavenumbers (Chebyshev sums in levels) instead of being evaluated per "
+                                         "wavenumber, so frac prices far less work than round 4's did at twice the time")
+            if pmc and name in pmc:
+                x["finish_kernel_counters"] = {k: v for k, v in pmc[name].get("finish_kernel", {}).items()
+                                               if k in ("SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "GRBM_GUI_ACTIVE", "_dispatches_per_step")}
+        else:
+            x["launch"] = "hip graph replay"
+    if "c4shard" in extra and "error" not in extra["c4shard"]:
+        # `value` is configs[3] whole on this one GPU; the 128-profile share one of 8 GPUs holds runs at a lower rate (the
+        # fixed cost of a launch is spread over an eighth of the profiles): what the weak-scaling unit delivers
+        out["value_weak_shard"] = extra["c4shard"]["value"]
+        out["value_weak_shard_what"] = "the 128-profile share of one of 8 GPUs (1024 / 8), evals/s - see workloads.c4shard"
+    if extra:
+        out["workloads"] = extra
+        if "c2" in extra:
+            out["configs1_single_profile"] = extra["c2"]
+    if world == 1 and not (args.no_extra or args.no_single) and args.workload in ("c4", "c4shard", "c2lc"):
+        try:
+            out["dropin"] = dropin_latency(res.rec, res.profs[:128], res.tmp)
+        except Exception as e:
+            out["dropin"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and not args.no_cpu_baseline:
+        try:
+            if args.workload == "c3":
+                out["cpu_baseline"] = {"value": None, "unit": "evals/s", "cores": 1, "kind": "reference",
+                                       "sample": "not timed for c3 (about an hour of CPU work); see the c4shard line"}
+            else:
+                # ~10-15 s of single-core work: 256 configs[3] profiles, 64 c5 runs (4x the channels), the one c2 profile
+                ns = args.cpu_sample or {"c4": 256, "c4shard": 256, "c2lc": 64, "c5": 64, "c5full": 64}.get(args.workload, 1)
+                sample = res.profs if ns <= len(res.profs) else build_workload(args.workload, 0, ns)[1]
+                out["cpu_baseline"] = cpu_baseline(res.rec, sample, min(ns, len(sample)), sgl=res.real_kind == 4, ncpu_procs=args.cpu_procs)
+                if "c5full" in extra and "error" not in extra["c5full"]:
+                    # configs[4] is the reference's "sgl" build: its own CPU leg (32 profiles x 2 views of the same workload)
+                    rec5, profs5, _, _, _ = build_workload("c5", 0, 128)
+                    extra["c5full"]["cpu_baseline"] = cpu_baseline(rec5, profs5, 64, sgl=True)
+        except Exception as e:
+            out["cpu_baseline"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
+    # evals count the lines that the 25 cm-1 rule rejects (the reference visits them, SURVEY 8(d)); the kernel never touches
+    # those: the rate of line shapes actually evaluated, where the branch census of the CPU leg gives the share
+    try:
+        cpf = out.get("cpu_baseline", {}).get("census", {}).get("cut_pass_frac")
+        if cpf:
+            out["shapes_evaluated_per_s"] = out["value"] * cpf
+            out["roofline"]["shapes_evaluated_per_s"] = out["value"] * cpf
+        for k, x in out.get("workloads", {}).items():
+            c2 = x.get("cpu_baseline", {}).get("census", {}).get("cut_pass_frac") if isinstance(x, dict) else None
+            if c2:
+                x["shapes_evaluated_per_s"] = x["value"] * c2
+    except Exception:
+        pass
+
+
 # ------------------------------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -943,10 +1143,15 @@ def main():
                     "(default 1 = every step, the north-star's one gather per pass); separates compute scaling from the collective")
     ap.add_argument("--cpu-procs", type=int, default=16, help="reference processes of the all-cores CPU leg (the GPU's share of the host)")
     ap.add_argument("--detail-file", default="", help="where the full record goes (default gpurun_out/bench_detail.json)")
+    ap.add_argument("--full", action="store_true", help="measure everything besides the headline: per-kernel times, the other "
+                    "workloads, counters and rooflines, drop-in latency, CPU baseline, the gather alone (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-workloads", default="", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-manifest", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.pmc_child:
         return pmc_child(args)
 
@@ -998,25 +1203,31 @@ def main():
     # takes the block as it is - the torch.stack + copy that used to feed it cost 15 us per step on the compute stream,
     # profiles/r05_gather_overlap.txt)
     plan = None
+    gather_us = None
     if world > 1:
         res.batch.pingpong = True
         plan = D.GatherPlan(nprof_total, res.batch.spectral_block(), field_major=True)
-        # what the collective costs by itself (nothing else on the GPU): 20 gathers of the real block, back to back
-        res.batch.step()
-        plan.start(res.batch.spectral_block())
-        plan.wait()
-        torch.cuda.synchronize()
-        dist.barrier()
-        t0 = time.perf_counter()
-        for _ in range(20):
+        if args.full:
+            # what the collective costs by itself (nothing else on the GPU): 20 gathers of the real block, back to back
+            res.batch.step()
             plan.start(res.batch.spectral_block())
             plan.wait()
-        torch.cuda.synchronize()
-        gather_us = torch.tensor([(time.perf_counter() - t0) / 20 * 1e6], dtype=torch.float64, device=dev)
-        dist.all_reduce(gather_us, op=dist.ReduceOp.MAX)
-        gather_us = float(gather_us.item())
+            torch.cuda.synchronize()
+            dist.barrier()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                plan.start(res.batch.spectral_block())
+                plan.wait()
+            torch.cuda.synchronize()
+            gather_us = torch.tensor([(time.perf_counter() - t0) / 20 * 1e6], dtype=torch.float64, device=dev)
+            dist.all_reduce(gather_us, op=dist.ReduceOp.MAX)
+            gather_us = float(gather_us.item())
+    snap = {}
+    dump = (lambda: snap.update(snapshot_outputs(output_arrays(res, plan)))) if args.dump_outputs and rank == 0 else None
+    # a plain run times the steps alone: no HIP events in the timed region, no untimed steps for the per-kernel split
     m = timed_steps(torch, dist, res, args.steps, args.warmup, args.min_seconds, plan=plan, graph=args.graph,
-                    events=not args.no_events, world=world, gather_every=max(1, args.gather_every))
+                    events=args.full and not args.no_events, world=world, gather_every=max(1, args.gather_every),
+                    kernel_split=args.full, after_timed=dump)
     dt = m["dt"]
     seen, ordinals = world, [local]
     if world > 1:
@@ -1035,7 +1246,6 @@ def main():
     rc = 0
     if rank == 0:
         value = e_all * args.steps / dt
-        avg_ms = m["kernel_ms"]["lines"]
         out = {
             "metric": "(wavenumber x layer x line) optical-depth evals/sec",
             "value": value,
@@ -1056,137 +1266,17 @@ def main():
             "data": "synthetic",
             "config": res.config(world, args.graph),
             "profiles_per_sec": nprof_total * args.steps / dt,
-            "kernel_ms_per_step": m["kernel_ms"],
         }
+        if "kernel_ms" in m:
+            out["kernel_ms_per_step"] = m["kernel_ms"]
         if world > 1:
             out["gather_every"] = max(1, args.gather_every)
-            out["gather_us_alone"] = gather_us
-        extra = {}
-        if world == 1 and not (args.no_extra or args.no_single) and args.workload == "c4":
-            # the other BASELINE configurations that fit one GPU, in the same line: each timed for >= min-seconds
-            for name, graph in (("c4shard", False), ("c3", False), ("c5", False), ("c5full", False), ("c2lc", False), ("c4brd", False),
-                                ("c2real", False), ("c2", True)):
-                try:
-                    r2 = Resident(name, 0, local, args.profiles_per_gpu, tmp=res.tmp)
-                    m2 = measure_by_duration(torch, r2, args.min_seconds, graph=graph)
-                    extra[name] = {"config": r2.config(1, graph), "dtype": "f64" if r2.real_kind == 8 else "f32",
-                                   "value": r2.e_step * m2["steps"] / m2["dt"], "unit": "evals/s", "steps": m2["steps"],
-                                   "ms_per_step": m2["dt"] / m2["steps"] * 1e3, "timed_ms": m2["dt"] * 1e3,
-                                   "profiles_per_sec": len(r2.profs) * m2["steps"] / m2["dt"],
-                                   "kernel_ms_per_step": m2["kernel_ms"], "_e_step": r2.e_step}
-                    if name == "c3" and not args.no_cpu_baseline:
-                        # the reference on a slice of configs[2] in the same run: ONE layer x every third wavenumber of the grid x the
-                        # 100000 lines = 3.3e8 evals, ~25 s on one core (no more extrapolation from the 50-channel
-                        # case; the rate per eval does not depend on the number of wavenumbers - the whole grid takes 72 s, 1.4e7 evals/s:
-                        # half the rate of the 500-line case, the reference's (39, 250000) arrays miss the caches)
-                        from monortm_amd import synth as _synth
-                        p3 = r2.profs[0]
-                        one = _synth.Profile(wn=p3.wn[::3], p=p3.p[:1], t=p3.t[:1], tz=p3.tz[:2], wkl=p3.wkl[:1], wbrodl=p3.wbrodl[:1],
-                                             clw=p3.clw[:1], irt=3, dvset=p3.dvset * 3)
-                        thin = _synth.Profile(wn=p3.wn[::50], p=p3.p[:1], t=p3.t[:1], tz=p3.tz[:2], wkl=p3.wkl[:1], wbrodl=p3.wbrodl[:1],
-                                              clw=p3.clw[:1], irt=3, dvset=p3.dvset * 50)
-                        try:
-                            extra[name]["cpu_baseline"] = cpu_baseline(r2.rec, [one], 1, census_profile=thin)
-                        except Exception as e:
-                            extra[name]["cpu_baseline"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
-                    r2.close()
-                except Exception as e:  # a secondary workload never takes the headline down
-                    extra[name] = {"error": f"{type(e).__name__}: {e}"}
-        # counters: live child run under rocprofv3 --pmc; else the committed summary if it matches this source tree
-        pmc, source = None, None
-        names = [args.workload] + [k for k in ("c4shard", "c3", "c5", "c5full", "c2lc", "c4brd", "c2real") if k in extra and "error" not in extra[k]]
-        nested = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "") \
-            or "HSA_TOOLS_LIB" in os.environ
-        if world == 1 and not args.no_pmc and not nested:
-            try:
-                t0 = time.perf_counter()
-                pmc = collect_pmc(names, args.profiles_per_gpu)
-                source = f"live: rocprofv3 --pmc child run of this script ({time.perf_counter() - t0:.0f} s, 3 launches per workload)"
-                if args.save_pmc:
-                    with open(args.save_pmc, "w") as f:
-                        json.dump({"csrc_hash": csrc_hash(), "profiles_per_gpu": args.profiles_per_gpu, "passes": PMC_PASSES,
-                                   "per_launch": pmc}, f, indent=1)
-            except Exception as e:
-                source = f"live collection failed: {type(e).__name__}: {str(e)[:200]}"
-        if pmc is None:
-            for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_per_launch.json")), reverse=True):
-                try:
-                    j = json.load(open(f))
-                    if j.get("csrc_hash") == csrc_hash() and j.get("profiles_per_gpu") == args.profiles_per_gpu:
-                        pmc = j["per_launch"]
-                        source = (source + "; " if source else "") + f"{os.path.relpath(f, ROOT)} (csrc hash matches)"
-                        break
-                except Exception:
-                    pass
-            else:
-                source = (source + "; " if source else "") + "no committed counter summary matches this source tree (stale files are refused)"
-        get = lambda w: (pmc or {}).get(w, {}).get("lines_kernel")  # noqa: E731
-        out["roofline"] = roofline_from_counters(get(args.workload), avg_ms, res.e_step, source, f32=res.real_kind == 4,
-                                                 nwn=res.profs[0].nwn)
-        out["roofline"]["launches"] = m["lines_launches"]
-        if out["roofline"]["frac"] is not None:
-            assert 0.0 < out["roofline"]["frac"] <= 1.0, out["roofline"]
-        out["roofline_hbm_model"] = hbm_model(avg_ms, res.e_step)
-        for name, x in extra.items():
-            if "error" in x:
-                continue
-            e2 = x.pop("_e_step")
-            if name != "c2":
-                x["roofline"] = roofline_from_counters(get(name), x["kernel_ms_per_step"]["lines"], e2, source, f32=x["dtype"] == "f32",
-                                                       nwn=x["config"]["wavenumbers"])
-                if name == "c3":
-                    x["roofline"]["note"] = ("kernel family = physics_kernel + far_plan_kernel + far_kernel (every level) + lines_kernel, all between the "
-                                             "'lines' events; the counted FP64 work per eval is ~1.4 flop where direct summation needs ~25: far lines are "
-                                             "expanded once per interval of wavenumbers (Chebyshev sums in levels) instead of being evaluated per "
-                                             "wavenumber, so frac prices far less work than round 4's did at twice the time")
-                if pmc and name in pmc:
-                    x["finish_kernel_counters"] = {k: v for k, v in pmc[name].get("finish_kernel", {}).items()
-                                                   if k in ("SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "GRBM_GUI_ACTIVE", "_dispatches_per_step")}
-            else:
-                x["launch"] = "hip graph replay"
-        if "c4shard" in extra and "error" not in extra["c4shard"]:
-            # `value` is configs[3] whole on this one GPU; the 128-profile share one of 8 GPUs holds runs at a lower rate (the
-            # fixed cost of a launch is spread over an eighth of the profiles): what the weak-scaling unit delivers
-            out["value_weak_shard"] = extra["c4shard"]["value"]
-            out["value_weak_shard_what"] = "the 128-profile share of one of 8 GPUs (1024 / 8), evals/s - see workloads.c4shard"
-        if extra:
-            out["workloads"] = extra
-            if "c2" in extra:
-                out["configs1_single_profile"] = extra["c2"]
-        if world == 1 and not (args.no_extra or args.no_single) and args.workload in ("c4", "c4shard", "c2lc"):
-            try:
-                out["dropin"] = dropin_latency(res.rec, res.profs[:128], res.tmp)
-            except Exception as e:
-                out["dropin"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                if args.workload == "c3":
-                    out["cpu_baseline"] = {"value": None, "unit": "evals/s", "cores": 1, "kind": "reference",
-                                           "sample": "not timed for c3 (about an hour of CPU work); see the c4shard line"}
-                else:
-                    # ~10-15 s of single-core work: 256 configs[3] profiles, 64 c5 runs (4x the channels), the one c2 profile
-                    ns = args.cpu_sample or {"c4": 256, "c4shard": 256, "c2lc": 64, "c5": 64, "c5full": 64}.get(args.workload, 1)
-                    sample = res.profs if ns <= len(res.profs) else build_workload(args.workload, 0, ns)[1]
-                    out["cpu_baseline"] = cpu_baseline(res.rec, sample, min(ns, len(sample)), sgl=res.real_kind == 4, ncpu_procs=args.cpu_procs)
-                    if "c5full" in extra and "error" not in extra["c5full"]:
-                        # configs[4] is the reference's "sgl" build: its own CPU leg (32 profiles x 2 views of the same workload)
-                        rec5, profs5, _, _, _ = build_workload("c5", 0, 128)
-                        extra["c5full"]["cpu_baseline"] = cpu_baseline(rec5, profs5, 64, sgl=True)
-            except Exception as e:
-                out["cpu_baseline"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
-        # evals count the lines that the 25 cm-1 rule rejects (the reference visits them); the kernel never touches
-        # those: the rate of line shapes actually evaluated, where the branch census of the CPU leg gives the share
-        try:
-            cpf = out.get("cpu_baseline", {}).get("census", {}).get("cut_pass_frac")
-            if cpf:
-                out["shapes_evaluated_per_s"] = out["value"] * cpf
-                out["roofline"]["shapes_evaluated_per_s"] = out["value"] * cpf
-            for k, x in out.get("workloads", {}).items():
-                c2 = x.get("cpu_baseline", {}).get("census", {}).get("cut_pass_frac") if isinstance(x, dict) else None
-                if c2:
-                    x["shapes_evaluated_per_s"] = x["value"] * c2
-        except Exception:
-            pass
+            if gather_us is not None:
+                out["gather_us_alone"] = gather_us
+        if args.full:
+            full_record(args, torch, res, m, out, local, world)
+        if args.dump_outputs:
+            write_outputs(snap, args.dump_outputs)
         emit(out, args.detail_file)
     res.close()
     if world > 1:

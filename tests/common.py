@@ -29,6 +29,17 @@ TIPS_ISONM = [6, 9, 18, 5, 6, 3, 3, 3, 2, 1, 2, 1, 3, 1, 2, 2, 1, 2, 5, 3, 2, 1,
 ALLMOL_SKIP = (19, 20)
 
 
+def dropin_env() -> dict:
+    """Environment for oracle/_ref/monortm_hipdrop_dbl, the reference's driver relinked against this package's library.  The
+    binary is a build product that may reach this tree from elsewhere (a copy or a link of oracle/_ref/), where its own
+    relative search path finds no library: the loader is pointed at this tree's libmonortm_hip.so."""
+    from monortm_amd import _build
+
+    assert os.path.exists(_build.LIB), f"{_build.LIB} not built"
+    old = os.environ.get("LD_LIBRARY_PATH")
+    return {**os.environ, "LD_LIBRARY_PATH": _build.LIBDIR + (os.pathsep + old if old else "")}
+
+
 def golden_names(single_precision: bool = False):
     """Double-precision reference fixtures by default; the `sgl_*` ones come from the reference's "sgl" build."""
     names = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))

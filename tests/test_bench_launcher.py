@@ -90,6 +90,34 @@ def test_compact_line_of_a_real_record():
     assert c["workloads"]["c5full"]["frac"] == pytest.approx(full["workloads"]["c5full"]["roofline"]["frac"], rel=1e-5)
 
 
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_sample_is_seeded_and_bounded():
+    """--dump-outputs: small arrays go out whole, large ones as a sample whose elements depend on the array's size only; the
+    dump never exceeds its byte limit and keeps the arrays' float dtype."""
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(3)
+    arrays = {"tb": torch.rand(1024, 50, dtype=torch.float64, generator=g), "od": torch.rand(1024, 64, 50, dtype=torch.float64, generator=g),
+              "od_by_mol": torch.rand(1024, 64, 7, 50, dtype=torch.float64, generator=g), "od_clw": torch.rand(64, 50, generator=g)}
+    a, b = bench.snapshot_outputs(arrays), bench.snapshot_outputs({k: v.clone() for k, v in arrays.items()})
+    assert set(a) == {"tb", "od", "od_by_mol_sample", "od_clw"}
+    assert np.array_equal(a["od"], arrays["od"].numpy()) and a["od_clw"].dtype == np.float32
+    assert all(np.array_equal(a[k], b[k]) for k in a) and sum(x.nbytes for x in a.values()) <= bench.DUMP_LIMIT
+    arrays["od_by_mol"] += 1.0                            # other values, same elements
+    c = bench.snapshot_outputs(arrays)
+    assert np.array_equal(c["od_by_mol_sample"], a["od_by_mol_sample"] + 1.0)
+
+
 def test_world_size_mismatch_is_refused():
     r = _run(["--gpus", "4", "--steps", "1"], {"MONORTM_BENCH_STUB": "1", "WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 2 and "WORLD_SIZE=2" in r.stderr
@@ -101,7 +129,7 @@ def test_world_size_mismatch_is_refused():
 def test_bench_two_ranks_gather_every_second_step():
     """--gather-every 2 with the real step on two ranks sharing the card: the block a gather reads is not rewritten while it is in
     flight (timed_steps waits before the step after next), the line says how often it gathered and what the gather costs alone."""
-    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--min-seconds", "0.2", "--gather-every", "2", "--no-pmc", "--no-cpu-baseline", "--no-extra"],
+    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--min-seconds", "0.2", "--gather-every", "2", "--full", "--no-pmc", "--no-cpu-baseline", "--no-extra"],
              {"MONORTM_BENCH_BACKEND": "gloo"}, timeout=360)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     j = json.loads(r.stdout.rstrip("\n").splitlines()[-1])
@@ -116,7 +144,7 @@ def test_bench_two_ranks_on_one_card_is_the_drivers_command():
     starts its two ranks itself, both on the one card of the test box (MONORTM_BENCH_BACKEND=gloo: RCCL refuses two ranks on
     one device), each takes its 512-profile block of configs[3], the spectral outputs are gathered to rank 0 every step by
     GatherPlan, and rank 0 prints ONE line: strong scaling, two ranks seen, evals of BOTH ranks in `value`."""
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--min-seconds", "0.2", "--no-pmc", "--no-cpu-baseline", "--no-extra"],
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--min-seconds", "0.2", "--full", "--no-pmc", "--no-cpu-baseline", "--no-extra"],
              {"MONORTM_BENCH_BACKEND": "gloo"}, timeout=360)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -131,3 +159,35 @@ def test_bench_two_ranks_on_one_card_is_the_drivers_command():
     evals = j["value"] * j["ms_per_step"] * 1e-3
     assert abs(evals - 1024 * 50 * 64 * 500) <= 1e-5 * evals, evals   # (the compact line carries six significant digits)
     assert j["profiles_per_sec"] > 0 and j["dtype"] == "f64" and "stub" not in j
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain run is the headline alone (no per-kernel split, no other workloads, counters or CPU legs), its line reports the
+    steps it was given, and --dump-outputs writes what the last timed step computed: the brightness temperatures of configs[3]
+    agree with the CPU oracle on the same seeded profiles."""
+    import numpy as np
+
+    from monortm_amd import tape3
+    from oracle.pyoracle import Oracle
+
+    d = tmp_path / "dump"
+    r = _run(["--steps", "3", "--warmup", "1", "--min-seconds", "0.2", "--dump-outputs", str(d), "--detail-file", str(tmp_path / "d.json")],
+             {}, timeout=600)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    j = json.loads(r.stdout.rstrip("\n").splitlines()[-1])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["dtype"] == "f64" and j["higher_is_better"] is True
+    assert not {"kernel_ms_per_step", "workloads", "roofline", "cpu_baseline", "dropin_ms_per_profile"} & set(j), sorted(j)
+    files = {p.name: np.load(p) for p in d.glob("*.npy")}
+    assert {"tb.npy", "rad.npy", "trtot.npy", "tmr.npy", "rup.npy", "rdn.npy", "tmpsfc.npy"} <= set(files), sorted(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in d.glob("*.npy")) <= 64e6
+    tb = files["tb.npy"]
+    assert tb.shape == (1024, 50) and np.isfinite(tb).all()
+    rec, profs, _, _, _ = _bench_module().build_workload("c4", 0, 128)
+    t3 = str(tmp_path / "TAPE3")
+    tape3.write_tape3(t3, rec)
+    orc = Oracle(t3, profs[0].wn[0], profs[0].wn[-1])
+    for i in (0, 517, 1023):
+        np.testing.assert_allclose(tb[i], orc.run(profs[i]).tb, rtol=1e-6)
+    orc.close()

@@ -24,6 +24,13 @@ def harness():
     return info["harness"]
 
 
+def run_harness(exe, cwd, case, tape3_path, out, **kw):
+    """Run examples/harness.f90 (drop-in or reference build) in `cwd`.  The harness hands MODM at most 80 characters of the
+    TAPE3 path (HFILE), so the files are named relative to the run directory: short wherever the temporary directory lies."""
+    return subprocess.run([exe, *(os.path.relpath(f, cwd) for f in (case, tape3_path, out))], cwd=cwd, capture_output=True,
+                          text=True, **kw)
+
+
 @pytest.mark.parametrize("name", golden_names())
 def test_fortran_shim_reproduces_reference(name, workdir, harness):
     g = Golden(name, workdir)
@@ -32,7 +39,7 @@ def test_fortran_shim_reproduces_reference(name, workdir, harness):
     caseio.write_case(case, g.profiles)
     # IXSECT = 1 fixtures: FSCDXS and the xs files are opened by name in the working directory (src/monortm_sub.F90:1341,:1662)
     cwd = getattr(g, "xs_dir", None) or workdir
-    r = subprocess.run([harness, case, g.tape3, out], cwd=cwd, capture_output=True, text=True, timeout=300)
+    r = run_harness(harness, cwd, case, g.tape3, out, timeout=300)
     assert r.returncode == 0 and "HARNESS_SECONDS" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     dumps = caseio.read_dump(out)
     assert len(dumps) == len(g.expected)
@@ -50,7 +57,7 @@ def test_single_precision_caller(workdir):
         case = os.path.join(workdir, f"case_{name}.bin")
         out = os.path.join(workdir, f"out_{name}.bin")
         caseio.write_case(case, g.profiles)
-        r = subprocess.run([exe, case, g.tape3, out], cwd=workdir, capture_output=True, text=True, timeout=300)
+        r = run_harness(exe, workdir, case, g.tape3, out, timeout=300)
         assert r.returncode == 0 and "HARNESS_SECONDS" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
         for i, (got, exp) in enumerate(zip(caseio.read_dump(out), g.expected)):
             # (sgl_real_like[2]: the reference's REAL*4 sums over 3300 lines carry ~1e-3 of noise, tests/test_hip_parity.py SGL_LONG_SUMS)
@@ -62,8 +69,7 @@ def test_fortran_shim_stops_like_the_reference(workdir, harness):
     g = Golden("cntnm_factors", workdir)
     case = os.path.join(workdir, "case_stop.bin")
     caseio.write_case(case, g.profiles[:1])
-    r = subprocess.run([harness, case, os.path.join(workdir, "NO_SUCH_TAPE3"), os.path.join(workdir, "o.bin")],
-                       cwd=workdir, capture_output=True, text=True, timeout=120)
+    r = run_harness(harness, workdir, case, os.path.join(workdir, "NO_SUCH_TAPE3"), os.path.join(workdir, "o.bin"), timeout=120)
     assert r.returncode != 0 or "HARNESS_SECONDS" not in r.stdout
     assert "ERROR OPENING HITRAN FILE" in (r.stdout + r.stderr)
 
@@ -76,8 +82,7 @@ def test_rtm_before_first_modm_still_loads_the_line_file(workdir, harness):
     case = os.path.join(workdir, "case_rtmfirst.bin")
     out = os.path.join(workdir, "out_rtmfirst.bin")
     caseio.write_case(case, g.profiles)
-    r = subprocess.run([harness, case, g.tape3, out], cwd=workdir, capture_output=True, text=True, timeout=300,
-                       env={**os.environ, "HARNESS_RTM_FIRST": "1"})
+    r = run_harness(harness, workdir, case, g.tape3, out, timeout=300, env={**os.environ, "HARNESS_RTM_FIRST": "1"})
     assert r.returncode == 0 and "HARNESS_SECONDS" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     for i, (got, exp) in enumerate(zip(caseio.read_dump(out), g.expected)):
         assert got.o_by_mol.max() > 0
@@ -93,7 +98,7 @@ def test_shim_writes_the_line_file_summary_to_the_log_unit(workdir, harness):
     caseio.write_case(case, g.profiles[:1])
     run = os.path.join(workdir, "log_hip")
     os.makedirs(run, exist_ok=True)
-    r = subprocess.run([harness, case, g.tape3, os.path.join(run, "o.bin")], cwd=run, capture_output=True, text=True, timeout=300)
+    r = run_harness(harness, run, case, g.tape3, os.path.join(run, "o.bin"), timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
     def block(path):
@@ -109,7 +114,7 @@ def test_shim_writes_the_line_file_summary_to_the_log_unit(workdir, harness):
     if os.path.exists(ref):
         rr = os.path.join(workdir, "log_ref")
         os.makedirs(rr, exist_ok=True)
-        r2 = subprocess.run([ref, case, g.tape3, os.path.join(rr, "o.bin")], cwd=rr, capture_output=True, text=True, timeout=600)
+        r2 = run_harness(ref, rr, case, g.tape3, os.path.join(rr, "o.bin"), timeout=600)
         assert r2.returncode == 0, r2.stdout[-2000:] + r2.stderr[-2000:]
         assert got == block(os.path.join(rr, "HARNESS.LOG"))
 
@@ -134,7 +139,7 @@ def test_ragged_cross_section_files_packed_like_the_python_loader(workdir, harne
     tape3.write_tape3(t3, synth.synthetic_lines(40, seed=3, vlo=760.0, vhi=870.0))
     case, out = os.path.join(workdir, "case_ragged.bin"), os.path.join(workdir, "out_ragged.bin")
     caseio.write_case(case, [pr])
-    r = subprocess.run([harness, case, t3, out], cwd=xd, capture_output=True, text=True, timeout=300)
+    r = run_harness(harness, xd, case, t3, out, timeout=300)
     assert r.returncode == 0 and "HARNESS_SECONDS" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     f = caseio.read_dump(out)[0]
     rt = api.MonoRTM(t3, wn[0], wn[-1])

@@ -5,6 +5,8 @@ oracle/_ref/harness_ref_dbl = the reference compiled from /root/reference by amd
 Two independent implementations of IEEE double arithmetic in the same operation order agree
 to a few ulp; the bound used here (1e-10) is four orders tighter than the product tolerance.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -141,7 +143,9 @@ def test_oracle_matches_reference_on_fuzz_cases(seed, workdir):
     t3, pr = random_case(seed, workdir)
     case, out = f"{workdir}/fz{seed}.bin", f"{workdir}/fz{seed}.out"
     caseio.write_case(case, [pr])
-    r = subprocess.run([h, case, t3, out], cwd=workdir, capture_output=True, text=True, timeout=600)
+    # names relative to the run directory: the harness hands the reference at most 80 characters of the TAPE3 path (hfile)
+    r = subprocess.run([h, *(os.path.relpath(f, workdir) for f in (case, t3, out))], cwd=workdir, capture_output=True, text=True,
+                       timeout=600)
     assert r.returncode == 0, r.stdout[-2000:]
     exp = caseio.read_dump(out)[0]
     got = Oracle(t3, pr.wn[0], pr.wn[-1]).run(pr)
@@ -176,7 +180,9 @@ def test_oracle_matches_reference_on_all_molecule_fuzz(seed, workdir):
                          clw=pr.clw[:1], irt=3)
     case, out = f"{workdir}/fm{seed}.bin", f"{workdir}/fm{seed}.out"
     caseio.write_case(case, [warm, pr])
-    r = subprocess.run([h, case, t3, out], cwd=workdir, capture_output=True, text=True, timeout=600)
+    # names relative to the run directory: the harness hands the reference at most 80 characters of the TAPE3 path (hfile)
+    r = subprocess.run([h, *(os.path.relpath(f, workdir) for f in (case, t3, out))], cwd=workdir, capture_output=True, text=True,
+                       timeout=600)
     assert r.returncode == 0, r.stdout[-2000:]
     exp = caseio.read_dump(out)[1]
     assert np.isfinite(exp.o_by_mol).all() and np.isfinite(exp.tb).all()

@@ -12,7 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from common import ROOT
+from common import ROOT, dropin_env
 
 pytestmark = pytest.mark.gpu
 DECKS = os.path.join(ROOT, "tests", "golden", "decks")
@@ -113,7 +113,7 @@ def test_reference_driver_with_hip_modules(case, tmp_path):
     src = os.path.join(DECKS, case)
     stage_inputs(src, tmp_path)
     shutil.copy(os.path.join(DECKS, "TAPE3_synthetic"), tmp_path / "TAPE3")
-    r = subprocess.run([EXE], cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([EXE], cwd=tmp_path, capture_output=True, text=True, timeout=600, env=dropin_env())
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     check_out(tmp_path / "MONORTM.OUT", os.path.join(src, "MONORTM.OUT.expected"))
     check_layer_od(tmp_path, src)

@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from common import ROOT
+from common import ROOT, dropin_env
 
 pytestmark = pytest.mark.gpu
 
@@ -77,7 +77,7 @@ def test_reference_driver_with_dropin_modm_handles_cross_sections(tmp_path):
     for exe, tag in ((drop, "drop"), (own, "own")):
         d = str(tmp_path / tag)
         tool.build_deck(d, ixsect=1)
-        r = subprocess.run([exe], cwd=d, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([exe], cwd=d, capture_output=True, text=True, timeout=600, env=dropin_env())
         assert r.returncode == 0 and os.path.getsize(os.path.join(d, "MONORTM.OUT")) > 0, (r.stdout + r.stderr)[-2000:]
         cols.append(_columns(os.path.join(d, "MONORTM.OUT")))
     assert cols[0].shape == cols[1].shape and np.all(cols[0][:, -1] > 0)

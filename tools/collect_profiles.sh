@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the measurement artefacts of a round on the GPU box (run through gpurun from the repo root):
 #   tools/collect_profiles.sh TAG     e.g. TAG=r02_a
-# 1. the default bench.py command (headline + c3 / c5 / c2lc / single profile + drop-in latency + CPU baseline), with
+# 1. bench.py --full (headline + c3 / c5 / c2lc / single profile + drop-in latency + CPU baseline), with
 #    its live counter collection saved   -> gpurun_out/TAG_bench.json (compact line), TAG_bench_detail.json, TAG_pmc_per_launch.json
 # 2. per workload: rocprofv3 --kernel-trace --stats of `bench.py --workload W --no-extra --no-pmc --no-cpu-baseline`
 #    (the average duration of lines_kernel must agree with roofline.avg_launch_ms of the same workload in 1.)
@@ -15,7 +15,7 @@ OUT=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p $OUT
 # (stdout = the compact line the driver parses; the full record goes to the detail file)
-timeout -k 10 700 python3 bench.py --save-pmc $OUT/${TAG}_pmc_per_launch.json --detail-file $OUT/${TAG}_bench_detail.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 1
+timeout -k 10 700 python3 bench.py --full --save-pmc $OUT/${TAG}_pmc_per_launch.json --detail-file $OUT/${TAG}_bench_detail.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 1
 for W in c4 c4shard c3 c5 c5full c2lc c4brd c2real; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace_$W -- \
     python3 bench.py --workload $W --no-extra --no-pmc --no-cpu-baseline > $OUT/${TAG}_trace_$W.log 2>&1 || exit 1
