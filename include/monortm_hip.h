@@ -201,6 +201,69 @@ int monortm_hip_rtm_dev(void *ctx, int nprof, int nwn, const double *wn, const i
                         const monortm_real *reflc, monortm_real *RUP, monortm_real *RDN, monortm_real *TRTOT,
                         monortm_real *RAD, monortm_real *TB, monortm_real *TMR, void *stream);
 
+/* ---- Jacobians for retrievals (no reference counterpart: "CURRENTLY MONORTM DOES NOT HANDLE DERIVATIVES",
+ * src/monortm_sub.F90:199).  DESIGN.md section 3.6 has the method and the error budget.
+ *   Inputs: the arguments of monortm_hip_modm / monortm_hip_rtm.  K holds PARTIAL derivatives with respect to them, every other
+ *   input fixed (d/dT_k holds WKL, P and TZ constant); callers chain to their own state vector.
+ *   quantity = 1: q = TB (needs RAD > 0);  quantity = 0: q = RAD.
+ *   K_T   [nprof][nlay_max][nwn]     dq/dT_k, layer temperature: the Planck term of RTM and, in monortm_hip_jacobian, its effect on O
+ *                                    through MODM (lines, continuum, cloud);  monortm_hip_rtm_jac: the Planck term only
+ *   K_TZ  [nprof][nlay_max + 1][nwn] dq/dTZ_j, level temperature (RTM only, analytic; TZ_0 enters only RDN of layer 1, TZ_nlay only
+ *                                    RUP: 0 for irt = 3)
+ *   K_W   [nprof][nlay_max][njac][nwn] dq/d ln WKL_k,jac_mol[i] = WKL dq/dWKL (0 where WKL = 0)
+ *   K_CLW [nprof][nlay_max][nwn]     dq/dCLW_k; the cloud optical depth is linear in CLW (ODCLW_TKC, src/CloudOptProp.f90:18-20,49),
+ *                                    dO_k/dCLW_k = ODCLW_TKC(wn, T_k, 1) in closed form (right at CLW = 0 too)
+ *   K_O   [nprof][nlay_max][nwn]     dq/dO_k, the optical-depth Jacobian (to chain cross sections or species outside jac_mol)
+ *   K_SFC [nprof][3][nwn]            dq/dTMPSFC, dq/dEMISS, dq/dREFLC; the TMPSFC term is 0 for irt = 2, 3 (RTM replaces TMPSFC by
+ *                                    2.75 K there, RTMmono.f90:113-124)
+ *   Wavenumber axis fastest; entries of layers >= nlay[p] and levels > nlay[p] are 0.  tmpsfc is input only (not set to 2.75).
+ * The derivatives of RTM are the exact adjoint of RAD_UP_DN + RTM.  Those of MODM are central differences: layers do not interact
+ * in MODM (src/modm.f90:200-272), so ONE MODM evaluation with every layer's T shifted by +h gives O(T_k + h) for all k at once -
+ * 2 evaluations per variable, not 2 nlay.  Half-steps (monortm_hip_set_option "jac_dt" / "jac_dlnw"): */
+#define MONORTM_JAC_DT 1e-2   /* K: T +- h */
+#define MONORTM_JAC_DLNW 1e-4 /* WKL (1 +- eps) */
+/* O is only piecewise smooth in T (line-shape switches at zeta > 0.99 and |v - v0| > 100 HWHM_D, src/modm.f90:427): a difference
+ * across a switch reports the switch.  T +- h must stay within 70-3000 K (MONORTM_ETEMP otherwise).
+ * Cross-section molecules (IXSECT = 1) are not part of monortm_hip_jacobian: chain K_O with their dO.
+ *
+ * RTM adjoint only, given O (e.g. from monortm_hip_modm): RAD, TB, K_O, K_T (Planck terms only), K_TZ, K_SFC.  real_kind 8 and 4
+ * (double arithmetic either way).  Host buffers; a multi-device context shards the profiles like monortm_hip_rtm. */
+int monortm_hip_rtm_jac(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                        int quantity, const monortm_real *T, const monortm_real *TZ, const monortm_real *O,
+                        const monortm_real *tmpsfc, const monortm_real *emiss, const monortm_real *reflc,
+                        monortm_real *RAD, monortm_real *TB, monortm_real *K_O, monortm_real *K_T, monortm_real *K_TZ,
+                        monortm_real *K_SFC);
+/* The same on device pointers (nlay, irt, tmpsfc device arrays), asynchronous on `stream`; one-device context. */
+int monortm_hip_rtm_jac_dev(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                            int quantity, const monortm_real *T, const monortm_real *TZ, const monortm_real *O,
+                            const monortm_real *tmpsfc, const monortm_real *emiss, const monortm_real *reflc,
+                            monortm_real *RAD, monortm_real *TB, monortm_real *K_O, monortm_real *K_T, monortm_real *K_TZ,
+                            monortm_real *K_SFC, void *stream);
+
+/* MODM + RTM with Jacobians: the forward outputs of the base state (O, RAD, TB) and K_T (total), K_TZ, K_W, K_CLW, K_O (may be
+ * NULL), K_SFC.  jac_mol[njac]: HOST array of 1-based molecules (<= nmol, no duplicates; njac = 0: no K_W, which may then be NULL)
+ * in both variants.  real_kind 8 only (MONORTM_EUNSUPPORTED otherwise).  Host buffers: shards like monortm_hip_modm.
+ * Errors: MONORTM_EARG for a NULL required array, a bad quantity, a bad jac_mol; MONORTM_ETEMP when T +- h leaves 70-3000 K. */
+int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
+                         int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
+                         const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac, double sclcpl,
+                         double sclhw, double y0res, int ibrd, const int *irt, const monortm_real *TZ,
+                         const monortm_real *tmpsfc, const monortm_real *emiss, const monortm_real *reflc, int quantity,
+                         int njac, const int *jac_mol, monortm_real *O, monortm_real *RAD, monortm_real *TB,
+                         monortm_real *K_T, monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_O,
+                         monortm_real *K_SFC);
+/* The same on device pointers, asynchronous on `stream`; one-device context.  wn_ends as for monortm_hip_modm_dev (given: no
+ * synchronisation).  Device-side failures (temperature range) surface through monortm_hip_check.  After one call, a second of the
+ * same shapes allocates nothing (graph capture). */
+int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
+                             int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
+                             const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac /*host*/,
+                             double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const monortm_real *TZ,
+                             const monortm_real *tmpsfc, const monortm_real *emiss, const monortm_real *reflc, int quantity,
+                             int njac, const int *jac_mol /*host*/, monortm_real *O, monortm_real *RAD, monortm_real *TB,
+                             monortm_real *K_T, monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW,
+                             monortm_real *K_O, monortm_real *K_SFC, const double *wn_ends, void *stream);
+
 /* Device-side failure flags raised by the kernels of earlier *_dev calls (temperature range, SD-Voigt
  * sign): synchronises `stream`, returns MONORTM_OK or the first error and clears the flags. */
 int monortm_hip_check(void *ctx, void *stream);
@@ -220,6 +283,8 @@ int monortm_hip_profile(void *ctx, int enable);
  *   "far_levels" = "auto" | 0..6: dense grids (>= 4 tiles of wavenumbers) - levels of intervals (tiles, pairs of tiles, fours, eights ...)
  *       whose far lines far_kernel expands before the line sum; 0 = the far field of a tile is formed inside the line-sum kernel;
  *   "lines_kernel" = "auto" | "wn" (the one kernel; the round-3 alternatives "state" / "p" were removed in round 5).
+ *   "jac_dt" = "auto" | a finite double > 0 (K; MONORTM_JAC_DT), "jac_dlnw" = "auto" | a finite double in (0, 1) (MONORTM_JAC_DLNW):
+ *       the half-steps of the Jacobian's central differences (monortm_hip_jacobian).
  * Values are parsed strictly (whole string, in range).  Unknown names / values: MONORTM_EARG. */
 int monortm_hip_set_option(void *ctx, const char *name, const char *value);
 int monortm_hip_kernel_time(void *ctx, int kernel, double *total_ms, long long *launches);

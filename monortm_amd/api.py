@@ -58,12 +58,33 @@ SYMBOLS = {
                                        _vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "monortm_hip_rtm_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "monortm_hip_rtm_jac": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 12),
+    "monortm_hip_rtm_jac_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 13),
+    "monortm_hip_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]
+                             + [_vp] * 9),
+    "monortm_hip_jacobian_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]
+                                 + [_vp] * 11),
     "monortm_hip_check": (C.c_int, [_vp, _vp]),
     "monortm_hip_profile": (C.c_int, [_vp, C.c_int]),
     "monortm_hip_kernel_time": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_longlong)]),
 }
 
 _LIB = None
+
+# half-steps of the Jacobian's central differences (include/monortm_hip.h MONORTM_JAC_DT / MONORTM_JAC_DLNW; set_option "jac_dt" /
+# "jac_dlnw" changes them per context)
+JAC_DT = 1e-2
+JAC_DLNW = 1e-4
+JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_sfc")
+
+
+def _quantity(q) -> int:
+    """'tb' -> 1, 'rad' -> 0; an int is passed through unchanged (the C ABI checks it)."""
+    if isinstance(q, str):
+        return {"tb": 1, "rad": 0}[q.lower()]
+    return int(q)
 
 
 class MonoRTMError(RuntimeError):
@@ -241,6 +262,66 @@ class MonoRTM:
                             float(ts[i]), None if ODX is None else ODX[i, :n]))
         return out
 
+    # ---- Jacobians (monortm_hip_rtm_jac / monortm_hip_jacobian) --------------------------------------
+    def _pack_rtm(self, profiles: list[Profile]):
+        nprof, nwn = len(profiles), profiles[0].nwn
+        nlay = np.array([p.nlay for p in profiles], np.int32)
+        lm = int(nlay.max())
+        dt = self.dtype
+        T = np.zeros((nprof, lm), dt)
+        TZ = np.zeros((nprof, lm + 1), dt)
+        for i, p in enumerate(profiles):
+            T[i, : p.nlay] = p.t
+            TZ[i, : p.nlay + 1] = p.tz
+        irt = np.array([p.irt for p in profiles], np.int32)
+        ts = np.array([p.tmpsfc for p in profiles], dt)
+        em = _np(np.stack([p.emiss for p in profiles]), dt)
+        rf = _np(np.stack([p.reflc for p in profiles]), dt)
+        return nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf
+
+    def rtm_jacobian(self, profiles: list[Profile], O: np.ndarray, quantity="tb") -> dict:
+        """The adjoint of RTM alone, given the optical depths O [nprof, nlay_max, nwn]: dict of rad, tb [nprof, nwn], k_o, k_t (Planck
+        term only) [nprof, nlay_max, nwn], k_tz [nprof, nlay_max + 1, nwn], k_sfc [nprof, 3, nwn] (d/dTMPSFC, d/dEMISS, d/dREFLC).
+        quantity: "tb" or "rad" (what q is)."""
+        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
+        dt = self.dtype
+        O = _np(O, dt)
+        out = dict(rad=np.zeros((nprof, nwn), dt), tb=np.zeros((nprof, nwn), dt), k_o=np.zeros((nprof, lm, nwn), dt),
+                   k_t=np.zeros((nprof, lm, nwn), dt), k_tz=np.zeros((nprof, lm + 1, nwn), dt), k_sfc=np.zeros((nprof, 3, nwn), dt))
+        wn = _np(profiles[0].wn)
+        self._chk(self.lib.monortm_hip_rtm_jac(self.ctx, nprof, nwn, _ptr(wn), _ptr(nlay), lm, _ptr(irt), _quantity(quantity), _ptr(T),
+                                               _ptr(TZ), _ptr(O), _ptr(ts), _ptr(em), _ptr(rf), *[_ptr(out[k]) for k in
+                                                                                                  ("rad", "tb", "k_o", "k_t", "k_tz", "k_sfc")]))
+        return out
+
+    def jacobian(self, profiles: list[Profile], mols=(1,), quantity="tb") -> dict:
+        """MODM + RTM with Jacobians for a batch (real_kind 8): dict of o [nprof, nlay_max, nwn], rad, tb [nprof, nwn], k_t, k_clw, k_o
+        [nprof, nlay_max, nwn], k_tz [nprof, nlay_max + 1, nwn], k_w [nprof, nlay_max, len(mols), nwn] (d/d ln WKL of mols, 1-based)
+        and k_sfc [nprof, 3, nwn].  Partial derivatives with respect to the MODM / RTM inputs (see include/monortm_hip.h)."""
+        p0 = profiles[0]
+        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
+        nmol, dt = p0.nmol, self.dtype
+
+        def pack(get, width=None):
+            out = np.zeros((nprof, lm) if width is None else (nprof, lm, width), dt)
+            for i, p in enumerate(profiles):
+                out[i, : p.nlay] = get(p)
+            return out
+
+        P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
+        WKL = pack(lambda p: p.wkl, nmol)
+        jm = np.ascontiguousarray(np.asarray(mols, np.int32).reshape(-1))
+        nj = len(jm)
+        out = dict(o=np.zeros((nprof, lm, nwn), dt), rad=np.zeros((nprof, nwn), dt), tb=np.zeros((nprof, nwn), dt),
+                   k_t=np.zeros((nprof, lm, nwn), dt), k_tz=np.zeros((nprof, lm + 1, nwn), dt), k_w=np.zeros((nprof, lm, nj, nwn), dt),
+                   k_clw=np.zeros((nprof, lm, nwn), dt), k_o=np.zeros((nprof, lm, nwn), dt), k_sfc=np.zeros((nprof, 3, nwn), dt))
+        wn, fac = _np(p0.wn), _np(p0.cntnm)
+        self._chk(self.lib.monortm_hip_jacobian(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T), _ptr(CLW),
+                                                _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, _ptr(irt), _ptr(TZ),
+                                                _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj, _ptr(jm) if nj else None,
+                                                *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS]))
+        return out
+
     # ---- the C-ABI gather of a profile-sharded job (RCCL; what a C / Fortran caller uses instead of torch.distributed) ------
     @staticmethod
     def comm_unique_id() -> bytes:
@@ -366,6 +447,32 @@ class DeviceBatch:
         rt._chk(lib.monortm_hip_rtm_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), d(self.nlay), self.lm, d(self.irt), p0.iout,
                                         d(self.T), d(self.TZ), d(self.O), d(self.tmpsfc), d(self.emiss), d(self.reflc),
                                         d(self.RUP), d(self.RDN), d(self.TRTOT), d(self.RAD), d(self.TB), d(self.TMR), sp))
+
+    # ---- Jacobians on the resident batch (monortm_hip_jacobian_dev) ---------------------------------------------------------------
+    def jacobian(self, mols=(1,), quantity="tb", stream=None) -> dict:
+        """K of the batch's profiles on the current (or the given) stream, asynchronously: a dict of torch tensors with the fields and
+        shapes of MonoRTM.jacobian, allocated at the first call for (mols, quantity) and overwritten by every later one (so that a
+        graph capture of the call replays into the same tensors).  TMPSFC is the profiles' own (input only)."""
+        t = self.torch
+        key = (tuple(int(m) for m in mols), _quantity(quantity))
+        cache = self.__dict__.setdefault("_jac", {})
+        if key not in cache:
+            f64 = t.float32 if self.rt.real_kind == 4 else t.float64
+            z = lambda *s: t.zeros(*s, dtype=f64, device=self.dev)  # noqa: E731
+            n, lm, nw, nj = self.nprof, self.lm, self.nwn, len(key[0])
+            cache[key] = (dict(o=z(n, lm, nw), rad=z(n, nw), tb=z(n, nw), k_t=z(n, lm, nw), k_tz=z(n, lm + 1, nw), k_w=z(n, lm, nj, nw),
+                               k_clw=z(n, lm, nw), k_o=z(n, lm, nw), k_sfc=z(n, 3, nw)), np.ascontiguousarray(key[0], np.int32))
+        out, jm = cache[key]
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        p0, lib, rt = self.p0, self.rt.lib, self.rt
+        d = lambda x: _vp(x.data_ptr())  # noqa: E731
+        nj = len(jm)
+        rt._chk(lib.monortm_hip_jacobian_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol, d(self.P),
+                                             d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl, p0.sclhw, p0.y0res,
+                                             p0.ibrd, d(self.irt), d(self.TZ), d(self.tmpsfc0), d(self.emiss), d(self.reflc), key[1], nj,
+                                             _ptr(jm) if nj else None, *[d(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS],
+                                             _ptr(self.wn_ends), _vp(s.cuda_stream)))
+        return out
 
     # ---- HIP graph: the three launches of a step recorded once, replayed with a single call ------------------
     def capture(self):

@@ -42,6 +42,7 @@ struct Ctx {
         int lines_ms = -1;        // -1 = chosen per call; 0 = never lines_ms_kernel; 1 = whenever its layout fits (tests, measurements)
         int ms_ablate = 0;        // timing experiments: lines_ms_kernel without its later stages (wrong results)
         int ms_items = 0;         // 0 = chosen per call; 64 / 128 / 192 (state, line) items per chunk of lines_ms_kernel
+        double jac_dt = MONORTM_JAC_DT, jac_dlnw = MONORTM_JAC_DLNW;   // half-steps of the Jacobian's central differences
     } opt;
     void *comm = nullptr;     // RCCL communicator of a multi-process job (monortm_hip_comm_init), one rank per context
     int comm_rank = 0, comm_world = 1;
@@ -80,7 +81,11 @@ struct Ctx {
         void *p = nullptr;
         size_t bytes = 0;
     };
-    Stage stage[8];  // modm: host in, device in, host out, device out; rtm: the same four
+    Stage stage[12];  // modm: host in, device in, host out, device out; rtm: the same four; the Jacobian entries: the same four
+    // monortm_hip_jacobian_dev: the MODM inputs and optical depths of the base and the perturbed states, and the outputs of MODM
+    // that the Jacobian does not use, grown on demand and kept (a second call of the same shapes allocates nothing)
+    void *jac_ws = nullptr;
+    size_t jac_ws_bytes = 0;
     // The host-buffer entry points run on their own stream: one asynchronous upload, the kernels, one asynchronous
     // download (+ the 4-byte error flag) and a single synchronisation per call.
     hipStream_t hs = nullptr;
@@ -158,11 +163,15 @@ int set_option(Ctx *c, const char *name, const char *value) {
     const std::string n = name ? name : "", v = value ? value : "";
     const bool autov = v.empty() || v == "auto";
     long iv = 0;
-    bool isint = false;
+    double dv = 0.;
+    bool isint = false, isdbl = false;
     if (!autov) {
         char *end = nullptr;
         iv = strtol(v.c_str(), &end, 10);
         isint = end && end != v.c_str() && *end == '\0';
+        end = nullptr;
+        dv = strtod(v.c_str(), &end);
+        isdbl = end && end != v.c_str() && *end == '\0';
     }
     if (n == "nslice" && (autov || (isint && iv >= 1 && iv <= 16))) c->opt.nslice = autov ? 0 : (int)iv;
     else if (n == "fair" && (autov || (isint && (iv == 0 || iv == 1)))) c->opt.fair = autov ? -1 : (int)iv;
@@ -175,6 +184,11 @@ int set_option(Ctx *c, const char *name, const char *value) {
     else if (n == "ms_ablate" && isint && iv >= 0 && iv <= 9) c->opt.ms_ablate = (int)iv;
 #endif
     else if (n == "ms_items" && (autov || (isint && (iv == 64 || iv == 128 || iv == 192 || iv == 256)))) c->opt.ms_items = autov ? 0 : (int)iv;
+    // half-steps of the Jacobian: a finite positive double (jac_dlnw below 1: WKL (1 - eps) stays positive)
+    else if ((n == "jac_dt" || n == "jac_dlnw") && (autov || (isdbl && std::isfinite(dv) && dv > 0. && (n == "jac_dt" || dv < 1.)))) {
+        if (n == "jac_dt") c->opt.jac_dt = autov ? MONORTM_JAC_DT : dv;
+        else c->opt.jac_dlnw = autov ? MONORTM_JAC_DLNW : dv;
+    }
     else { c->err = "unknown option or value: " + n + " = " + v; return MONORTM_EARG; }
     return MONORTM_OK;
 }
@@ -455,6 +469,128 @@ static int rtm_host(Ctx *c, int nprof, int nwn, const double *wn, const int *nla
     return complete();
 }
 
+// ---- the Jacobian entries on host buffers: one upload, the *_dev call, one download (staging slots 8-11, so that the resident O of
+// the last MODM call - Ctx::lastO, in slot 3 - stays valid across a Jacobian call)
+int jac_check_args(Ctx *c, int nprof, int nwn, const int *nlay, int nlay_max, int quantity) {
+    if (nprof < 1 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    for (int p = 0; p < nprof; p++)
+        if (nlay[p] < 1 || nlay[p] > nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
+    return MONORTM_OK;
+}
+int jac_check_mol(Ctx *c, int nmol, int njac, const int *jac_mol, const void *K_W) {
+    if (njac < 0 || njac > nmol || (njac > 0 && (!jac_mol || !K_W))) { c->err = "njac outside 0..nmol, or jac_mol / K_W missing"; return MONORTM_EARG; }
+    for (int i = 0; i < njac; i++) {
+        if (jac_mol[i] < 1 || jac_mol[i] > nmol) { c->err = "jac_mol[" + std::to_string(i) + "] outside 1..nmol"; return MONORTM_EARG; }
+        for (int j = 0; j < i; j++)
+            if (jac_mol[j] == jac_mol[i]) { c->err = "jac_mol lists molecule " + std::to_string(jac_mol[i]) + " twice"; return MONORTM_EARG; }
+    }
+    return MONORTM_OK;
+}
+
+static int rtm_jac_host(Ctx *c, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
+                        const void *T, const void *TZ, const void *O, const void *tmpsfc, const void *emiss, const void *reflc,
+                        void *RAD, void *TB, void *K_O, void *K_T, void *K_TZ, void *K_SFC, std::function<int()> *defer) {
+    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn;
+    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_tz = (size_t)nprof * (nlay_max + 1) * d,
+                 b_o = npl * nwn * d, b_p = nprof * d, b_pw = pw * d, b_tzw = b_tz * nwn;
+    Arena in, out;
+    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_T = in.add(b_l), i_TZ = in.add(b_tz), i_O = in.add(b_o),
+                 i_ts = in.add(b_p), i_em = in.add(b_pw), i_rf = in.add(b_pw);
+    const size_t o_rad = out.add(b_pw), o_tb = out.add(b_pw), o_ko = out.add(b_o), o_kt = out.add(b_o), o_ktz = out.add(b_tzw),
+                 o_ks = out.add(3 * b_pw);
+    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
+    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
+    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
+    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
+    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
+    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
+    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_T, T, b_l);
+    memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_O, O, b_o); memcpy(h + i_ts, tmpsfc, b_p); memcpy(h + i_em, emiss, b_pw);
+    memcpy(h + i_rf, reflc, b_pw);
+    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
+    int rc = monortm_hip_rtm_jac_dev(c, nprof, nwn, (double *)(dv + i_wn), (int *)(dv + i_nl), nlay_max, (int *)(dv + i_irt), quantity,
+                                     dv + i_T, dv + i_TZ, dv + i_O, dv + i_ts, dv + i_em, dv + i_rf, dz + o_rad, dz + o_tb, dz + o_ko,
+                                     dz + o_kt, dz + o_ktz, dz + o_ks, c->hs);
+    if (rc) return rc;
+    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs));
+    auto complete = [=]() mutable -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->hs));
+        const char *ho = static_cast<const char *>(hout);
+        memcpy(RAD, ho + o_rad, b_pw); memcpy(TB, ho + o_tb, b_pw); memcpy(K_O, ho + o_ko, b_o); memcpy(K_T, ho + o_kt, b_o);
+        memcpy(K_TZ, ho + o_ktz, b_tzw); memcpy(K_SFC, ho + o_ks, 3 * b_pw);
+        return MONORTM_OK;
+    };
+    if (defer) { *defer = complete; return MONORTM_OK; }
+    return complete();
+}
+
+static int jac_host(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
+                    const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl,
+                    double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc, const void *emiss,
+                    const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD, void *TB, void *K_T, void *K_TZ,
+                    void *K_W, void *K_CLW, void *K_O, void *K_SFC, std::function<int()> *defer) {
+    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
+    for (int i = 1; i < nwn; i++)
+        if (!(wn[i] >= wn[i - 1])) { c->err = "wavenumbers must be ascending (the reference takes v1 = wn(1), v2 = wn(nwn), modm.f90:180-181)"; return MONORTM_EARG; }
+    {   // the perturbed states' temperatures must stay inside the TIPS range (the MODM kernels would flag them as well)
+        const double h = c->opt.jac_dt, *Tp = static_cast<const double *>(T);
+        for (int p = 0; p < nprof; p++)
+            for (int k = 0; k < nlay[p]; k++) {
+                const double t = Tp[(size_t)p * nlay_max + k];
+                if (!(t - h >= 70. && t + h <= 3000.)) {
+                    c->err = "layer temperature +- jac_dt outside 70-3000 K (TIPS, tips_2003.f90:277): profile " + std::to_string(p) + " layer " + std::to_string(k);
+                    return MONORTM_ETEMP;
+                }
+            }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn;
+    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_w = npl * nmol * d,
+                 b_tz = (size_t)nprof * (nlay_max + 1) * d, b_o = npl * nwn * d, b_p = nprof * d, b_pw = pw * d, b_tzw = b_tz * nwn,
+                 b_kw = b_o * njac;
+    Arena in, out;
+    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_P = in.add(b_l), i_T = in.add(b_l), i_C = in.add(b_l),
+                 i_W = in.add(b_w), i_B = in.add(b_l), i_TZ = in.add(b_tz), i_ts = in.add(b_p), i_em = in.add(b_pw), i_rf = in.add(b_pw);
+    const size_t o_O = out.add(b_o), o_rad = out.add(b_pw), o_tb = out.add(b_pw), o_kt = out.add(b_o), o_ktz = out.add(b_tzw),
+                 o_kw = out.add(b_kw), o_kc = out.add(b_o), o_ko = K_O ? out.add(b_o) : 0, o_ks = out.add(3 * b_pw);
+    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
+    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
+    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
+    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
+    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
+    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
+    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_P, P, b_l); memcpy(h + i_T, T, b_l);
+    memcpy(h + i_C, CLW, b_l); memcpy(h + i_W, WKL, b_w); memcpy(h + i_B, WBRODL, b_l); memcpy(h + i_TZ, TZ, b_tz);
+    memcpy(h + i_ts, tmpsfc, b_p); memcpy(h + i_em, emiss, b_pw); memcpy(h + i_rf, reflc, b_pw);
+    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
+    const double ends[2] = {wn[0], wn[nwn - 1]};
+    int rc = monortm_hip_jacobian_dev(c, nprof, nwn, (double *)(dv + i_wn), dvset, (int *)(dv + i_nl), nlay_max, nmol, dv + i_P, dv + i_T,
+                                      dv + i_C, dv + i_W, dv + i_B, cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)(dv + i_irt), dv + i_TZ,
+                                      dv + i_ts, dv + i_em, dv + i_rf, quantity, njac, jac_mol, dz + o_O, dz + o_rad, dz + o_tb, dz + o_kt,
+                                      dz + o_ktz, njac ? dz + o_kw : nullptr, dz + o_kc, K_O ? dz + o_ko : nullptr, dz + o_ks, ends, c->hs);
+    if (rc) return rc;
+    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs, c->errflag, c->errflag_host));
+    auto complete = [=]() mutable -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->hs));
+        if (int rcf = decode_flag(c, *c->errflag_host, c->hs)) return rcf;
+        const char *ho = static_cast<const char *>(hout);
+        memcpy(O, ho + o_O, b_o); memcpy(RAD, ho + o_rad, b_pw); memcpy(TB, ho + o_tb, b_pw); memcpy(K_T, ho + o_kt, b_o);
+        memcpy(K_TZ, ho + o_ktz, b_tzw); memcpy(K_CLW, ho + o_kc, b_o); memcpy(K_SFC, ho + o_ks, 3 * b_pw);
+        if (njac) memcpy(K_W, ho + o_kw, b_kw);
+        if (K_O) memcpy(K_O, ho + o_ko, b_o);
+        return MONORTM_OK;
+    };
+    if (defer) { *defer = complete; return MONORTM_OK; }
+    return complete();
+}
+
 // ---- sharding of a host-buffer call over the devices of a multi-device context (monortm_hip_init_multi) ------------
 // Profiles are independent (src/monortm.f90:357 is a loop without cross-iteration data flow): device g takes the
 // contiguous block [g ceil(P/G), (g+1) ceil(P/G)) of the batch, every device holds the whole line table, each block
@@ -626,7 +762,8 @@ void monortm_hip_finalize(void *ctx) {
     for (hipEvent_t e : c->far_ev)
         if (e) hipEventDestroy(e);
     c->mw_cache.release();
-    for (int i = 0; i < 8; i++)
+    if (c->jac_ws) hipFree(c->jac_ws);
+    for (int i = 0; i < 12; i++)
         if (c->stage[i].p) {
             if (i % 2 == 0) hipHostFree(c->stage[i].p);  // even slots: pinned host arenas
             else hipFree(c->stage[i].p);
@@ -1455,6 +1592,197 @@ int monortm_hip_rtm(void *ctx, int nprof, int nwn, const double *wn, const int *
         const int r = rtm_host(s, n, nwn, wn, nlay + p0, nlay_max, irt + p0, iout, off(T, p0 * l), off(TZ, p0 * (l + d)), off(O, p0 * w),
                                off(tmpsfc, p0 * d), off(emiss, p0 * v), off(reflc, p0 * v), off(RUP, p0 * v), off(RDN, p0 * v),
                                off(TRTOT, p0 * v), off(RAD, p0 * v), off(TB, p0 * v), TMR ? off(TMR, p0 * v) : nullptr, &fin[g]);
+        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
+    }
+    for (int g = 0; g < G; g++)
+        if (fin[g]) {
+            const int r = fin[g]();
+            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
+        }
+    return rc;
+}
+
+// ---- Jacobians ----------------------------------------------------------------------------------
+int monortm_hip_rtm_jac_dev(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
+                            const void *T, const void *TZ, const void *O, const void *tmpsfc, const void *emiss, const void *reflc,
+                            void *RAD, void *TB, void *K_O, void *K_T, void *K_TZ, void *K_SFC, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !tmpsfc || !emiss || !reflc || !RAD || !TB || !K_O || !K_T || !K_TZ || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (int rcd = check_device(c)) return rcd;
+    RtmJacArgs a{};
+    a.nprof = nprof; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = c->real_kind;
+    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
+    launch_rtm_jac(a, false, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+// MODM of the base and the 2 (1 + njac) perturbed states, then the adjoint chained with their differences.  Small batches (single-
+// profile retrievals underfill the GPU) go through ONE extended MODM launch of all states; larger ones through one launch of nprof
+// profiles per state, of the shapes of a plain MODM call - so that alternating Jacobian and plain calls never resizes the MODM
+// workspaces (an extended launch is only taken while its line-physics records stay below the 64 MB under which MODM keeps them).
+int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                             const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                             double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                             const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD,
+                             void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC, const double *wn_ends,
+                             void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (c->real_kind != 8) { c->err = "monortm_hip_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !O || !RAD ||
+        !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (int rcd = check_device(c)) return rcd;
+    double vends[2];
+    if (wn_ends) { vends[0] = wn_ends[0]; vends[1] = wn_ends[1]; }
+    else {   // once here, not in every MODM call below
+        HIPCHK(c, hipMemcpyAsync(&vends[0], wn, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&vends[1], wn + nwn - 1, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    const int nstate = 3 + 2 * njac;
+    const size_t npl = (size_t)nprof * nlay_max, st = npl * nwn;
+    const bool ext = (long long)nstate * nprof <= 64 && (size_t)nstate * npl * c->host.size() * 48 <= (64u << 20);
+    const size_t nj = ext ? nstate : 1;   // states whose unused MODM outputs are held at once
+    Arena ws;
+    const size_t w_P = ws.add(nstate * npl * 8), w_T = ws.add(nstate * npl * 8), w_C = ws.add(nstate * npl * 8), w_B = ws.add(nstate * npl * 8),
+                 w_W = ws.add(nstate * npl * nmol * 8), w_nl = ws.add(nstate * (size_t)nprof * sizeof(int)), w_O = ws.add(nstate * st * 8),
+                 w_OM = ws.add(nj * st * nmol * 8), w_OC = ws.add(nj * st * MONORTM_NCONT * 8), w_OL = ws.add(nj * st * 8);
+    if (ws.size > c->jac_ws_bytes) {
+        if (c->jac_ws) HIPCHK(c, hipFree(c->jac_ws));
+        c->jac_ws = nullptr;
+        c->jac_ws_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->jac_ws, ws.size));
+        c->jac_ws_bytes = ws.size;
+    }
+    char *wb = static_cast<char *>(c->jac_ws);
+    double *xO = reinterpret_cast<double *>(wb + w_O);
+    JacPerturbArgs pa{};
+    pa.nstate = nstate; pa.nprof = nprof; pa.nlay_max = nlay_max; pa.nmol = nmol; pa.dt = c->opt.jac_dt; pa.dlnw = c->opt.jac_dlnw;
+    for (int i = 0; i < njac; i++) pa.jac_mol[i] = jac_mol[i];
+    pa.P = static_cast<const double *>(P); pa.T = static_cast<const double *>(T); pa.CLW = static_cast<const double *>(CLW);
+    pa.WKL = static_cast<const double *>(WKL); pa.WBRODL = static_cast<const double *>(WBRODL); pa.nlay = nlay;
+    pa.xP = reinterpret_cast<double *>(wb + w_P); pa.xT = reinterpret_cast<double *>(wb + w_T); pa.xCLW = reinterpret_cast<double *>(wb + w_C);
+    pa.xWBRODL = reinterpret_cast<double *>(wb + w_B); pa.xWKL = reinterpret_cast<double *>(wb + w_W); pa.xnlay = reinterpret_cast<int *>(wb + w_nl);
+    launch_jac_perturb(pa, s);
+    HIPCHK(c, hipGetLastError());
+    auto modm = [&](int n, int s0, void *Oout, int slot) {   // MODM of n profiles of the state arrays from state s0 on
+        const size_t l0 = (size_t)s0 * npl;
+        return monortm_hip_modm_xs_dev(c, n, nwn, wn, dvset, pa.xnlay + (size_t)s0 * nprof, nlay_max, nmol, pa.xP + l0, pa.xT + l0, pa.xCLW + l0,
+                                       pa.xWKL + l0 * nmol, pa.xWBRODL + l0, cntnm_fac, sclcpl, sclhw, y0res, ibrd, 0, nullptr, nullptr, Oout,
+                                       wb + w_OM + slot * st * nmol * 8, wb + w_OC + slot * st * MONORTM_NCONT * 8, wb + w_OL + slot * st * 8,
+                                       vends, s);
+    };
+    if (ext) {
+        if (int rc = modm(nstate * nprof, 0, xO, 0)) return rc;
+        HIPCHK(c, hipMemcpyAsync(O, xO, st * 8, hipMemcpyDeviceToDevice, s));
+    } else {
+        // the base state straight from the caller's arrays, into the caller's O: what monortm_hip_modm_dev returns for them
+        if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw,
+                                             y0res, ibrd, 0, nullptr, nullptr, O, wb + w_OM, wb + w_OC, wb + w_OL, vends, s))
+            return rc;
+        for (int k = 1; k < nstate; k++)
+            if (int rc = modm(nprof, k, xO + k * st, 0)) return rc;
+    }
+    RtmJacArgs a{};
+    a.nprof = nprof; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = 8; a.njac = njac;
+    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC; a.K_W = K_W; a.K_CLW = K_CLW;
+    a.Opert = xO + st;
+    a.state_stride = st;
+    a.dt = c->opt.jac_dt;
+    a.dlnw = c->opt.jac_dlnw;
+    launch_rtm_jac(a, true, s);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+int monortm_hip_rtm_jac(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
+                        const void *T, const void *TZ, const void *O, const void *tmpsfc, const void *emiss, const void *reflc, void *RAD,
+                        void *TB, void *K_O, void *K_T, void *K_TZ, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !tmpsfc || !emiss || !reflc || !RAD || !TB || !K_O || !K_T || !K_TZ || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    DeviceGuard guard;
+    if (c->shards.empty())
+        return rtm_jac_host(c, nprof, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, tmpsfc, emiss, reflc, RAD, TB, K_O, K_T, K_TZ, K_SFC, nullptr);
+    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
+    const int G = (int)c->shards.size();
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d,
+                 wz = (size_t)(nlay_max + 1) * nwn * d;
+    std::vector<std::function<int()>> fin(G);
+    int rc = MONORTM_OK;
+    for (int g = 0; g < G; g++) {
+        int p0, n;
+        shard_block(nprof, G, g, &p0, &n);
+        if (n < 1) continue;
+        Ctx *s = c->shards[g];
+        const int r = rtm_jac_host(s, n, nwn, wn, nlay + p0, nlay_max, irt + p0, quantity, off(T, p0 * l), off(TZ, p0 * (l + d)), off(O, p0 * w),
+                                   off(tmpsfc, p0 * d), off(emiss, p0 * v), off(reflc, p0 * v), off(RAD, p0 * v), off(TB, p0 * v), off(K_O, p0 * w),
+                                   off(K_T, p0 * w), off(K_TZ, p0 * wz), off(K_SFC, p0 * 3 * v), &fin[g]);
+        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
+    }
+    for (int g = 0; g < G; g++)
+        if (fin[g]) {
+            const int r = fin[g]();
+            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
+        }
+    return rc;
+}
+
+int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                         const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                         double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                         const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD, void *TB,
+                         void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (c->real_kind != 8) { c->err = "monortm_hip_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
+    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !O || !RAD ||
+        !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    DeviceGuard guard;
+    if (c->shards.empty())
+        return jac_host(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt, TZ,
+                        tmpsfc, emiss, reflc, quantity, njac, jac_mol, O, RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O, K_SFC, nullptr);
+    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    const int G = (int)c->shards.size();
+    const size_t d = 8, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d, wz = (size_t)(nlay_max + 1) * nwn * d;
+    std::vector<std::function<int()>> fin(G);
+    int rc = MONORTM_OK;
+    for (int g = 0; g < G; g++) {
+        int p0, n;
+        shard_block(nprof, G, g, &p0, &n);
+        if (n < 1) continue;
+        Ctx *s = c->shards[g];
+        const int r = jac_host(s, n, nwn, wn, dvset, nlay + p0, nlay_max, nmol, off(P, p0 * l), off(T, p0 * l), off(CLW, p0 * l),
+                               off(WKL, p0 * l * nmol), off(WBRODL, p0 * l), cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt + p0, off(TZ, p0 * (l + d)),
+                               off(tmpsfc, p0 * d), off(emiss, p0 * v), off(reflc, p0 * v), quantity, njac, jac_mol, off(O, p0 * w), off(RAD, p0 * v),
+                               off(TB, p0 * v), off(K_T, p0 * w), off(K_TZ, p0 * wz), njac ? off(K_W, p0 * w * njac) : nullptr, off(K_CLW, p0 * w),
+                               K_O ? off(K_O, p0 * w) : nullptr, off(K_SFC, p0 * 3 * v), &fin[g]);
         if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
     }
     for (int g = 0; g < G; g++)

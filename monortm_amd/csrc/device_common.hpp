@@ -196,6 +196,31 @@ struct RtmArgs {
     void *tmpsfc, *RUP, *RDN, *TRTOT, *RAD, *TB, *TMR;
 };
 
+// Jacobians (jacobian_kernel.hip).  The adjoint of RTM: O, T, TZ, surface in; RAD, TB and the derivatives
+// of q = RAD (quantity 0) or TB (quantity 1) out - K_O, K_T [nprof][nlay_max][nwn], K_TZ [nprof][nlay_max + 1][nwn], K_SFC [nprof][3][nwn]
+// (K_O may be null when FULL).  FULL: K_W [nprof][nlay_max][njac][nwn] and K_CLW from the perturbed states' optical depths Opert:
+// state s at Opert + (s - 1) state_stride, s = 1 / 2: T +- dt, 3 + 2i / 4 + 2i: WKL(jac_mol[i]) x (1 +- dlnw).
+struct RtmJacArgs {
+    int nprof, nwn, nlay_max, quantity, real_kind, njac;
+    const double *wn;
+    const void *T, *TZ, *O, *tmpsfc, *emiss, *reflc;
+    const int *nlay, *irt;
+    void *RAD, *TB, *K_O, *K_T, *K_TZ, *K_SFC, *K_W, *K_CLW;
+    const void *Opert;
+    size_t state_stride;   // elements of one state's O: nprof x nlay_max x nwn
+    double dt, dlnw;
+};
+// the MODM inputs of the base (state 0) and the perturbed states, [nstate][nprof][nlay_max](x nmol), real_kind 8
+struct JacPerturbArgs {
+    int nstate, nprof, nlay_max, nmol;
+    double dt, dlnw;
+    int jac_mol[MXMOL];   // 1-based
+    const double *P, *T, *CLW, *WKL, *WBRODL;
+    const int *nlay;
+    double *xP, *xT, *xCLW, *xWKL, *xWBRODL;
+    int *xnlay;
+};
+
 // exp() and 1/x for the small kernels behind the line sum (radiance recurrences, microwave continuum): Cody-Waite reduction +
 // degree-13 polynomial (the routine of the line kernel's prepare stage: 20 instructions, 1-2 ulp like the library call at ~35)
 // and v_rcp_f64 + two Newton steps (1 ulp; an IEEE division is ~11 instructions).  exp_cw: |n| < 2^31 for every argument that
@@ -310,5 +335,8 @@ void launch_kat(int which, int n, const double *in, const double *tab, double *o
 void launch_xsec(const ModmArgs &a, const DevXsec &x, hipStream_t s);
 // rtm_kernel.hip
 void launch_rtm(const RtmArgs &a, hipStream_t s);
+// jacobian_kernel.hip (full = FULL instantiation, real_kind 8)
+void launch_jac_perturb(const JacPerturbArgs &a, hipStream_t s);
+void launch_rtm_jac(const RtmJacArgs &a, bool full, hipStream_t s);
 
 }  // namespace monortm_dev
