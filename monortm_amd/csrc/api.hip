@@ -1211,12 +1211,16 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
         int G = std::min(std::min(12, 64 / LPS), nprof);
         // slots of the molecules of this call: slot_base[nmol] pairs
         ms.nslot = c->ms_slot_host[nmol];
-        // lines per chunk: three passes of 64 (state, line) items, two, or one - the largest that leaves <= 10 KB of LDS a wave
-        // (16 waves per compute unit)
+        // lines per chunk: a prepare pass holds spp = 64 / CL whole states (a lane then keeps its line through the passes of a chunk),
+        // so CL is one of the values that leave few lanes idle, the largest whose ceil(G / spp) passes stay within the budget - three
+        // passes of 64 (state, line) items, two, or one - and that leaves <= 10 KB of LDS a wave (16 waves per compute unit)
+        static const int cl_set[] = {64, 32, 21, 16, 12, 10, 9, 8};
         for (int items = c->opt.ms_items ? c->opt.ms_items : 192; items >= 64 && !use_ms && G >= 1 && ms.nslot > 0; items -= 64) {
-            const int CL = std::min(64, items / G);
-            if (CL < 8) break;
-            ms.G = G; ms.LPS = LPS; ms.CL = CL; ms.nsteps = (G * CL + 63) / 64;
+            int CL = 0;
+            for (int cand : cl_set)
+                if (CL == 0 && (G + 64 / cand - 1) / (64 / cand) <= items / 64) CL = cand;
+            if (CL == 0) break;
+            ms.G = G; ms.LPS = LPS; ms.CL = CL; ms.spp = 64 / CL; ms.nsteps = (G + ms.spp - 1) / ms.spp;
             // records per state in LDS: the chunk + 2 read ahead, padded so that the states' arrays start 24 banks apart (a lane reads
             // 16 bytes of ITS state's record: eight states then touch eight disjoint groups of four banks)
             ms.sa_stride = CL + 2;
@@ -1226,7 +1230,7 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
             ms.inv_lps = (65536 + LPS - 1) / LPS;
             bool exact = ms.nsteps <= MS_MAXSTEPS;
             for (int ln = 0; ln < 64 && exact; ln++) exact = (int)(((unsigned)ln * (unsigned)ms.inv_lps) >> 16) == ln / LPS;
-            for (int item = 0; item < ms.nsteps * 64 && exact; item++) exact = (int)(((unsigned)item * (unsigned)ms.inv_cl) >> 16) == item / CL;
+            for (int ln = 0; ln < 64 && exact; ln++) exact = (int)(((unsigned)ln * (unsigned)ms.inv_cl) >> 16) == ln / CL;
             if (exact && lines_ms_lds(ms, nmol) <= 10240 - 160) use_ms = true;
         }
         const long long groups = (long long)ms.npg * nlay_max;

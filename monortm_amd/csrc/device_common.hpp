@@ -271,11 +271,12 @@ __host__ __device__ inline R *wp(void *p) { return static_cast<R *>(p); }
 #define MS_WPS 5
 #define MS_MAXSTEPS 4
 struct MsArgs {
-    int G, LPS, CL, nsteps;   // states per wave, lanes per state, lines per chunk, prepare passes of 64 items (ceil(G CL / 64))
+    int G, LPS, CL, nsteps;   // states per wave, lanes per state, lines per chunk, prepare passes (ceil(G / spp))
+    int spp;                  // states per prepare pass (64 / CL): lane = sub CL + l serves line l of state t spp + sub in pass t
     int sa_stride;            // HotA records per state in LDS (CL + 2: the class loops read two records ahead)
     int npg;                  // groups of G profiles (ceil(nprof / G)); grid = npg x nlay_max
     int nslot;                // (molecule, isotopologue) pairs of the line table: slot_base[m] + iso - 1
-    int inv_cl;               // ceil(65536 / CL): item / CL = (item * inv_cl) >> 16 for item < 256
+    int inv_cl;               // ceil(65536 / CL): lane / CL = (lane * inv_cl) >> 16 for lane < 64
     int inv_lps;              // ceil(65536 / LPS): lane / LPS likewise
     const int *slot_base;     // [nmol + 1] on the device
     void *scratch;            // per workgroup G x CL x (HotB + ColdLine): the records of the rare shapes of a chunk

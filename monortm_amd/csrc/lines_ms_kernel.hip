@@ -10,6 +10,7 @@
 //     (G = 6, 10 lanes x 5 channels a state), four one-resonance lines share one reciprocal, and a block (group of lines x slot of
 //     ten consecutive channels of every state) that no line of the group can reach is jumped over (lines_ms_asm.hpp);
 //   * prepare: one lane per (state, line) as before - the same functions (line_physics_core, line_records of lines_device.hpp);
+//     a pass holds whole states (64 / CL of them), so a lane keeps ITS line through the passes of a chunk and reads the table once;
 //   * prologue: one pass over (state, molecule) and (state, isotopologue) items for all G states.
 // The G states share ONE candidate window per molecule (the union of theirs: a line outside a state's own window lies beyond
 // 25 cm-1 of every channel and adds nothing - the clamp / the EXEC mask of its class says so), so a line index means the same
@@ -47,7 +48,8 @@ struct MsState {
     const HotA *sA;
     const HotB *gB;
     const ColdLine *gC;
-    int item0;   // first item (state * CL) of the state: bit item0 + j of `spec` says whether gB / gC of line j were written
+    int item0;   // where the prepare stage served the state: 64 x its pass + its first lane there (sub CL) - bit item0 + j of `spec`
+                 // says whether gB / gC of line j were written
 };
 struct MsSpec { unsigned long long w[MS_MAXSTEPS]; };
 __device__ __forceinline__ bool ms_own(const MsSpec &sp, int item) {
@@ -238,12 +240,13 @@ struct MsLds {
     double *sScor, *sDop;  // [G][nslot] Q(296)/Q(T), HWHM_D / Xnu per (molecule, isotopologue) of the table
     int *sLo, *sOff;       // [nmol] first candidate line of the wave (union over its states), [nmol + 1] prefix sums of the counts
     int *sSlot;            // [nmol + 1] slot of (molecule, isotopologue 1)
-    unsigned long long *sMask;   // [4 + MS_MAXSTEPS + 2 WPS + 1] class masks of the chunk (NT, M2, V, Y), the items whose rare-shape records exist,
+    unsigned long long *sMask;   // [4 + MS_MAXSTEPS + 2 WPS + 1] class masks of the chunk (NT, M2, V, Y), per prepare pass the lanes whose rare-shape records exist,
                                  // per slot k the lines that reach one of its channels (lines_ms_asm.hpp, MS_IFK), and a word that
                                  // is non-zero when a state of the wave is denser than ms_reach_kernel's margin allows; behind it per slot
                                  // the lines whose NEGATIVE resonance reaches the slot (MS_IFQ)
-    unsigned char *sFlag;  // [nsteps * 64] class flags per item: bits 0-3 NT, M2, V, Y
-    int *sRole;            // [64] the lane in the evaluate stage: se | ce << 8 | kvalid << 16 | profile exists << 24 | state active << 25
+    unsigned char *sFlag;  // [nsteps * 64] class flags per item (state * CL + line): bits 0-3 NT, M2, V, Y
+    int *sRole;            // [64] the lane in the evaluate stage: se | ce << 8 | kvalid << 16 | profile exists << 24 | state active << 25 |
+                           // prepare pass of the state << 26 | its place in that pass (sub) << 28
     double *sS;            // [WPS][64] the sums of the molecule run in progress (a lane's own slots; global memory): in registers only inside a run's walk
 };
 __device__ __forceinline__ MsLds ms_lds(double *dyn, int G, int sa_stride, int nmol, int nslot, double *gS = nullptr) {
@@ -285,7 +288,7 @@ __device__ __forceinline__ kseg_t ms_kseg() {
 }
 
 // the lane in the evaluate stage: state se (of G), channels ce + LPS k of it; lanes beyond G x LPS idle along with state 0
-struct MsLane { int lane, se, ce, prof; unsigned kvalid; bool act; };
+struct MsLane { int lane, se, ce, prof, item0; unsigned kvalid; bool act; };
 __device__ __forceinline__ MsLane ms_lane(const MsArgs &mc, int pg, const int *sRole) {
     MsLane l;
     l.lane = (int)__lane_id();
@@ -296,6 +299,7 @@ __device__ __forceinline__ MsLane ms_lane(const MsArgs &mc, int pg, const int *s
     l.kvalid = (r >> 16) & 255u;
     l.prof = ((r >> 24) & 1u) ? pg * mc.G + l.se : 0;
     l.act = (r >> 25) & 1u;
+    l.item0 = (int)(((r >> 26) & 3u) * 64u + ((r >> 28) & 7u) * (unsigned)mc.CL);   // (MsState::item0)
     return l;
 }
 
@@ -342,7 +346,8 @@ __device__ __attribute__((noinline)) int ms_prologue(const unsigned long long *s
             }
     }
     if (__builtin_amdgcn_ballot_w64(act_e) == 0ull) return -1;   // no state of the wave has this layer
-    l.sRole[lane] = (int)((unsigned)se | ((unsigned)ce << 8) | (kvalid << 16) | ((unsigned)prof_ok << 24) | ((unsigned)act_e << 25));
+    const unsigned pass_e = (unsigned)(se / ms.spp), sub_e = (unsigned)se - pass_e * (unsigned)ms.spp;   // (ms_prepare serves state se in pass pass_e, lanes sub_e CL ..)
+    l.sRole[lane] = (int)((unsigned)se | ((unsigned)ce << 8) | (kvalid << 16) | ((unsigned)prof_ok << 24) | ((unsigned)act_e << 25) | (pass_e << 26) | (sub_e << 28));
 
     l.sWn[lane] = a.wn[min(lane, nwn - 1)];
     if (lane <= nmol) l.sSlot[lane] = ms.slot_base[lane];   // (device array: a per-lane index into the kernel arguments would go through scratch)
@@ -468,9 +473,11 @@ __device__ __attribute__((noinline)) int ms_prologue(const unsigned long long *s
     return l.sOff[nmol];
 }
 
-// ---- prepare: the chunk's lines [base, base + CL) for every state, one lane per (state, line) item, ms.nsteps passes of 64.
-// Leaves the records in sA (+ HotB / ColdLine of the rare shapes in the workgroup's scratch), the class of every line for the wave
-// - the most general over its states - and the items whose rare-shape records exist in sMask.
+// ---- prepare: the chunk's lines [base, base + CL) for every state.  A lane is (sub, l): line l of the chunk for state t spp + sub in
+// pass t (spp = 64 / CL whole states a pass; lanes from spp CL on idle), so its line is the same in every pass: molecule, table
+// index, the table's fields, meta and the plain / non-plain choice are resolved once per chunk, and a pass does what depends on the
+// state.  Leaves the records in sA (+ HotB / ColdLine of the rare shapes in the workgroup's scratch), the class of every line for
+// the wave - the most general over its states - and per pass the lanes whose rare-shape records exist in sMask.
 template <bool IBRD>
 __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int base, int mchunk, int total, HotB *gB, ColdLine *gC) {
     extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
@@ -481,22 +488,47 @@ __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int 
     const int G = ms.G, CL = ms.CL, nmol = a.nmol, nslot = ms.nslot;
     const MsLds ld = ms_lds(dyn_lds, G, ms.sa_stride, nmol, nslot, nullptr);   // (sS itself is not used here)
     const int lane = threadIdx.x;
+    const int sub = (int)(((unsigned)lane * (unsigned)ms.inv_cl) >> 16), l = lane - sub * CL;   // lane = sub CL + l
+    const bool lane_in = sub < ms.spp;
+    const bool lin = lane_in && base + l < total;   // the lane's line exists
+    // ---- the line, once per chunk -----------------------------------------------------------------------------------------------
+    int m = mchunk, idx = 0, slot0 = 0;
+    LineFields lf{0., 0., 0.f, 0.f, 0.f, 0.f, 0.f, 0u};
+    float near0 = 0.f;
+    if (lin) {
+        const int v = base + l;
+        while (ld.sOff[m + 1] <= v) m++;
+        idx = ld.sLo[m] + (v - ld.sOff[m]);
+        slot0 = ld.sSlot[m];
+        // (species broadening: the seven-species blocks of a pass leave no registers for the fields across the passes - held, they
+        // were spilled inside the pass loop - so that instantiation keeps molecule, index, meta and slot and reads the fields per pass)
+        if constexpr (IBRD) lf.meta = L.meta[idx];
+        else lf = load_line_fields(L, idx);
+        near0 = ms.near0[idx];
+    }
+    const uint32_t meta = lf.meta;
+    // a chunk without a coupled line or an air-width / air-shift conversion (meta bits 10-11, 13, 14: most chunks of most
+    // tables) takes the instantiation without those blocks - fifteen divergent regions less to step through
+    const bool plain = ((meta >> 10) & 3u) == 0u && ((meta >> 13) & 3u) == 0u;
+    const bool all_plain = __builtin_amdgcn_ballot_w64(lin && !plain) == 0ull;
+    // ---- the states: pass t serves state t spp + sub ------------------------------------------------------------------------------
 #pragma unroll 1
     for (int t = 0; t < ms.nsteps; t++) {
-        const int item = t * 64 + lane;
-        const int s = (int)(((unsigned)item * (unsigned)ms.inv_cl) >> 16), l = item - s * CL;   // item = s CL + l
-        const int v = base + l;
-        const bool in = s < G && v < total && ld.sLay[s * 20 + 19] != 0.;
+        const int s = t * ms.spp + sub;
+        const bool s_in = lane_in && s < G;
+        const bool in = lin && s_in && ld.sLay[s * 20 + 19] != 0.;
+        const int item = s * CL + l;   // where the consumers look for (state, line)
         HotA hA{0., 1., 0., 0.};
         unsigned flag = 0u;
         bool special = false;
         if (in) {
-            int m = mchunk;
-            while (ld.sOff[m + 1] <= v) m++;
-            const int idx = ld.sLo[m] + (v - ld.sOff[m]);
-            const int mol = m + 1;
+            // (species broadening: what a pass forms from the line alone - addresses into the table's arrays, constants chosen by
+            // molecule and meta - is formed in the pass: ahead of the loop it found no registers and was spilled)
+            int idxp = idx, mp = m;
+            uint32_t metap = meta;
+            if constexpr (IBRD) asm volatile("" : "+v"(idxp), "+v"(mp), "+v"(metap));
+            const int molp = mp + 1, isop = (metap >> 6) & 15;
             const double *ly = ld.sLay + s * 20;
-            const uint32_t meta = L.meta[idx];
             LayerScalars lys;
             lys.ILC = (int)ly[17];
             lys.RHORAT = ly[0]; lys.RP = ly[1]; lys.RP2 = ly[2]; lys.lnRT = ly[3]; lys.cTk = ly[4]; lys.cT0 = ly[5];
@@ -504,29 +536,26 @@ __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int 
             double rho7[MXBRD];
 #pragma unroll
             for (int j = 0; j < MXBRD; j++) rho7[j] = IBRD ? ly[10 + j] : 0.;
-            const int iso = (meta >> 6) & 15;
-            const double rho_self = (mol <= MXBRD) ? ly[10 + mol - 1] : lys.RHORAT * ld.sW[s * nmol + mol - 1] / ly[9];
-            const int sl = s * nslot + ld.sSlot[m];
-            const double XIPSF = iso ? ld.sScor[sl + iso - 1] : 0.;
-            const double dopfac = iso ? ld.sDop[sl + iso - 1] : ld.sDop[sl];
-            LineFields lf = load_line_fields(L, idx);
-            lf.meta = meta;
+            const double rho_self = (molp <= MXBRD) ? ly[10 + molp - 1] : lys.RHORAT * ld.sW[s * nmol + molp - 1] / ly[9];
+            const int sl = s * nslot + slot0;
+            const double XIPSF = isop ? ld.sScor[sl + isop - 1] : 0.;
+            const double dopfac = isop ? ld.sDop[sl + isop - 1] : ld.sDop[sl];
+            LineFields lfp = lf;
+            if constexpr (IBRD) lfp = load_line_fields(L, idxp);   // (see above: this instantiation reads the fields per pass)
+            lfp.meta = metap;
             HotB hB;
             ColdLine cC;
             bool fAL, fM2, fV, fY;
-            // a pass without a coupled line or an air-width / air-shift conversion (meta bits 10-11, 13, 14: most passes of most
-            // tables) takes the instantiation without those blocks - fifteen divergent regions less to step through
-            const bool plain = ((meta >> 10) & 3u) == 0u && ((meta >> 13) & 3u) == 0u;
             // near_lb: no channel nearer to the shifted centre than this (<= 0: unknown) - the table centre's distance less the shift,
             // with a margin far above the roundings involved
-            if (__builtin_amdgcn_ballot_w64(!plain) == 0ull) {
-                const LinePhys ph = line_physics_core<IBRD, true>(phys_params(a, L), idx, mol, lf, lys, rho_self, rho7, XIPSF, dopfac);
-                const double near_lb = (double)ms.near0[idx] * (1. - 1e-6) - fabs(ph.xnu - lf.xnu0) - 1e-9;
-                line_records<double, true>(a, L, idx, m, meta, ph, ld.sW + s * nmol, ld.sWn, 64, hA, hB, cC, fAL, fM2, fV, fY, near_lb);
+            if (all_plain) {
+                const LinePhys ph = line_physics_core<IBRD, true>(phys_params(a, L), idxp, molp, lfp, lys, rho_self, rho7, XIPSF, dopfac);
+                const double near_lb = (double)near0 * (1. - 1e-6) - fabs(ph.xnu - lfp.xnu0) - 1e-9;
+                line_records<double, true>(a, L, idxp, mp, metap, ph, ld.sW + s * nmol, ld.sWn, 64, hA, hB, cC, fAL, fM2, fV, fY, near_lb);
             } else {
-                const LinePhys ph = line_physics_core<IBRD>(phys_params(a, L), idx, mol, lf, lys, rho_self, rho7, XIPSF, dopfac);
-                const double near_lb = (double)ms.near0[idx] * (1. - 1e-6) - fabs(ph.xnu - lf.xnu0) - 1e-9;
-                line_records<double>(a, L, idx, m, meta, ph, ld.sW + s * nmol, ld.sWn, 64, hA, hB, cC, fAL, fM2, fV, fY, near_lb);
+                const LinePhys ph = line_physics_core<IBRD>(phys_params(a, L), idxp, molp, lfp, lys, rho_self, rho7, XIPSF, dopfac);
+                const double near_lb = (double)near0 * (1. - 1e-6) - fabs(ph.xnu - lfp.xnu0) - 1e-9;
+                line_records<double>(a, L, idxp, mp, metap, ph, ld.sW + s * nmol, ld.sWn, 64, hA, hB, cC, fAL, fM2, fV, fY, near_lb);
             }
             flag = (fAL ? 0u : 1u) | (fM2 ? 2u : 0u) | (fV ? 4u : 0u) | (fY ? 8u : 0u);
             special = fV || fY;
@@ -535,8 +564,10 @@ __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int 
                 gC[item] = cC;
             }
         }
-        if (s < G) ld.sA[s * ms.sa_stride + l] = hA;
-        ld.sFlag[item] = (unsigned char)flag;
+        if (s_in) {
+            ld.sA[s * ms.sa_stride + l] = hA;
+            ld.sFlag[item] = (unsigned char)flag;
+        }
         const unsigned long long bs = __builtin_amdgcn_ballot_w64(special);
         if (lane == 0) ld.sMask[4 + t] = bs;
     }
@@ -554,11 +585,8 @@ __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int 
     // last word - uses no mask); rare shapes reach every slot
     {
         unsigned r = 0u;
-        const int v = base + lane;
-        if (lane < CL && v < total) {
-            int m = mchunk;
-            while (ld.sOff[m + 1] <= v) m++;
-            r = ms.reach[ld.sLo[m] + (v - ld.sOff[m])];
+        if (lane < CL && lin) {   // (lanes below CL are sub 0: their l is the lane, idx the line's)
+            r = ms.reach[idx];
             if ((f & (4u | 8u)) || ld.sMask[4 + MS_MAXSTEPS + WPS] != 0ull) r = 0x1f1fu;
         }
 #pragma unroll
@@ -634,7 +662,7 @@ __global__ __launch_bounds__(64, 4) void lines_ms_kernel(ModmArgs a, DevLines L,
         const DevTables &tk = *(const DevTables *)(ks + KA_TABLES);
         const MsArgs &mk = *(const MsArgs *)(ks + KA_MS);
         if (ak.wn != a.wn || ak.errflag != a.errflag || ak.nmol != a.nmol || Lk.vnu != L.vnu || Lk.meta != L.meta || Lk.mol_start[MXMOL + 1] != L.mol_start[MXMOL + 1] ||
-            tk.tips_qoft != tb.tips_qoft || tk.smass != tb.smass || mk.scratch != ms.scratch || mk.inv_cl != ms.inv_cl || mk.slot_base != ms.slot_base)
+            tk.tips_qoft != tb.tips_qoft || tk.smass != tb.smass || mk.scratch != ms.scratch || mk.inv_cl != ms.inv_cl || mk.spp != ms.spp || mk.slot_base != ms.slot_base)
             atomicOr(a.errflag, ERRBIT_ARG);
     }
     const int total = __builtin_amdgcn_readfirstlane(ms_prologue(&sKseg, lay, pg));
@@ -695,7 +723,7 @@ __global__ __launch_bounds__(64, 4) void lines_ms_kernel(ModmArgs a, DevLines L,
             const int mol = m + 1;
             {
                 const MsLane ln = ms_lane(mc, pg, ld.sRole);
-                const MsState st{ld.sA + ln.se * mc.sa_stride, gB + ln.se * CL, gC + ln.se * CL, ln.se * CL};
+                const MsState st{ld.sA + ln.se * mc.sa_stride, gB + ln.se * CL, gC + ln.se * CL, ln.item0};
 #ifdef MONORTM_EXPERIMENT
                 if ((mc.ablate == 3 && (mol == 7 || mol == 2)) || (mc.ablate == 5 && mol != 7 && mol != 2)) continue;
 #endif
