@@ -114,7 +114,8 @@ int monortm_hip_kat(void *ctx, int which, int n, const double *args, const doubl
 
 /* Diagnostics: which = 0 -> number of monortm_hip_rtm calls on this context that found the optical depths O of the
  * preceding monortm_hip_modm call still resident on the device (the caller handed back exactly what MODM returned, as
- * PROGRAM MONORTM does at src/monortm.f90:567-574) and skipped the upload.  -1 for an unknown selector / NULL. */
+ * PROGRAM MONORTM does at src/monortm.f90:567-574) and skipped the upload.  which = 1 -> the same count for monortm_hip_rtm_scan.
+ * -1 for an unknown selector / NULL. */
 long long monortm_hip_counter(void *ctx, int which);
 
 /* Physical line records (IFLG >= 0) held for molecule mol (1..39); mol = 0 -> all molecules.
@@ -200,6 +201,29 @@ int monortm_hip_rtm_dev(void *ctx, int nprof, int nwn, const double *wn, const i
                         const monortm_real *O, monortm_real *tmpsfc, const monortm_real *emiss,
                         const monortm_real *reflc, monortm_real *RUP, monortm_real *RDN, monortm_real *TRTOT,
                         monortm_real *RAD, monortm_real *TB, monortm_real *TMR, void *stream);
+
+/* CALCTMR + RTM along npath paths per profile from ONE set of optical depths.  No reference counterpart: the reference gets every
+ * path from a new LBLATM + MODM run.  path [nprof][npath][nlay_max] (monortm_real) = the factor by which every amount of the layer
+ * (WKL, WBRODL, CLW, XAMNT) along that path exceeds the amounts O was computed for; finite, >= 0; entries of layers >= nlay[p] are
+ * ignored.  Exact while the layers' P and T are those O was computed with (plane-parallel secants: exact; refracted / spherical
+ * geometry: the caller's layer means).  irt, T, TZ, tmpsfc (IN/OUT as in monortm_hip_rtm) are per profile;
+ * emiss, reflc: [nprof][nwn] (sfc_per_path = 0) or [nprof][npath][nwn] (1).  Outputs [nprof][npath][nwn]; TMR may be NULL.
+ * 1 <= npath <= 16384, nlay_max <= 603 (the bound of monortm_hip_modm).  Host buffers: a negative or non-finite factor of an active
+ * layer is MONORTM_EARG and nothing is launched; a multi-device context shards the profiles like monortm_hip_rtm; when O is what the
+ * preceding monortm_hip_modm call returned it is read where it lies on the device (counted by monortm_hip_counter(ctx, 1)). */
+int monortm_hip_rtm_scan(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max,
+                         const int *irt, int iout, const monortm_real *T, const monortm_real *TZ, const monortm_real *O,
+                         const monortm_real *path, monortm_real *tmpsfc, int sfc_per_path, const monortm_real *emiss,
+                         const monortm_real *reflc, monortm_real *RUP, monortm_real *RDN, monortm_real *TRTOT,
+                         monortm_real *RAD, monortm_real *TB, monortm_real *TMR);
+/* The same on device pointers (nlay, irt int arrays, the others monortm_real), asynchronous on `stream`; one-device context, which
+ * must be the current device.  Allocates nothing.  A bad factor of an active layer surfaces through monortm_hip_check
+ * (MONORTM_EARG); the kernel still finishes. */
+int monortm_hip_rtm_scan_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max,
+                             const int *irt, int iout, const monortm_real *T, const monortm_real *TZ, const monortm_real *O,
+                             const monortm_real *path, monortm_real *tmpsfc, int sfc_per_path, const monortm_real *emiss,
+                             const monortm_real *reflc, monortm_real *RUP, monortm_real *RDN, monortm_real *TRTOT,
+                             monortm_real *RAD, monortm_real *TB, monortm_real *TMR, void *stream);
 
 /* ---- Jacobians for retrievals (no reference counterpart: "CURRENTLY MONORTM DOES NOT HANDLE DERIVATIVES",
  * src/monortm_sub.F90:199).  DESIGN.md section 3.6 has the method and the error budget.

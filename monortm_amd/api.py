@@ -58,6 +58,10 @@ SYMBOLS = {
                                        _vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "monortm_hip_rtm_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "monortm_hip_rtm_scan": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int]
+                             + [_vp] * 8),
+    "monortm_hip_rtm_scan_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int]
+                                 + [_vp] * 9),
     "monortm_hip_rtm_jac": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 12),
     "monortm_hip_rtm_jac_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 13),
     "monortm_hip_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -85,6 +89,20 @@ def _quantity(q) -> int:
     if isinstance(q, str):
         return {"tb": 1, "rad": 0}[q.lower()]
     return int(q)
+
+
+SCAN_FIELDS = ("rup", "rdn", "trtot", "rad", "tb", "tmr")   # output order of monortm_hip_rtm_scan
+
+
+def plane_parallel_path(zenith_deg, nlay_max: int) -> np.ndarray:
+    """Path factors of a plane-parallel atmosphere for rtm_scan / scan: [npath, nlay_max] of 1 / cos(zenith), the same in every
+    layer.  Angles outside [0, 90) degrees (and NaN) are refused."""
+    z = np.atleast_1d(np.asarray(zenith_deg, np.float64))
+    if z.ndim != 1 or z.size < 1 or int(nlay_max) < 1:
+        raise ValueError("zenith_deg: a scalar or a 1-D sequence of angles; nlay_max >= 1")
+    if not np.all((z >= 0.) & (z < 90.)):
+        raise ValueError("zenith angles must lie in [0, 90) degrees")
+    return np.ascontiguousarray(np.repeat((1. / np.cos(np.deg2rad(z)))[:, None], int(nlay_max), axis=1))
 
 
 class MonoRTMError(RuntimeError):
@@ -248,6 +266,48 @@ class MonoRTM:
         self._chk(self.lib.monortm_hip_rtm(self.ctx, nprof, nwn, _ptr(wn), _ptr(nlay), lm, _ptr(irt), p0.iout, _ptr(T), _ptr(TZ),
                                            _ptr(O), _ptr(ts), _ptr(em), _ptr(rf), *[_ptr(o) for o in outs]))
         return (*outs, ts)
+
+    # ---- path scans (monortm_hip_rtm_scan; DESIGN.md section 3.7) ------------------------------------------------------------
+    def _path(self, path, nprof: int, lm: int) -> np.ndarray:
+        """[npath, nlay_max] (the same paths for every profile) or [nprof, npath, nlay_max] -> the latter, contiguous."""
+        f = np.asarray(path, self.dtype)
+        if f.ndim == 2:
+            f = np.broadcast_to(f[None], (nprof,) + f.shape)
+        if f.ndim != 3 or f.shape[0] != nprof or f.shape[1] < 1 or f.shape[2] != lm:
+            raise ValueError(f"path must be [npath, {lm}] or [{nprof}, npath, {lm}], got {f.shape}")
+        return np.ascontiguousarray(f)
+
+    def rtm_scan(self, profiles: list[Profile], O: np.ndarray, path, emiss=None, reflc=None) -> dict:
+        """CALCTMR + RTM along npath paths per profile from one O [nprof, nlay_max, nwn]: path [npath, nlay_max] or
+        [nprof, npath, nlay_max] holds the factor of every layer's amounts along the path (plane_parallel_path for secants).
+        emiss / reflc default to the profiles' own; given as [nprof, npath, nwn] they differ per path (sfc_per_path = 1).
+        Returns a dict of rup, rdn, trtot, rad, tb, tmr [nprof, npath, nwn] and tmpsfc [nprof]."""
+        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
+        dt = self.dtype
+        f = self._path(path, nprof, lm)
+        npath = f.shape[1]
+        em = em if emiss is None else _np(emiss, dt)
+        rf = rf if reflc is None else _np(reflc, dt)
+        if em.shape != rf.shape or em.shape not in ((nprof, nwn), (nprof, npath, nwn)):
+            raise ValueError(f"emiss / reflc must both be [{nprof}, {nwn}] or [{nprof}, {npath}, {nwn}]")
+        O = _np(O, dt)
+        if O.shape != (nprof, lm, nwn):
+            raise ValueError(f"O must be [{nprof}, {lm}, {nwn}], got {O.shape}")
+        out = {k: np.zeros((nprof, npath, nwn), dt) for k in SCAN_FIELDS}
+        wn = _np(profiles[0].wn)
+        self._chk(self.lib.monortm_hip_rtm_scan(self.ctx, nprof, npath, nwn, _ptr(wn), _ptr(nlay), lm, _ptr(irt), profiles[0].iout,
+                                                _ptr(T), _ptr(TZ), _ptr(O), _ptr(f), _ptr(ts), int(em.ndim == 3), _ptr(em), _ptr(rf),
+                                                *[_ptr(out[k]) for k in SCAN_FIELDS]))
+        out["tmpsfc"] = ts
+        return out
+
+    def scan(self, profiles: list[Profile], path, emiss=None, reflc=None) -> dict:
+        """MODM once, then the radiances along every path (rtm_scan)."""
+        return self.rtm_scan(profiles, self.modm(profiles)[0], path, emiss, reflc)
+
+    def counter(self, which: int = 0) -> int:
+        """monortm_hip_counter: 0 = rtm calls, 1 = rtm_scan calls that found O resident on the device."""
+        return int(self.lib.monortm_hip_counter(self.ctx, which))
 
     def run(self, profiles: list[Profile]) -> list[Dump]:
         """MODM + CALCTMR + RTM for a batch, as PROGRAM MONORTM chains them (src/monortm.f90:557-574)."""
@@ -422,6 +482,7 @@ class DeviceBatch:
         self.fac = _np(p0.cntnm)
         self.wn_ends = _np([p0.wn[0], p0.wn[-1]])  # host copy: keeps step() free of device->host traffic
         self.nlay_total = int(nlay.sum())
+        self._scan = {}  # npath -> (output block, device copy of the factors) of scan()
 
     def _bind_spectral(self):
         b = self._spec[self._cur]
@@ -473,6 +534,43 @@ class DeviceBatch:
                                              _ptr(jm) if nj else None, *[d(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS],
                                              _ptr(self.wn_ends), _vp(s.cuda_stream)))
         return out
+
+    # ---- path scans on the resident batch (monortm_hip_modm_dev + monortm_hip_rtm_scan_dev) ---------------------------------------
+    def scan(self, path, stream=None):
+        """MODM once and the radiances along npath paths per profile, on the current (or the given) stream, asynchronously.
+        path: [npath, nlay_max] or [nprof, npath, nlay_max] (numpy or a torch tensor).  Returns one [6, nprof, npath, nwn] block in
+        the order of spectral_block() (RAD, TB, TRTOT, TMR, RUP, RDN), allocated at the first call for that npath and overwritten
+        by every later one, as is the device copy of the factors (so that a graph capture of the call replays into the same
+        tensors).  A torch tensor on the batch's device is copied on the stream: only then is the call asynchronous and fit for
+        a graph capture.  A numpy array or a host tensor is uploaded from pageable memory, which blocks the host on every call
+        and cannot be captured.  Bad factors surface through check()."""
+        t = self.torch
+        real = t.float32 if self.rt.real_kind == 4 else t.float64  # dtype of the REAL arrays
+        f = t.as_tensor(path)
+        if f.dim() == 2:
+            f = f.unsqueeze(0).expand(self.nprof, -1, -1)
+        if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
+            raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
+        npath = int(f.shape[1])
+        if npath not in self._scan:
+            self._scan[npath] = (t.zeros(6, self.nprof, npath, self.nwn, dtype=real, device=self.dev),
+                                 t.zeros(self.nprof, npath, self.lm, dtype=real, device=self.dev))
+        blk, fd = self._scan[npath]
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        with t.cuda.stream(s):
+            fd.copy_(f, non_blocking=True)
+        sp = _vp(s.cuda_stream)
+        p0, lib, rt = self.p0, self.rt.lib, self.rt
+        d = lambda x: _vp(x.data_ptr())  # noqa: E731
+        rad, tb, trtot, tmr, rup, rdn = (blk[k] for k in range(6))
+        rt._chk(lib.monortm_hip_modm_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol,
+                                         d(self.P), d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl,
+                                         p0.sclhw, p0.y0res, p0.ibrd, 0, d(self.O), d(self.OBM), d(self.OC), d(self.OCLW), _ptr(self.wn_ends),
+                                         sp))
+        rt._chk(lib.monortm_hip_rtm_scan_dev(rt.ctx, self.nprof, npath, self.nwn, d(self.wn), d(self.nlay), self.lm, d(self.irt), p0.iout,
+                                             d(self.T), d(self.TZ), d(self.O), d(fd), d(self.tmpsfc), 0, d(self.emiss), d(self.reflc),
+                                             d(rup), d(rdn), d(trtot), d(rad), d(tb), d(tmr), sp))
+        return blk
 
     # ---- HIP graph: the three launches of a step recorded once, replayed with a single call ------------------
     def capture(self):

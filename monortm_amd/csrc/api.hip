@@ -99,10 +99,11 @@ struct Ctx {
         int nprof = 0, nwn = 0, nlay_max = 0;
     } lastO;
     long long o_reused = 0;  // calls of monortm_hip_rtm that found O resident
+    long long o_reused_scan = 0;  // calls of monortm_hip_rtm_scan that did
     // MONORTM_HOST_TIMING=1: wall time of the host-buffer calls by phase (pack, enqueue, wait, unpack), printed at finalize
     bool host_timing = false;
-    double ht[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    long long ht_calls[2] = {0, 0};
+    double ht[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};   // modm, rtm, rtm_scan
+    long long ht_calls[3] = {0, 0, 0};
     size_t partial_elems = 0;
     int profiling = 0;  // bit k set: record events around kernel k
     int prof_stride = 1;  // ... around every prof_stride-th launch of it (an event pair costs a few microseconds of the stream)
@@ -247,9 +248,10 @@ int check_modm_args(Ctx *c, int nprof, int nwn, int nlay_max, int nmol, int ibrd
 Ctx *g_timing_ctx = nullptr;
 void print_host_timing(Ctx *c) {
     if (!c->host_timing) return;
-    for (int k = 0; k < 2; k++)
+    static const char *const names[3] = {"modm", "rtm ", "scan"};
+    for (int k = 0; k < 3; k++)
         if (c->ht_calls[k])
-            fprintf(stderr, "monortm_hip %s: %lld calls, us per call: pack %.1f enqueue %.1f wait %.1f unpack %.1f\n", k ? "rtm " : "modm",
+            fprintf(stderr, "monortm_hip %s: %lld calls, us per call: pack %.1f enqueue %.1f wait %.1f unpack %.1f\n", names[k],
                     c->ht_calls[k], c->ht[k][0] / c->ht_calls[k] * 1e6, c->ht[k][1] / c->ht_calls[k] * 1e6,
                     c->ht[k][2] / c->ht_calls[k] * 1e6, c->ht[k][3] / c->ht_calls[k] * 1e6);
 }
@@ -328,7 +330,7 @@ namespace {
 int decode_flag(Ctx *c, int flag, hipStream_t s) {
     if (!flag) return MONORTM_OK;
     HIPCHK(c, hipMemsetAsync(c->errflag, 0, sizeof(int), s));
-    if (flag & ERRBIT_ARG) { c->err = "device arguments: nlay[p] outside 1..nlay_max, wavenumbers not ascending or not the grid dvset promises"; return MONORTM_EARG; }
+    if (flag & ERRBIT_ARG) { c->err = "device arguments: nlay[p] outside 1..nlay_max, wavenumbers not ascending or not the grid dvset promises, or a negative / non-finite path factor (monortm_hip_rtm_scan_dev)"; return MONORTM_EARG; }
     if (flag & ERRBIT_TEMP) { c->err = "TIPS: layer temperature outside 70-3000 K / partition sum <= 0 (reference STOP, tips_2003.f90:277)"; return MONORTM_ETEMP; }
     c->err = "SDVOIGT: REAL(v) < 0 (reference STOP, modm.f90:1062)";
     return MONORTM_ESDV;
@@ -461,6 +463,98 @@ static int rtm_host(Ctx *c, int nprof, int nwn, const double *wn, const int *nla
         memcpy(RUP, ho + o_up, b_pw); memcpy(RDN, ho + o_dn, b_pw); memcpy(TRTOT, ho + o_tr, b_pw); memcpy(RAD, ho + o_rad, b_pw);
         if (iout == 1) memcpy(TB, ho + o_tb, b_pw);
         if (TMR) memcpy(TMR, ho + o_tmr, b_pw);
+        memcpy(tmpsfc, ho + o_ts, b_p);
+        hc.mark(3);
+        return MONORTM_OK;
+    };
+    if (defer) { *defer = complete; return MONORTM_OK; }
+    return complete();
+}
+
+// ---- path scans: the staging slots of rtm_host (4-7; the resident O of the last MODM call is in slot 3)
+constexpr int kScanMaxPaths = 16384;   // 4096 path tiles: inside the grid's z range
+int scan_check_args(Ctx *c, int nprof, int npath, int nwn, int nlay_max, int sfc_per_path) {
+    if (nprof < 1 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (nlay_max > 603) { c->err = "nlay_max exceeds MXLAY=603 (the bound of monortm_hip_modm, which O comes from)"; return MONORTM_EARG; }
+    if (npath < 1 || npath > kScanMaxPaths) { c->err = "npath outside 1.." + std::to_string(kScanMaxPaths); return MONORTM_EARG; }
+    if (sfc_per_path != 0 && sfc_per_path != 1) { c->err = "sfc_per_path must be 0 or 1"; return MONORTM_EARG; }
+    return MONORTM_OK;
+}
+template <typename R>
+bool scan_path_ok(const void *path, int nprof, int npath, const int *nlay, int nlay_max, int *bp, int *bj, int *bl) {
+    const R *f = static_cast<const R *>(path);
+    for (int p = 0; p < nprof; p++)
+        for (int j = 0; j < npath; j++)
+            for (int l = 0; l < nlay[p]; l++) {
+                const double v = (double)f[((size_t)p * npath + j) * nlay_max + l];
+                if (!(v >= 0. && std::isfinite(v))) { *bp = p; *bj = j; *bl = l; return false; }
+            }
+    return true;
+}
+
+// nlay and the factors of the active layers of a whole host call: checked before anything is staged or launched, on every device
+int scan_check_path(Ctx *c, int nprof, int npath, const int *nlay, int nlay_max, const void *path) {
+    for (int p = 0; p < nprof; p++)
+        if (nlay[p] < 1 || nlay[p] > nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
+    int bp = 0, bj = 0, bl = 0;
+    const bool ok = c->real_kind == 4 ? scan_path_ok<float>(path, nprof, npath, nlay, nlay_max, &bp, &bj, &bl)
+                                      : scan_path_ok<double>(path, nprof, npath, nlay, nlay_max, &bp, &bj, &bl);
+    if (!ok) {
+        c->err = "path factor negative or not finite: profile " + std::to_string(bp) + " path " + std::to_string(bj) + " layer " + std::to_string(bl);
+        return MONORTM_EARG;
+    }
+    return MONORTM_OK;
+}
+
+// One device's share of a host-buffer scan.  The arguments are those monortm_hip_rtm_scan has checked (scan_check_args,
+// scan_check_path) for the whole call.
+static int rtm_scan_host(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int iout,
+                         const void *T, const void *TZ, const void *O, const void *path, void *tmpsfc, int sfc_per_path, const void *emiss,
+                         const void *reflc, void *RUP, void *RDN, void *TRTOT, void *RAD, void *TB, void *TMR, std::function<int()> *defer) {
+    void *ctx = c;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn, ppw = pw * npath;
+    Arena in, out;
+    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_tz = (size_t)nprof * (nlay_max + 1) * d,
+                 b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d, b_sfc = (sfc_per_path ? ppw : pw) * d, b_out = ppw * d;
+    // O straight from the preceding MODM call?  Then it is still on the device (see Ctx::lastO): no second upload
+    const bool resident = c->lastO.dev && c->lastO.nprof == nprof && c->lastO.nwn == nwn && c->lastO.nlay_max == nlay_max &&
+                          c->lastO.bytes == npl * nwn * d && memcmp(O, c->lastO.host, c->lastO.bytes) == 0;
+    if (resident) c->o_reused_scan++;
+    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_T = in.add(b_l), i_TZ = in.add(b_tz), i_f = in.add(b_f),
+                 i_em = in.add(b_sfc), i_rf = in.add(b_sfc), i_ts = in.add(b_p), i_O = resident ? 0 : in.add(b_o);
+    const size_t o_up = out.add(b_out), o_dn = out.add(b_out), o_tr = out.add(b_out), o_rad = out.add(b_out), o_tb = out.add(b_out),
+                 o_tmr = out.add(b_out), o_ts = out.add(b_p);
+    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
+    HIPCHK(c, stage_get(c, 4, in.size, true, &hin));
+    HIPCHK(c, stage_get(c, 5, in.size, false, &din));
+    HIPCHK(c, stage_get(c, 6, out.size, true, &hout));
+    HIPCHK(c, stage_get(c, 7, out.size, false, &dout));
+    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
+    HostClock hc(c, 2);
+    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_T, T, b_l);
+    memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_f, path, b_f); memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
+    memcpy(h + i_ts, tmpsfc, b_p);
+    if (!resident) memcpy(h + i_O, O, b_o);
+    hc.mark(0);
+    // (tmpsfc is in/out: its piece of the input arena also seeds the output arena)
+    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs, nullptr, nullptr, dz + o_ts, h + i_ts, (b_p + 255) & ~size_t(255)));
+    if (iout != 1) HIPCHK(c, hipMemsetAsync(dz + o_tb, 0, b_out, c->hs));
+    const void *dO = resident ? c->lastO.dev : static_cast<const void *>(dv + i_O);
+    int rc = monortm_hip_rtm_scan_dev(ctx, nprof, npath, nwn, (double *)(dv + i_wn), (int *)(dv + i_nl), nlay_max, (int *)(dv + i_irt), iout,
+                                      dv + i_T, dv + i_TZ, dO, dv + i_f, dz + o_ts, sfc_per_path, dv + i_em, dv + i_rf, dz + o_up, dz + o_dn,
+                                      dz + o_tr, dz + o_rad, dz + o_tb, TMR ? dz + o_tmr : nullptr, c->hs);
+    if (rc) return rc;
+    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs));
+    hc.mark(1);
+    auto complete = [=]() mutable -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->hs));
+        hc.mark(2);
+        const char *ho = static_cast<const char *>(hout);
+        memcpy(RUP, ho + o_up, b_out); memcpy(RDN, ho + o_dn, b_out); memcpy(TRTOT, ho + o_tr, b_out); memcpy(RAD, ho + o_rad, b_out);
+        if (iout == 1) memcpy(TB, ho + o_tb, b_out);
+        if (TMR) memcpy(TMR, ho + o_tmr, b_out);
         memcpy(tmpsfc, ho + o_ts, b_p);
         hc.mark(3);
         return MONORTM_OK;
@@ -988,6 +1082,7 @@ long long monortm_hip_counter(void *ctx, int which) {
         return t;
     }
     if (which == 0) return c->o_reused;
+    if (which == 1) return c->o_reused_scan;
     return -1;
 }
 
@@ -1596,6 +1691,69 @@ int monortm_hip_rtm(void *ctx, int nprof, int nwn, const double *wn, const int *
         const int r = rtm_host(s, n, nwn, wn, nlay + p0, nlay_max, irt + p0, iout, off(T, p0 * l), off(TZ, p0 * (l + d)), off(O, p0 * w),
                                off(tmpsfc, p0 * d), off(emiss, p0 * v), off(reflc, p0 * v), off(RUP, p0 * v), off(RDN, p0 * v),
                                off(TRTOT, p0 * v), off(RAD, p0 * v), off(TB, p0 * v), TMR ? off(TMR, p0 * v) : nullptr, &fin[g]);
+        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
+    }
+    for (int g = 0; g < G; g++)
+        if (fin[g]) {
+            const int r = fin[g]();
+            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
+        }
+    return rc;
+}
+
+// ---- path scans ---------------------------------------------------------------------------------
+int monortm_hip_rtm_scan_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                             int iout, const void *T, const void *TZ, const void *O, const void *path, void *tmpsfc, int sfc_per_path,
+                             const void *emiss, const void *reflc, void *RUP, void *RDN, void *TRTOT, void *RAD, void *TB, void *TMR,
+                             void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!c->shards.empty()) return multi_only_host(c);
+    hipStream_t s = (hipStream_t)stream;
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !RUP || !RDN || !TRTOT || !RAD || !TB) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (int rcd = check_device(c)) return rcd;
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    RtmScanArgs a{};
+    a.real_kind = c->real_kind;
+    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.iout = iout; a.sfc_per_path = sfc_per_path;
+    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    a.tmpsfc = tmpsfc; a.RUP = RUP; a.RDN = RDN; a.TRTOT = TRTOT; a.RAD = RAD; a.TB = TB; a.TMR = TMR;
+    a.errflag = c->errflag;
+    Ctx::Ev ev{};
+    prof_begin(c, s, 2, ev);
+    launch_rtm_scan(a, s);
+    prof_end(c, s, ev);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+int monortm_hip_rtm_scan(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int iout,
+                         const void *T, const void *TZ, const void *O, const void *path, void *tmpsfc, int sfc_per_path, const void *emiss,
+                         const void *reflc, void *RUP, void *RDN, void *TRTOT, void *RAD, void *TB, void *TMR) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    DeviceGuard guard;
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !RUP || !RDN || !TRTOT || !RAD || !TB) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
+    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
+    if (c->shards.empty())
+        return rtm_scan_host(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, iout, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, RUP, RDN,
+                             TRTOT, RAD, TB, TMR, nullptr);
+    const int G = (int)c->shards.size();
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
+    const size_t f = l * npath, vo = v * npath, vs = sfc_per_path ? vo : v;
+    std::vector<std::function<int()>> fin(G);
+    int rc = MONORTM_OK;
+    for (int g = 0; g < G; g++) {
+        int p0, n;
+        shard_block(nprof, G, g, &p0, &n);
+        if (n < 1) continue;
+        Ctx *s = c->shards[g];
+        const int r = rtm_scan_host(s, n, npath, nwn, wn, nlay + p0, nlay_max, irt + p0, iout, off(T, p0 * l), off(TZ, p0 * (l + d)),
+                                    off(O, p0 * w), off(path, p0 * f), off(tmpsfc, p0 * d), sfc_per_path, off(emiss, p0 * vs),
+                                    off(reflc, p0 * vs), off(RUP, p0 * vo), off(RDN, p0 * vo), off(TRTOT, p0 * vo), off(RAD, p0 * vo),
+                                    off(TB, p0 * vo), TMR ? off(TMR, p0 * vo) : nullptr, &fin[g]);
         if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
     }
     for (int g = 0; g < G; g++)

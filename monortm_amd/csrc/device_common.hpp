@@ -113,7 +113,7 @@ __host__ __device__ inline int far_xcd_items(int nint, int k, int xlo, int nx) {
     return (nint - (k - xlo) + nx - 1) / nx;
 }
 
-enum : int { ERRBIT_TEMP = 1, ERRBIT_SDV = 2, ERRBIT_ARG = 4 };  // ARG: nlay[p] outside 1..nlay_max or wn not ascending (device arrays)
+enum : int { ERRBIT_TEMP = 1, ERRBIT_SDV = 2, ERRBIT_ARG = 4 };  // ARG: nlay[p] outside 1..nlay_max, wn not ascending or a bad path factor (device arrays)
 
 struct DevTables {  // device copies of monortm_tables.h
     const double *self296, *self260, *frgn296, *fco2, *n2c296, *n2sf296, *n2c220, *n2sf220, *xfac_rhu, *xfacco2,
@@ -194,6 +194,20 @@ struct RtmArgs {
     const void *T, *TZ, *O, *emiss, *reflc;
     const int *nlay, *irt;
     void *tmpsfc, *RUP, *RDN, *TRTOT, *RAD, *TB, *TMR;
+};
+
+// Path scans (rtm_scan_kernel.hip): CALCTMR + RTM along npath paths per profile from ONE set of optical
+// depths.  path [nprof][npath][nlay_max]: the factor of every layer's optical depth along the path; emiss, reflc [nprof][nwn]
+// (sfc_per_path = 0) or [nprof][npath][nwn] (1); outputs [nprof][npath][nwn].  A factor of an active layer that is negative or
+// not finite raises ERRBIT_ARG in errflag.
+struct RtmScanArgs {
+    int nprof, npath, nwn, nlay_max, iout;
+    int real_kind, sfc_per_path;
+    const double *wn;
+    const void *T, *TZ, *O, *path, *emiss, *reflc;
+    const int *nlay, *irt;
+    void *tmpsfc, *RUP, *RDN, *TRTOT, *RAD, *TB, *TMR;
+    int *errflag;
 };
 
 // Jacobians (jacobian_kernel.hip).  The adjoint of RTM: O, T, TZ, surface in; RAD, TB and the derivatives
@@ -336,6 +350,8 @@ void launch_kat(int which, int n, const double *in, const double *tab, double *o
 void launch_xsec(const ModmArgs &a, const DevXsec &x, hipStream_t s);
 // rtm_kernel.hip
 void launch_rtm(const RtmArgs &a, hipStream_t s);
+// rtm_scan_kernel.hip
+void launch_rtm_scan(const RtmScanArgs &a, hipStream_t s);
 // jacobian_kernel.hip (full = FULL instantiation, real_kind 8)
 void launch_jac_perturb(const JacPerturbArgs &a, hipStream_t s);
 void launch_rtm_jac(const RtmJacArgs &a, bool full, hipStream_t s);

@@ -1,0 +1,187 @@
+// rtm_scan_kernel.hip - CALCTMR + RAD_UP_DN + RTM (reference src/RTMmono.f90) along several paths through one atmosphere, from ONE
+// set of optical depths, for gfx950.  See DESIGN.md section 3.7.
+#include "device_common.hpp"
+
+namespace {
+using namespace monortm_dev;
+
+__device__ __forceinline__ double bb_fn(double v, double fbeta) { return K_RADCN1 * (v * v * v) / (exp(v * fbeta) - 1.); }
+
+// The layout of rtm_kernel (block = 64 wavenumbers x G layer groups of a profile, every thread walks its group of layers once from
+// the top down, group sums combined through LDS in the reference's visiting order) with NP paths per thread; blockIdx.z = tile of
+// NP paths, the last tile may hold fewer (npl; a workgroup-uniform count, so the guards below are scalar branches).
+//   per layer, once for the tile: (double)O, B(T_layer), B at the lower level;
+//   per path: tau = (double)O * factor rounded ONCE (__dmul_rn: no contraction into the sums that follow), which is the value a
+//   caller's pre-scaled O holds in double, then exactly the terms of rtm_kernel.
+// hc / kT of the layers and levels and the tile's factors are formed once per workgroup (LDS); factors of layers >= nlay[p] are
+// never read.  The LDS pieces of the group sums hold one path at a time: 24 KB at G = 16 whatever NP is.
+template <typename R, int G, int NP>
+__global__ __launch_bounds__(64 * G) void rtm_scan_kernel(RtmScanArgs a) {
+    __shared__ double sUp[G][64], sDn[G][64], sEx[G][64];
+    extern __shared__ __attribute__((aligned(16))) double sBeta[];  // [nlay_max] hc/kT of the layers, [nlay_max + 1] of the levels, [NP][nlay_max] factors
+    const int lane = threadIdx.x, g = threadIdx.y;
+    const int iw0 = blockIdx.x * 64 + lane, prof = blockIdx.y;
+    const int j0 = blockIdx.z * NP, npl = min(NP, a.npath - j0);
+    const int nwn = a.nwn, lm = a.nlay_max;
+    const bool valid = iw0 < nwn;
+    const int iw = valid ? iw0 : nwn - 1;
+    const int nlay = max(0, min(a.nlay[prof], lm)), irt = a.irt[prof];  // out-of-range counts are flagged by lines_kernel / the host
+    const double VV = a.wn[iw];
+    const R *O = rp<R>(a.O) + (size_t)prof * lm * nwn + iw;
+    const R *T = rp<R>(a.T) + (size_t)prof * lm, *TZ = rp<R>(a.TZ) + (size_t)prof * (lm + 1);
+    const R *F = rp<R>(a.path) + ((size_t)prof * a.npath + j0) * lm;
+    double *sBl = sBeta, *sBz = sBeta + lm, *sF = sBeta + 2 * lm + 1;
+    for (int l = g * 64 + lane; l < 2 * nlay + 1; l += 64 * G) {
+        if (l < nlay) sBl[l] = K_RADCN2 / (double)T[l];
+        else sBz[l - nlay] = K_RADCN2 / (double)TZ[l - nlay];
+    }
+    for (int j = 0; j < npl; j++)
+        for (int l = g * 64 + lane; l < nlay; l += 64 * G) {
+            const double f = (double)F[(size_t)j * lm + l];
+            if (!(f >= 0. && f < __builtin_inf())) atomicOr(a.errflag, ERRBIT_ARG);
+            sF[j * lm + l] = f;
+        }
+    __syncthreads();
+    const int chunk = (nlay + G - 1) / G;
+    const int l0 = min(nlay, g * chunk), l1 = min(nlay, l0 + chunk);  // 0-based layer range [l0, l1)
+
+    double part[NP];
+#pragma unroll
+    for (int j = 0; j < NP; j++) part[j] = 0.;
+    for (int l = l0; l < l1; l++) {
+        const double o = (double)O[(size_t)l * nwn];
+#pragma unroll
+        for (int j = 0; j < NP; j++)
+            if (j < npl) part[j] = part[j] + __dmul_rn(o, sF[j * lm + l]);
+    }
+    double above[NP], ODTOT[NP];
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+        above[j] = 0.;
+        ODTOT[j] = 0.;
+        if (j < npl) {
+            sUp[g][lane] = part[j];
+            __syncthreads();
+            double below = 0., tot = 0.;
+            for (int gg = 0; gg < G; gg++) {
+                if (gg < g) below = below + sUp[gg][lane];
+                tot = tot + sUp[gg][lane];
+            }
+            ODTOT[j] = tot;
+            above[j] = tot - below - part[j];
+            __syncthreads();
+        }
+    }
+    const double c3 = K_RADCN1 * (VV * VV * VV);
+    const bool up = irt != 3;
+
+    double RUP[NP], RDN[NP], sumexp[NP], ODTd[NP], ODTu[NP];
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+        RUP[j] = 0.;
+        RDN[j] = 0.;
+        sumexp[j] = 0.;
+        ODTd[j] = ODTOT[j] - above[j];  // downward sweep: optical depth from the surface up to and including the layer, running difference
+        ODTu[j] = above[j];             // upward sweep: optical depth above the layer
+    }
+    {  // RTMmono.f90:193-217 and CALCTMR :302-315, layers l1 .. l0+1 (1-based)
+        double bb_top = (up && l1 > l0) ? planck(c3, VV, sBz[l1]) : 0.;  // B at the upper level of the group's top layer
+        for (int l = l1; l >= l0 + 1; l--) {
+            const double o = (double)O[(size_t)(l - 1) * nwn];
+            const double bb = planck(c3, VV, sBl[l - 1]), bbz = planck(c3, VV, sBz[l - 1]);
+#pragma unroll
+            for (int j = 0; j < NP; j++)
+                if (j < npl) {
+                    const double ODVI = __dmul_rn(o, sF[j * lm + l - 1]);
+                    const double TRI = exp_cw(-ODVI);
+                    const double pade = 0.193 * ODVI + 0.013 * (ODVI * ODVI);
+                    const double rp1 = rcp2(1. + pade), emis = 1. - TRI;
+                    ODTd[j] = ODTd[j] - ODVI;
+                    const double TRd = exp_cw(-ODTd[j]);
+                    const double bnum = bb + pade * bbz;
+                    RDN[j] = RDN[j] + ((TRd * emis) * bnum) * rp1;            // TR (1 - TRI) (bb + pade bba) / (1 + pade), RTMmono.f90:216
+                    sumexp[j] = sumexp[j] + ((bnum * rp1) * TRd) * emis;  // beff TR (1 - TRI), RTMmono.f90:312-313
+                    if (up) {
+                        const double TRu = exp_cw(-ODTu[j]);
+                        RUP[j] = RUP[j] + ((TRu * emis) * (bb + pade * bb_top)) * rp1;  // RTMmono.f90:203
+                        ODTu[j] = ODTu[j] + ODVI;
+                    }
+                }
+            bb_top = bbz;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; j++)
+        if (j < npl) {
+            sUp[g][lane] = RUP[j];
+            sDn[g][lane] = RDN[j];
+            sEx[g][lane] = sumexp[j];
+            __syncthreads();
+            if (g == 0) {
+                double u = 0., d = 0., e = 0.;
+                for (int gg = 0; gg < G; gg++) u = u + sUp[gg][lane];
+                for (int gg = G - 1; gg >= 0; gg--) {
+                    d = d + sDn[gg][lane];
+                    e = e + sEx[gg][lane];
+                }
+                RUP[j] = u;
+                RDN[j] = d;
+                sumexp[j] = e;
+            }
+            __syncthreads();
+        }
+    if (g != 0 || !valid) return;
+    const double TSKY = 2.75;
+    double tmpsfc = (double)wp<R>(a.tmpsfc)[prof];
+    if (irt == 3 || irt == 2) tmpsfc = TSKY;  // RTMmono.f90:113-124
+    const double SURFRAD = bb_fn(VV, K_RADCN2 / tmpsfc), COSMOS = bb_fn(VV, K_RADCN2 / TSKY);
+    // TMPSFC is in/out as in rtm_kernel: lanes that still read the old value ignore it exactly when it is overwritten (irt = 2,3)
+    if (iw == 0 && blockIdx.z == 0 && (irt == 3 || irt == 2)) wp<R>(a.tmpsfc)[prof] = (R)TSKY;
+#pragma unroll
+    for (int j = 0; j < NP; j++)
+        if (j < npl) {
+            const double TRTOT = exp(-ODTOT[j]);
+            const size_t o = ((size_t)prof * a.npath + j0 + j) * nwn + iw;
+            const size_t os = a.sfc_per_path ? o : (size_t)prof * nwn + iw;
+            if (a.TMR) {
+                const double radtmr = sumexp[j] / (1. - exp(-1 * ODTOT[j]));
+                const double x = K_RADCN1 * (VV * VV * VV) / radtmr + 1.;
+                wp<R>(a.TMR)[o] = (R)(K_RADCN2 * VV / log(x));
+            }
+            const double ESFC = (double)rp<R>(a.emiss)[os], RSFC = (double)rp<R>(a.reflc)[os];
+            double RAD = 0.;
+            if (irt == 1) RAD = RUP[j] + TRTOT * (ESFC * SURFRAD + RSFC * (RDN[j] + TRTOT * COSMOS));
+            if (irt == 2) RAD = RUP[j] + TRTOT * (RDN[j] + TRTOT * COSMOS);
+            if (irt == 3) RAD = RDN[j] + (TRTOT * COSMOS);
+            wp<R>(a.RUP)[o] = (R)RUP[j];
+            wp<R>(a.RDN)[o] = (R)RDN[j];
+            wp<R>(a.TRTOT)[o] = (R)TRTOT;
+            wp<R>(a.RAD)[o] = (R)RAD;
+            if (a.iout == 1) {
+                const double X = K_RADCN1 * (VV * VV * VV) / RAD + 1.;
+                wp<R>(a.TB)[o] = (R)(K_RADCN2 * VV / log(X));
+            }
+        }
+}
+
+constexpr int SCAN_NP = 4;  // paths per thread: 8 running doubles per path -> 64 of the 128 VGPRs a 1024-thread workgroup may use
+
+template <typename R>
+void launch_r(const RtmScanArgs &a, hipStream_t s) {
+    dim3 grid((a.nwn + 63) / 64, a.nprof, (a.npath + SCAN_NP - 1) / SCAN_NP);
+    // the rule of launch_rtm with the path tiles counted: few workgroups and many layers -> 16 layer groups
+    const bool few = (long long)grid.x * grid.y * grid.z < 256 && a.nlay_max >= 48;
+    const size_t lds = sizeof(double) * ((size_t)(2 * a.nlay_max + 1) + (size_t)SCAN_NP * a.nlay_max);
+    if (few) hipLaunchKernelGGL((rtm_scan_kernel<R, 16, SCAN_NP>), grid, dim3(64, 16), lds, s, a);
+    else if (a.nlay_max >= 24) hipLaunchKernelGGL((rtm_scan_kernel<R, 8, SCAN_NP>), grid, dim3(64, 8), lds, s, a);
+    else hipLaunchKernelGGL((rtm_scan_kernel<R, 2, SCAN_NP>), grid, dim3(64, 2), lds, s, a);
+}
+
+}  // namespace
+
+namespace monortm_dev {
+void launch_rtm_scan(const RtmScanArgs &a, hipStream_t s) {
+    if (a.real_kind == 4) launch_r<float>(a, s);
+    else launch_r<double>(a, s);
+}
+}  // namespace monortm_dev
