@@ -108,7 +108,9 @@ int monortm_hip_xsec_regions(void *ctx);
  * (:1150)  3 SDVOIGT(deltnu,alphal,alphad,sdep) (:965)  4 RADFN(vi,xkt) (src/lblrtm_sub.f90:36)  5 AtoB(aa) on the TIPS
  * temperature grid with the 119-point table tab119 (src/tips_2003.f90:4610)  6 ODCLW_TKC(wn,temp,clw)
  * (src/CloudOptProp.f90:29)  7 scor(mol,iso) of TIPS_2003(39,T,scor) for args (T, mol, iso) (src/tips_2003.f90:2-298; out[.][1] = 1
- * where the reference would STOP, 0 where it leaves scor untouched).  Returns MONORTM_ESDV when SDVOIGT meets the
+ * where the reference would STOP, 0 where it leaves scor untouched)  8 HALFWHM_D(mol,iso,xnu,T) (src/modm.f90:442)
+ * 9 bb_fn(v,fbeta) (src/RTMmono.f90:223) as the radiance kernels form it  10 exp_cw(x) and 11 rcp2(x), the exp() and 1 / x
+ * of the radiance kernels (device_common.hpp), for their ulp bounds.  Returns MONORTM_ESDV when SDVOIGT meets the
  * reference's STOP condition. */
 int monortm_hip_kat(void *ctx, int which, int n, const double *args, const double *tab119, double *out);
 

@@ -405,7 +405,8 @@ class MonoRTM:
         self._chk(self.lib.monortm_hip_set_option(self.ctx, name.encode(), str(value).encode()))
 
     def kat(self, which: int, args: np.ndarray, tab: np.ndarray | None = None) -> np.ndarray:
-        """Known-answer hook: device versions of W4 / SD_Humlicek / SDVOIGT / RADFN / AtoB / ODCLW_TKC, args [n,4] -> [n,2]."""
+        """Known-answer hook: device versions of W4 / SD_Humlicek / SDVOIGT / RADFN / AtoB / ODCLW_TKC / TIPS / HALFWHM_D / bb_fn and
+        (which = 10, 11) the radiance kernels' exp_cw / rcp2, args [n,4] -> [n,2]."""
         a = _np(args)
         t = _np(tab) if tab is not None else None
         out = np.zeros((len(a), 2))

@@ -1053,7 +1053,7 @@ int monortm_hip_kat(void *ctx, int which, int n, const double *args, const doubl
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
     if (!c->shards.empty()) c = c->shards[0];
-    if (which < 1 || which > 9 || n < 1 || !args || !out || (which == 5 && !tab119)) { c->err = "bad known-answer request"; return MONORTM_EARG; }
+    if (which < 1 || which > 11 || n < 1 || !args || !out || (which == 5 && !tab119)) { c->err = "bad known-answer request"; return MONORTM_EARG; }
     DeviceGuard guard;
     HIPCHK(c, hipSetDevice(c->device));
     double *din = nullptr, *dtab = nullptr, *dout = nullptr;

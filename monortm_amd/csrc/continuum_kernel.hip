@@ -853,6 +853,8 @@ __global__ void kat_kernel(int which, int n, const double *in, const double *tab
         const int mol = (int)a[0], iso = (int)a[1];
         if (mol >= 1 && mol <= MXMOL && iso >= 1 && iso <= 9) r0 = a[2] * doppler_factor(tips.smass[(mol - 1) * 9 + iso - 1], a[3]);
     } else if (which == 9) r0 = planck(K_RADCN1 * (a[0] * a[0] * a[0]), a[0], a[1]);  // bb_fn(v, fbeta) as rtm_kernel forms it
+    else if (which == 10) r0 = exp_cw(a[0]);  // the exp() and 1 / x of the radiance kernels (device_common.hpp), held to their
+    else if (which == 11) r0 = rcp2(a[0]);    // documented ulp bounds by tests/test_function_kat.py
     out[2 * i] = r0;
     out[2 * i + 1] = r1;
 }

@@ -271,6 +271,56 @@ __device__ __forceinline__ double planck(double c3, double v, double fbeta) {
     const double e = exp_cw(v * fbeta) - 1.;
     return (e == __builtin_inf()) ? 0. : c3 * rcp2(e);
 }
+// ---- the arithmetic rtm_kernel, rtm_scan_kernel and rtm_jac_kernel's forward pass share --------------------------------------------------------------------------
+// A scan path with factor 1 is monortm_hip_rtm's result bit for bit (tests/test_rtm_extremes.py).  Left to the compiler, which
+// products fuse into which sums depends on the surrounding code (scalars in one kernel, per-path arrays in the other) - RAD came out
+// one ulp apart.  So both kernels call these, every product-sum is spelled out as an fma or a separately rounded product, and
+// contraction is off inside them.
+// Planck function with the library exp, as RTM's surface and cosmic terms (RTMmono.f90:223-237)
+__device__ __forceinline__ double bb_fn(double v, double fbeta) {
+#pragma clang fp contract(off)
+    return K_RADCN1 * (v * v * v) / (exp(v * fbeta) - 1.);
+}
+// One layer's terms of RAD_UP_DN (RTMmono.f90:193-217) and CALCTMR (:302-315): ODVI the layer's optical depth, bb / bbz / bb_top the
+// Planck function of the layer, its lower and its upper level; ODTd (the optical depth up to and including the layer) and ODTu
+// (above the layer) are advanced to the layer below
+__device__ __forceinline__ void rtm_layer_terms(double ODVI, double bb, double bbz, double bb_top, bool up, double &ODTd, double &ODTu,
+                                                double &RUP, double &RDN, double &sumexp) {
+#pragma clang fp contract(off)
+    const double TRI = exp_cw(-ODVI);
+    const double pade = fma(0.013, ODVI * ODVI, 0.193 * ODVI);
+    const double rp1 = rcp2(1. + pade), emis = 1. - TRI;
+    ODTd = ODTd - ODVI;
+    const double TRd = exp_cw(-ODTd);
+    const double bnum = fma(pade, bbz, bb);
+    RDN = fma((TRd * emis) * bnum, rp1, RDN);        // TR (1 - TRI) (bb + pade bba) / (1 + pade), RTMmono.f90:216
+    sumexp = fma((bnum * rp1) * TRd, emis, sumexp);  // beff TR (1 - TRI), RTMmono.f90:312-313
+    if (up) {
+        const double TRu = exp_cw(-ODTu);
+        RUP = fma((TRu * emis) * fma(pade, bb_top, bb), rp1, RUP);  // RTMmono.f90:203
+        ODTu = ODTu + ODVI;
+    }
+}
+// RTM's combination of the sweeps (RTMmono.f90:138-147), TB and CALCTMR's mean radiating temperature (:316-321); TB and TMR only
+// where the caller stores them (want_tb, want_tmr; 0 otherwise)
+__device__ __forceinline__ void rtm_combine(int irt, double VV, double RUP, double RDN, double sumexp, double ODTOT, double ESFC, double RSFC,
+                                            double SURFRAD, double COSMOS, bool want_tb, bool want_tmr, double &TRTOT, double &RAD,
+                                            double &TB, double &TMR) {
+#pragma clang fp contract(off)
+    const double c3 = K_RADCN1 * (VV * VV * VV);
+    TRTOT = exp(-ODTOT);
+    TMR = 0.;
+    if (want_tmr) {
+        const double radtmr = sumexp / (1. - exp(-1 * ODTOT));
+        TMR = K_RADCN2 * VV / log(c3 / radtmr + 1.);
+    }
+    const double sky = fma(TRTOT, COSMOS, RDN);
+    RAD = 0.;
+    if (irt == 1) RAD = fma(TRTOT, fma(RSFC, sky, ESFC * SURFRAD), RUP);
+    if (irt == 2) RAD = fma(TRTOT, sky, RUP);
+    if (irt == 3) RAD = sky;
+    TB = want_tb ? K_RADCN2 * VV / log(c3 / RAD + 1.) : 0.;
+}
 // Doppler half width per unit wavenumber, HALFWHM_D / XNU (modm.f90:442-454) for an isotopologue of mass M [g/mol]
 __device__ __forceinline__ double doppler_factor(double M, double T) {
     return sqrt(2. * log(2.) * ((K_BOLTZ * T) / (M / K_AVOGAD))) / K_CLIGHT;

@@ -95,24 +95,13 @@ __global__ __launch_bounds__(64 * G) void rtm_jac_kernel(RtmJacArgs a) {
     // ---- pass 1: the forward sums of rtm_kernel (RTMmono.f90:193-217), layers l1 .. l0+1 (1-based)
     double RUPg = 0., RDNg = 0.;
     {
-        double ODTd = ODTOT - above, ODTu = above;
+        double ODTd = ODTOT - above, ODTu = above, unused = 0.;  // (CALCTMR's sum: not needed here)
         double bb_top = (up && l1 > l0) ? planck(c3, VV, sBz[l1]) : 0.;
         for (int l = l1; l >= l0 + 1; l--) {
             const double ODVI = (double)O[(size_t)(l - 1) * nwn];
             const double bb = planck(c3, VV, sBl[l - 1]), bbz = planck(c3, VV, sBz[l - 1]);
-            const double TRI = exp_cw(-ODVI);
-            const double pade = 0.193 * ODVI + 0.013 * (ODVI * ODVI);
-            const double rp1 = rcp2(1. + pade), emis = 1. - TRI;
-            ODTd = ODTd - ODVI;
-            const double TRd = exp_cw(-ODTd);
-            const double bnum = bb + pade * bbz;
-            RDNg = RDNg + ((TRd * emis) * bnum) * rp1;
-            if (up) {
-                const double TRu = exp_cw(-ODTu);
-                RUPg = RUPg + ((TRu * emis) * (bb + pade * bb_top)) * rp1;
-                ODTu = ODTu + ODVI;
-                bb_top = bbz;
-            }
+            rtm_layer_terms(ODVI, bb, bbz, bb_top, up, ODTd, ODTu, RUPg, RDNg, unused);  // rtm_kernel's rounding (device_common.hpp)
+            bb_top = bbz;
         }
     }
     sUp[g][lane] = RUPg;
@@ -138,20 +127,22 @@ __global__ __launch_bounds__(64 * G) void rtm_jac_kernel(RtmJacArgs a) {
     const double ESFC = (double)rp<R>(a.emiss)[o], RSFC = (double)rp<R>(a.reflc)[o];
     double RAD = 0., cU = 0., cD = 0., cT = 0.;   // dRAD/dRUP, dRAD/dRDN, dRAD/dTRTOT
     if (irt == 1) {
-        RAD = RUP + TRTOT * (ESFC * SURFRAD + RSFC * (RDN + TRTOT * COSMOS));
+        RAD = fma(TRTOT, fma(RSFC, fma(TRTOT, COSMOS, RDN), ESFC * SURFRAD), RUP);   // (as rtm_combine rounds it, device_common.hpp)
         cU = 1.; cD = TRTOT * RSFC; cT = ESFC * SURFRAD + RSFC * RDN + 2. * RSFC * TRTOT * COSMOS;
     }
     if (irt == 2) {
-        RAD = RUP + TRTOT * (RDN + TRTOT * COSMOS);
+        RAD = fma(TRTOT, fma(TRTOT, COSMOS, RDN), RUP);
         cU = 1.; cD = TRTOT; cT = RDN + 2. * TRTOT * COSMOS;
     }
     if (irt == 3) {
-        RAD = RDN + (TRTOT * COSMOS);
+        RAD = fma(TRTOT, COSMOS, RDN);
         cU = 0.; cD = 1.; cT = COSMOS;
     }
     const double X = c3 / RAD + 1., lx = log(X);
     double dq = 1.;   // dq/dRAD
-    if (a.quantity == 1) dq = (K_RADCN2 * VV) * c3 / ((lx * lx) * X * (RAD * RAD));
+    // dTB/dRAD = RADCN2 v (c3 / RAD) / (ln^2 X X RAD); RAD enters once per factor: RAD^2 underflows for RAD < 1.5e-154 (a cold opaque
+    // column in the ultraviolet), where the derivative is finite
+    if (a.quantity == 1) dq = (K_RADCN2 * VV) * ((c3 / RAD) / X) / ((lx * lx) * RAD);
     if (g == 0 && valid) {
         wp<R>(a.RAD)[o] = (R)RAD;
         wp<R>(a.TB)[o] = (R)(K_RADCN2 * VV / lx);

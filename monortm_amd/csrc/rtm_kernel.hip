@@ -8,8 +8,6 @@ using namespace monortm_dev;
 // rtm_kernel: CALCTMR (RTMmono.f90:239-325) + RAD_UP_DN (:157-221) + RTM (:13-155); lane = (profile, wn)
 // ------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ double bb_fn(double v, double fbeta) { return K_RADCN1 * (v * v * v) / (exp(v * fbeta) - 1.); }
-
 // Block = 64 wavenumbers x G layer groups.  The recurrences of RAD_UP_DN are sums of independent terms once the optical depth
 // above / below a layer is known.  Every thread walks its contiguous group of layers ONCE, from the top of the group down, and
 // forms the terms of both sweeps and of CALCTMR from shared pieces (round 4; rounds 1-3 walked the group twice and formed every
@@ -65,20 +63,8 @@ __global__ __launch_bounds__(64 * G) void rtm_kernel(RtmArgs a) {
         for (int l = l1; l >= l0 + 1; l--) {
             const double ODVI = (double)O[(size_t)(l - 1) * nwn];
             const double bb = planck(c3, VV, sBl[l - 1]), bbz = planck(c3, VV, sBz[l - 1]);
-            const double TRI = exp_cw(-ODVI);
-            const double pade = 0.193 * ODVI + 0.013 * (ODVI * ODVI);
-            const double rp1 = rcp2(1. + pade), emis = 1. - TRI;
-            ODTd = ODTd - ODVI;
-            const double TRd = exp_cw(-ODTd);
-            const double bnum = bb + pade * bbz;
-            RDN = RDN + ((TRd * emis) * bnum) * rp1;      // TR (1 - TRI) (bb + pade bba) / (1 + pade), RTMmono.f90:216
-            sumexp = sumexp + ((bnum * rp1) * TRd) * emis;  // beff TR (1 - TRI), RTMmono.f90:312-313
-            if (up) {
-                const double TRu = exp_cw(-ODTu);
-                RUP = RUP + ((TRu * emis) * (bb + pade * bb_top)) * rp1;  // RTMmono.f90:203
-                ODTu = ODTu + ODVI;
-                bb_top = bbz;
-            }
+            rtm_layer_terms(ODVI, bb, bbz, bb_top, up, ODTd, ODTu, RUP, RDN, sumexp);  // (shared with rtm_scan_kernel: device_common.hpp)
+            bb_top = bbz;
         }
     }
     sUp[g][lane] = RUP;
@@ -94,22 +80,15 @@ __global__ __launch_bounds__(64 * G) void rtm_kernel(RtmArgs a) {
         RDN = RDN + sDn[gg][lane];
         sumexp = sumexp + sEx[gg][lane];
     }
-    const double TRTOT = exp(-ODTOT);
     const size_t o = (size_t)prof * nwn + iw;
-    if (a.TMR) {
-        const double radtmr = sumexp / (1. - exp(-1 * ODTOT));
-        const double x = K_RADCN1 * (VV * VV * VV) / radtmr + 1.;
-        wp<R>(a.TMR)[o] = (R)(K_RADCN2 * VV / log(x));
-    }
     const double TSKY = 2.75;
     double tmpsfc = (double)wp<R>(a.tmpsfc)[prof];
     if (irt == 3 || irt == 2) tmpsfc = TSKY;  // RTMmono.f90:113-124
     const double SURFRAD = bb_fn(VV, K_RADCN2 / tmpsfc), COSMOS = bb_fn(VV, K_RADCN2 / TSKY);
     const double ESFC = (double)rp<R>(a.emiss)[o], RSFC = (double)rp<R>(a.reflc)[o];
-    double RAD = 0.;
-    if (irt == 1) RAD = RUP + TRTOT * (ESFC * SURFRAD + RSFC * (RDN + TRTOT * COSMOS));
-    if (irt == 2) RAD = RUP + TRTOT * (RDN + TRTOT * COSMOS);
-    if (irt == 3) RAD = RDN + (TRTOT * COSMOS);
+    double TRTOT, RAD, TB, TMR;
+    rtm_combine(irt, VV, RUP, RDN, sumexp, ODTOT, ESFC, RSFC, SURFRAD, COSMOS, a.iout == 1, a.TMR != nullptr, TRTOT, RAD, TB, TMR);
+    if (a.TMR) wp<R>(a.TMR)[o] = (R)TMR;
     // TMPSFC is an in/out argument of the reference's RTM (RTMmono.f90:122).  Lanes of this profile that still
     // read the old value ignore it exactly when it is overwritten (irt = 2,3), so the store needs no ordering.
     if (iw == 0 && (irt == 3 || irt == 2)) wp<R>(a.tmpsfc)[prof] = (R)TSKY;
@@ -117,10 +96,7 @@ __global__ __launch_bounds__(64 * G) void rtm_kernel(RtmArgs a) {
     wp<R>(a.RDN)[o] = (R)RDN;
     wp<R>(a.TRTOT)[o] = (R)TRTOT;
     wp<R>(a.RAD)[o] = (R)RAD;
-    if (a.iout == 1) {
-        const double X = K_RADCN1 * (VV * VV * VV) / RAD + 1.;
-        wp<R>(a.TB)[o] = (R)(K_RADCN2 * VV / log(X));
-    }
+    if (a.iout == 1) wp<R>(a.TB)[o] = (R)TB;
 }
 
 }  // namespace

@@ -5,8 +5,6 @@
 namespace {
 using namespace monortm_dev;
 
-__device__ __forceinline__ double bb_fn(double v, double fbeta) { return K_RADCN1 * (v * v * v) / (exp(v * fbeta) - 1.); }
-
 // The layout of rtm_kernel (block = 64 wavenumbers x G layer groups of a profile, every thread walks its group of layers once from
 // the top down, group sums combined through LDS in the reference's visiting order) with NP paths per thread; blockIdx.z = tile of
 // NP paths, the last tile may hold fewer (npl; a workgroup-uniform count, so the guards below are scalar branches).
@@ -93,19 +91,7 @@ __global__ __launch_bounds__(64 * G) void rtm_scan_kernel(RtmScanArgs a) {
             for (int j = 0; j < NP; j++)
                 if (j < npl) {
                     const double ODVI = __dmul_rn(o, sF[j * lm + l - 1]);
-                    const double TRI = exp_cw(-ODVI);
-                    const double pade = 0.193 * ODVI + 0.013 * (ODVI * ODVI);
-                    const double rp1 = rcp2(1. + pade), emis = 1. - TRI;
-                    ODTd[j] = ODTd[j] - ODVI;
-                    const double TRd = exp_cw(-ODTd[j]);
-                    const double bnum = bb + pade * bbz;
-                    RDN[j] = RDN[j] + ((TRd * emis) * bnum) * rp1;            // TR (1 - TRI) (bb + pade bba) / (1 + pade), RTMmono.f90:216
-                    sumexp[j] = sumexp[j] + ((bnum * rp1) * TRd) * emis;  // beff TR (1 - TRI), RTMmono.f90:312-313
-                    if (up) {
-                        const double TRu = exp_cw(-ODTu[j]);
-                        RUP[j] = RUP[j] + ((TRu * emis) * (bb + pade * bb_top)) * rp1;  // RTMmono.f90:203
-                        ODTu[j] = ODTu[j] + ODVI;
-                    }
+                    rtm_layer_terms(ODVI, bb, bbz, bb_top, up, ODTd[j], ODTu[j], RUP[j], RDN[j], sumexp[j]);  // (device_common.hpp)
                 }
             bb_top = bbz;
         }
@@ -140,27 +126,18 @@ __global__ __launch_bounds__(64 * G) void rtm_scan_kernel(RtmScanArgs a) {
 #pragma unroll
     for (int j = 0; j < NP; j++)
         if (j < npl) {
-            const double TRTOT = exp(-ODTOT[j]);
             const size_t o = ((size_t)prof * a.npath + j0 + j) * nwn + iw;
             const size_t os = a.sfc_per_path ? o : (size_t)prof * nwn + iw;
-            if (a.TMR) {
-                const double radtmr = sumexp[j] / (1. - exp(-1 * ODTOT[j]));
-                const double x = K_RADCN1 * (VV * VV * VV) / radtmr + 1.;
-                wp<R>(a.TMR)[o] = (R)(K_RADCN2 * VV / log(x));
-            }
             const double ESFC = (double)rp<R>(a.emiss)[os], RSFC = (double)rp<R>(a.reflc)[os];
-            double RAD = 0.;
-            if (irt == 1) RAD = RUP[j] + TRTOT * (ESFC * SURFRAD + RSFC * (RDN[j] + TRTOT * COSMOS));
-            if (irt == 2) RAD = RUP[j] + TRTOT * (RDN[j] + TRTOT * COSMOS);
-            if (irt == 3) RAD = RDN[j] + (TRTOT * COSMOS);
+            double TRTOT, RAD, TB, TMR;
+            rtm_combine(irt, VV, RUP[j], RDN[j], sumexp[j], ODTOT[j], ESFC, RSFC, SURFRAD, COSMOS, a.iout == 1, a.TMR != nullptr, TRTOT, RAD,
+                        TB, TMR);
+            if (a.TMR) wp<R>(a.TMR)[o] = (R)TMR;
             wp<R>(a.RUP)[o] = (R)RUP[j];
             wp<R>(a.RDN)[o] = (R)RDN[j];
             wp<R>(a.TRTOT)[o] = (R)TRTOT;
             wp<R>(a.RAD)[o] = (R)RAD;
-            if (a.iout == 1) {
-                const double X = K_RADCN1 * (VV * VV * VV) / RAD + 1.;
-                wp<R>(a.TB)[o] = (R)(K_RADCN2 * VV / log(X));
-            }
+            if (a.iout == 1) wp<R>(a.TB)[o] = (R)TB;
         }
 }
 

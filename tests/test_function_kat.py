@@ -124,3 +124,91 @@ def test_device_functions_match_reference(which, key, tol):
         _check(rt.kat(which, KAT[key + "_in"], KAT["atob_tab"]), key, max(tol, 1e-11))
     finally:
         rt.close()
+
+
+# ---- exp_cw and rcp2 (device_common.hpp): the exp() and 1 / x of the radiance and continuum kernels, KAT rows 10 and 11 ---------------
+def _ulps(got, args, fn):
+    """|got - fn(arg)| in ulps of the true value (mpmath, 50 digits); a true value below the smallest normal double is measured in
+    denormal spacings.  -> (errors, true values as floats)."""
+    import mpmath
+
+    err, true = np.zeros(len(args)), np.zeros(len(args))
+    with mpmath.workdps(50):
+        for i, (g, x) in enumerate(zip(got, args)):
+            t = fn(mpmath.mpf(float(x)))
+            e = max(int(mpmath.floor(mpmath.log(abs(t), 2))), -1022) - 52
+            err[i] = float(abs(mpmath.mpf(float(g)) - t) / mpmath.ldexp(1, e)) if np.isfinite(g) else np.inf
+            true[i] = float(t)
+    return err, true
+
+
+def exp_cw_arguments():
+    rng = np.random.default_rng(1010)
+    ln2 = np.log(2.0)
+    ties = []
+    for k in range(-1075, 1024):   # the rounding ties of the reduction n = rint(x / ln 2), +- 4 neighbouring doubles
+        x = (k + 0.5) * ln2
+        lo = x
+        for _ in range(4):
+            lo = np.nextafter(lo, -np.inf)
+        for _ in range(9):
+            ties.append(lo)
+            lo = np.nextafter(lo, np.inf)
+    small = 10.0 ** rng.uniform(-300.0, 0.0, 1000)
+    return np.concatenate([rng.uniform(-745.2, 709.78, 4000), small, -small, np.array(ties), [0.0, -0.0, -745.13, -745.2, 709.78]])
+
+
+@pytest.mark.gpu
+def test_device_exp_cw_within_two_ulp():
+    """exp_cw is documented at 1-2 ulp: 2 ulp of the true value over the whole range of finite results, 2 denormal spacings below
+    2.2e-308; exactly 0 from -745.2 down to -1e9, +inf from 709.79 to 1000, NaN for NaN."""
+    import mpmath
+
+    from monortm_amd import api
+
+    x = exp_cw_arguments()
+    x = x[(x >= -745.2) & (x <= 709.78)]
+    rng = np.random.default_rng(1011)
+    zero = np.concatenate([[-745.2, -746.0, -800.0, -1e9], -10.0 ** rng.uniform(np.log10(745.2), 9.0, 500)])
+    inf = np.concatenate([[709.79, 1000.0], rng.uniform(709.79, 1000.0, 200)])
+    args = np.zeros((len(x) + len(zero) + len(inf) + 1, 4))
+    args[:, 0] = np.concatenate([x, zero, inf, [np.nan]])
+    rt = api.MonoRTM("", 0.0, 0.0)
+    try:
+        got = rt.kat(10, args)[:, 0]
+    finally:
+        rt.close()
+    err, true = _ulps(got[:len(x)], x, mpmath.exp)
+    w = int(np.argmax(err))
+    print(f"\nexp_cw: worst {err.max():.3f} ulp at x = {x[w]!r} ({len(x)} arguments); worst for results below 2.2e-308: "
+          f"{err[true < 2.2250738585072014e-308].max():.3f} denormal spacings")
+    assert err.max() <= 2.0, f"exp_cw({x[w]!r}) = {got[w]!r}: {err.max():.3f} ulp from {true[w]!r}"
+    z, i = got[len(x):len(x) + len(zero)], got[len(x) + len(zero):-1]
+    assert np.all(z == 0) and not np.any(np.signbit(z)), "exp_cw below -745.2 is not exactly +0"
+    assert np.all(i == np.inf), "exp_cw above 709.79 is not +inf"
+    assert np.isnan(got[-1])
+
+
+@pytest.mark.gpu
+def test_device_rcp2_within_one_ulp():
+    """rcp2 (v_rcp_f64 and two Newton steps) is documented at 1 ulp: +-10^U(-300, 300), and 1 + 10^U(-16, 0), the range of the
+    radiance kernels' 1 + pade."""
+    import mpmath
+
+    from monortm_amd import api
+
+    rng = np.random.default_rng(1012)
+    big = 10.0 ** rng.uniform(-300.0, 300.0, 3000)
+    x = np.concatenate([big, -big, 1.0 + 10.0 ** rng.uniform(-16.0, 0.0, 3000), [1.0, 2.0, 3.0, 1.0 + 2.0 ** -52, 2.0 - 2.0 ** -52]])
+    args = np.zeros((len(x), 4))
+    args[:, 0] = x
+    rt = api.MonoRTM("", 0.0, 0.0)
+    try:
+        got = rt.kat(11, args)[:, 0]
+    finally:
+        rt.close()
+    err, true = _ulps(got, x, lambda v: 1 / v)
+    w = int(np.argmax(err))
+    print(f"\nrcp2: worst {err.max():.3f} ulp at x = {x[w]!r} ({len(x)} arguments)")
+    assert err.max() <= 1.0, f"rcp2({x[w]!r}) = {got[w]!r}: {err.max():.3f} ulp from {true[w]!r}"
+    assert np.all(got[-5:-2] == [1.0, 0.5, 1.0 / 3.0])
