@@ -117,7 +117,12 @@ int monortm_hip_kat(void *ctx, int which, int n, const double *args, const doubl
 /* Diagnostics: which = 0 -> number of monortm_hip_rtm calls on this context that found the optical depths O of the
  * preceding monortm_hip_modm call still resident on the device (the caller handed back exactly what MODM returned, as
  * PROGRAM MONORTM does at src/monortm.f90:567-574) and skipped the upload.  which = 1 -> the same count for monortm_hip_rtm_scan.
- * -1 for an unknown selector / NULL. */
+ * which = 2 .. 7 -> launches of the continuum / cloud / total kernel of MODM on this context by variant, one per MODM evaluation
+ * (a Jacobian call makes several): 2 finish_mw_kernel (last wavenumber < 820 cm-1 and an ABSRB grid of <= 1000 points), 3
+ * finish_kernel<HIGH> (last wavenumber > 1340 cm-1), 4 finish_kernel<PAR> (fewer than 16 x compute units (profile, layer) workgroups),
+ * 5 finish_kernel<Q4> (four layers per wave: ABSRB grid <= 64 points, <= 128 wavenumbers), 6 finish_kernel with 64 threads (ABSRB
+ * grid <= 256 points, <= 128 wavenumbers), 7 finish_kernel with 256 threads.  Counted on the host next to the launch; tests use them
+ * to know which variant served a call.  A multi-device context returns the sum over its devices.  -1 for an unknown selector / NULL. */
 long long monortm_hip_counter(void *ctx, int which);
 
 /* Physical line records (IFLG >= 0) held for molecule mol (1..39); mol = 0 -> all molecules.
@@ -311,6 +316,9 @@ int monortm_hip_profile(void *ctx, int enable);
  *   "lines_kernel" = "auto" | "wn" (the one kernel; the round-3 alternatives "state" / "p" were removed in round 5).
  *   "jac_dt" = "auto" | a finite double > 0 (K; MONORTM_JAC_DT), "jac_dlnw" = "auto" | a finite double in (0, 1) (MONORTM_JAC_DLNW):
  *       the half-steps of the Jacobian's central differences (monortm_hip_jacobian).
+ *   "finish" = "auto" | "generic": generic = finish_kernel forms the continuum, cloud and total optical depths also where
+ *       finish_mw_kernel would (last wavenumber < 820 cm-1): the A/B switch between the two; MONORTM_FINISH_GENERIC (set to anything)
+ *       makes generic the default at monortm_hip_init.
  * Values are parsed strictly (whole string, in range).  Unknown names / values: MONORTM_EARG. */
 int monortm_hip_set_option(void *ctx, const char *name, const char *value);
 int monortm_hip_kernel_time(void *ctx, int kernel, double *total_ms, long long *launches);

@@ -91,6 +91,10 @@ def _quantity(q) -> int:
     return int(q)
 
 
+# selectors 2 .. 7 of MonoRTM.counter(): launches of the continuum / cloud / total kernel by variant
+FINISH_VARIANTS = ("mw", "high", "par", "q4", "plain64", "plain256")
+FINISH_COUNTER0 = 2
+
 SCAN_FIELDS = ("rup", "rdn", "trtot", "rad", "tb", "tmr")   # output order of monortm_hip_rtm_scan
 
 
@@ -306,7 +310,9 @@ class MonoRTM:
         return self.rtm_scan(profiles, self.modm(profiles)[0], path, emiss, reflc)
 
     def counter(self, which: int = 0) -> int:
-        """monortm_hip_counter: 0 = rtm calls, 1 = rtm_scan calls that found O resident on the device."""
+        """monortm_hip_counter: 0 = rtm calls, 1 = rtm_scan calls that found O resident on the device; 2 .. 7 = launches of the
+        continuum / cloud / total kernel by variant (FINISH_VARIANTS: finish_mw_kernel, finish_kernel<HIGH>, <PAR>, <Q4>, plain with
+        64 threads, plain with 256), one per MODM evaluation."""
         return int(self.lib.monortm_hip_counter(self.ctx, which))
 
     def run(self, profiles: list[Profile]) -> list[Dump]:
@@ -401,7 +407,9 @@ class MonoRTM:
                                                   C.c_void_p(recv.data_ptr()) if recv is not None else None, root, C.c_void_p(stream)))
 
     def set_option(self, name: str, value) -> None:
-        """Measurement switches of the context (monortm_hip_set_option): nslice, fair, tile_waves, far_levels (lines_kernel = wn only)."""
+        """Measurement switches of the context (monortm_hip_set_option): nslice, fair, tile_waves, far_levels, lines_kernel = auto | wn |
+        ms, ms_items, jac_dt, jac_dlnw, and finish = auto | generic (generic: finish_kernel also below 820 cm-1, where finish_mw_kernel
+        serves by default; the environment variable MONORTM_FINISH_GENERIC makes it the default of a new context)."""
         self._chk(self.lib.monortm_hip_set_option(self.ctx, name.encode(), str(value).encode()))
 
     def kat(self, which: int, args: np.ndarray, tab: np.ndarray | None = None) -> np.ndarray:

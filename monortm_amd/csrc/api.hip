@@ -33,7 +33,7 @@ struct Ctx {
     // multi-device context (monortm_hip_init_multi): no device resources of its own, one full context per device
     std::vector<Ctx *> shards;
     // measurement switches (monortm_hip_set_option; the environment variables MONORTM_NSLICE / _FAIR /
-    // _TILE_WAVES give their defaults ONCE, when the context is created - nothing on the launch path calls getenv)
+    // _TILE_WAVES / _FINISH_GENERIC give their defaults ONCE, when the context is created - nothing on the launch path calls getenv)
     struct Opt {
         int nslice = 0;           // 0 = chosen per call
         int fair = -1;            // -1 = chosen per call, 0 / 1 wave priorities off / on
@@ -42,6 +42,7 @@ struct Ctx {
         int lines_ms = -1;        // -1 = chosen per call; 0 = never lines_ms_kernel; 1 = whenever its layout fits (tests, measurements)
         int ms_ablate = 0;        // timing experiments: lines_ms_kernel without its later stages (wrong results)
         int ms_items = 0;         // 0 = chosen per call; 64 / 128 / 192 (state, line) items per chunk of lines_ms_kernel
+        int finish_generic = 0;   // 1 = finish_kernel also where finish_mw_kernel would serve (A/B measurements, tests of the two against each other)
         double jac_dt = MONORTM_JAC_DT, jac_dlnw = MONORTM_JAC_DLNW;   // half-steps of the Jacobian's central differences
     } opt;
     void *comm = nullptr;     // RCCL communicator of a multi-process job (monortm_hip_comm_init), one rank per context
@@ -100,6 +101,9 @@ struct Ctx {
     } lastO;
     long long o_reused = 0;  // calls of monortm_hip_rtm that found O resident
     long long o_reused_scan = 0;  // calls of monortm_hip_rtm_scan that did
+    // launches of the continuum / cloud / total kernel by variant (monortm_hip_counter 2 .. 7): finish_mw_kernel, finish_kernel<HIGH>,
+    // <PAR>, <Q4>, plain with 64 threads, plain with 256
+    long long finish_launches[6] = {0, 0, 0, 0, 0, 0};
     // MONORTM_HOST_TIMING=1: wall time of the host-buffer calls by phase (pack, enqueue, wait, unpack), printed at finalize
     bool host_timing = false;
     double ht[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};   // modm, rtm, rtm_scan
@@ -184,6 +188,8 @@ int set_option(Ctx *c, const char *name, const char *value) {
 #ifdef MONORTM_EXPERIMENT   // stage ablations of lines_ms_kernel: timing only, wrong results - experiment builds alone know the option
     else if (n == "ms_ablate" && isint && iv >= 0 && iv <= 9) c->opt.ms_ablate = (int)iv;
 #endif
+    // continuum / cloud / total kernel: auto = finish_mw_kernel below 820 cm-1, finish_kernel elsewhere; generic = finish_kernel always
+    else if (n == "finish" && (autov || v == "generic")) c->opt.finish_generic = autov ? 0 : 1;
     else if (n == "ms_items" && (autov || (isint && (iv == 64 || iv == 128 || iv == 192 || iv == 256)))) c->opt.ms_items = autov ? 0 : (int)iv;
     // half-steps of the Jacobian: a finite positive double (jac_dlnw below 1: WKL (1 - eps) stays positive)
     else if ((n == "jac_dt" || n == "jac_dlnw") && (autov || (isdbl && std::isfinite(dv) && dv > 0. && (n == "jac_dt" || dv < 1.)))) {
@@ -809,6 +815,7 @@ int monortm_hip_init(const char *tape3_path, double v1, double v2, int icp, int 
         return failed(MONORTM_EHIP);
     }
     if (const char *e = getenv("MONORTM_HOST_TIMING")) c->host_timing = e[0] == '1';
+    if (getenv("MONORTM_FINISH_GENERIC")) c->opt.finish_generic = 1;  // (set, whatever its value: the default of option "finish")
     for (const char *k : {"lines_kernel", "nslice", "fair", "tile_waves", "far_levels", "ms_items",
 #ifdef MONORTM_EXPERIMENT
                           "ms_ablate",
@@ -1083,6 +1090,7 @@ long long monortm_hip_counter(void *ctx, int which) {
     }
     if (which == 0) return c->o_reused;
     if (which == 1) return c->o_reused_scan;
+    if (which >= 2 && which <= 7) return c->finish_launches[which - 2];
     return -1;
 }
 
@@ -1403,9 +1411,9 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
     // configs[4] whole 0.992 -> 0.948 ms - so every one-wave tile up to 8 rounds)
     a.fair = ((nw == 1 && wpl == 1 && c->real_kind == 8) || nblocks * nslice * nw <= ((nw == 1) ? 8 : 4) * 16 * cus) ? 1 : 0;
     if (c->opt.fair >= 0) a.fair = c->opt.fair;  // measurements only
-    static const bool mw_off = getenv("MONORTM_FINISH_GENERIC") != nullptr;  // A/B switch for measurements
     // microwave to far infrared (last wavenumber below 820 cm-1: no O3 / O2 / Rayleigh term anywhere): the fused finish kernel
-    const bool mw = vends[1] < 820.0 && NPTABS <= 1000 && !mw_off;
+    // (option "finish" = generic: an A/B switch for measurements and tests)
+    const bool mw = vends[1] < 820.0 && NPTABS <= 1000 && !c->opt.finish_generic;
 #ifdef LINES_TIMING
     if (mw) {
 #else
@@ -1582,8 +1590,11 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
             c->err = std::string("launch_finish_mw: ") + (c->mw_cache.why ? c->mw_cache.why : hipGetErrorString(e));
             return c->mw_cache.why ? MONORTM_EUNSUPPORTED : MONORTM_EHIP;
         }
+        c->finish_launches[0]++;
+    } else {
+        HIPCHK(c, launch_finish(a, c->tables, V1ABS, V2ABS, NPTABS, csize, high, par, fin_threads, lds, lds_sets, s));
+        c->finish_launches[high ? 1 : (par ? 2 : (quad ? 3 : (fin_threads == 64 ? 4 : 5)))]++;
     }
-    else HIPCHK(c, launch_finish(a, c->tables, V1ABS, V2ABS, NPTABS, csize, high, par, fin_threads, lds, lds_sets, s));
     prof_end(c, s, ev);
     HIPCHK(c, hipGetLastError());
     return MONORTM_OK;
