@@ -295,6 +295,61 @@ int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, do
                              monortm_real *K_T, monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW,
                              monortm_real *K_O, monortm_real *K_SFC, const double *wn_ends, void *stream);
 
+/* ---- Jacobians of path scans: K for npath paths per profile from ONE set of optical depths and ONE set of perturbed MODM states
+ * (no reference counterpart; the radiance recurrence differentiated is src/RTMmono.f90:13-221).  DESIGN.md section 3.8.
+ * path, sfc_per_path, emiss, reflc as in monortm_hip_rtm_scan; quantity and the meaning of K as in monortm_hip_rtm_jac.  Along path j
+ * the optical depth of layer k is tau_jk = path_jk O_k; with ko_jk = dq_j / dtau_jk:
+ *   RAD, TB [nprof][npath][nwn]
+ *   K_O    [nprof][npath][nlay_max][nwn]       path_jk ko_jk = dq_j / dO_k of the vertical O (may be NULL)
+ *   K_PATH [nprof][npath][nlay_max][nwn]       O_k ko_jk = dq_j / dpath_jk, to chain with d path / d angle (may be NULL)
+ *   K_T    [nprof][npath][nlay_max][nwn]       the Planck term; monortm_hip_scan_jacobian adds K_O dO_k/dT_k
+ *   K_TZ   [nprof][npath][nlay_max + 1][nwn],  K_SFC [nprof][npath][3][nwn]
+ *   K_W    [nprof][npath][nlay_max][njac][nwn] K_O dO_k / d ln WKL_k of the batch's own (vertical) amounts
+ *   K_CLW  [nprof][npath][nlay_max][nwn]       K_O ODCLW_TKC(wn, T_k, 1): with respect to the batch's own (vertical) CLW_k
+ * Entries of layers >= nlay[p] and levels > nlay[p] are 0; tmpsfc is input only.  1 <= npath <= 16384, nlay_max <= 603.
+ *
+ * RTM adjoint only, given O: real_kind 8 and 4.  Host buffers: nlay and the factors of the whole call are checked before anything is
+ * staged on any device (MONORTM_EARG, nothing is launched); a multi-device context shards the profiles like monortm_hip_rtm_scan. */
+int monortm_hip_rtm_scan_jac(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max,
+                             const int *irt, int quantity, const monortm_real *T, const monortm_real *TZ, const monortm_real *O,
+                             const monortm_real *path, const monortm_real *tmpsfc, int sfc_per_path, const monortm_real *emiss,
+                             const monortm_real *reflc, monortm_real *RAD, monortm_real *TB, monortm_real *K_O,
+                             monortm_real *K_PATH, monortm_real *K_T, monortm_real *K_TZ, monortm_real *K_SFC);
+/* The same on device pointers, asynchronous on `stream`; one-device context.  Allocates nothing.  A bad factor of an active layer
+ * surfaces through monortm_hip_check (MONORTM_EARG). */
+int monortm_hip_rtm_scan_jac_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max,
+                                 const int *irt, int quantity, const monortm_real *T, const monortm_real *TZ,
+                                 const monortm_real *O, const monortm_real *path, const monortm_real *tmpsfc, int sfc_per_path,
+                                 const monortm_real *emiss, const monortm_real *reflc, monortm_real *RAD, monortm_real *TB,
+                                 monortm_real *K_O, monortm_real *K_PATH, monortm_real *K_T, monortm_real *K_TZ,
+                                 monortm_real *K_SFC, void *stream);
+
+/* MODM + RTM with Jacobians along npath paths: the 3 + 2 njac MODM passes of monortm_hip_jacobian ONCE (their differences do not depend
+ * on the path), then one adjoint launch for all paths.  O returns the vertical optical depths.  real_kind 8 only
+ * (MONORTM_EUNSUPPORTED otherwise); jac_mol, the half-steps and the errors as monortm_hip_jacobian, the factors as above; no
+ * cross-section molecules. */
+int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
+                              int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
+                              const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac, double sclcpl,
+                              double sclhw, double y0res, int ibrd, const int *irt, const monortm_real *TZ,
+                              const monortm_real *tmpsfc, const monortm_real *emiss, const monortm_real *reflc, int quantity,
+                              int njac, const int *jac_mol, int npath, const monortm_real *path, int sfc_per_path,
+                              monortm_real *O, monortm_real *RAD, monortm_real *TB, monortm_real *K_T, monortm_real *K_TZ,
+                              monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_O, monortm_real *K_PATH,
+                              monortm_real *K_SFC);
+/* The same on device pointers, asynchronous on `stream`; one-device context.  wn_ends as for monortm_hip_modm_dev.  Device-side
+ * failures (temperature range, bad factors) surface through monortm_hip_check.  After one call, a second of the same shapes
+ * allocates nothing (graph capture). */
+int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
+                                  int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
+                                  const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac /*host*/,
+                                  double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const monortm_real *TZ,
+                                  const monortm_real *tmpsfc, const monortm_real *emiss, const monortm_real *reflc,
+                                  int quantity, int njac, const int *jac_mol /*host*/, int npath, const monortm_real *path,
+                                  int sfc_per_path, monortm_real *O, monortm_real *RAD, monortm_real *TB, monortm_real *K_T,
+                                  monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_O,
+                                  monortm_real *K_PATH, monortm_real *K_SFC, const double *wn_ends, void *stream);
+
 /* Device-side failure flags raised by the kernels of earlier *_dev calls (temperature range, SD-Voigt
  * sign): synchronises `stream`, returns MONORTM_OK or the first error and clears the flags. */
 int monortm_hip_check(void *ctx, void *stream);

@@ -70,6 +70,16 @@ SYMBOLS = {
     "monortm_hip_jacobian_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                            C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]
                                  + [_vp] * 11),
+    "monortm_hip_rtm_scan_jac": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int]
+                                 + [_vp] * 9),
+    "monortm_hip_rtm_scan_jac_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                               C.c_int] + [_vp] * 10),
+    "monortm_hip_scan_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
+                                            C.c_int, _vp, C.c_int] + [_vp] * 10),
+    "monortm_hip_scan_jacobian_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
+                                                C.c_int, _vp, C.c_int] + [_vp] * 12),
     "monortm_hip_check": (C.c_int, [_vp, _vp]),
     "monortm_hip_profile": (C.c_int, [_vp, C.c_int]),
     "monortm_hip_kernel_time": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_longlong)]),
@@ -82,6 +92,8 @@ _LIB = None
 JAC_DT = 1e-2
 JAC_DLNW = 1e-4
 JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_sfc")
+SCAN_JAC_RTM_FIELDS = ("rad", "tb", "k_o", "k_path", "k_t", "k_tz", "k_sfc")                 # output order of monortm_hip_rtm_scan_jac
+SCAN_JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_path", "k_sfc")   # ... of monortm_hip_scan_jacobian
 
 
 def _quantity(q) -> int:
@@ -388,6 +400,68 @@ class MonoRTM:
                                                 *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS]))
         return out
 
+    # ---- Jacobians of path scans (monortm_hip_rtm_scan_jac / monortm_hip_scan_jacobian) ----------------------
+    def _scan_sfc(self, em, rf, emiss, reflc, nprof, npath, nwn):
+        em = em if emiss is None else _np(emiss, self.dtype)
+        rf = rf if reflc is None else _np(reflc, self.dtype)
+        if em.shape != rf.shape or em.shape not in ((nprof, nwn), (nprof, npath, nwn)):
+            raise ValueError(f"emiss / reflc must both be [{nprof}, {nwn}] or [{nprof}, {npath}, {nwn}]")
+        return em, rf
+
+    def rtm_scan_jacobian(self, profiles: list[Profile], O: np.ndarray, path, quantity="tb", emiss=None, reflc=None) -> dict:
+        """The adjoint of RTM along npath paths per profile from one O [nprof, nlay_max, nwn]; path, emiss, reflc as rtm_scan,
+        quantity as rtm_jacobian.  Dict of rad, tb [nprof, npath, nwn], k_o (= factor x dq/dtau: with respect to the vertical O),
+        k_path (= O x dq/dtau: with respect to the factor), k_t (Planck term only) [nprof, npath, nlay_max, nwn],
+        k_tz [nprof, npath, nlay_max + 1, nwn], k_sfc [nprof, npath, 3, nwn]."""
+        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
+        dt = self.dtype
+        f = self._path(path, nprof, lm)
+        npath = f.shape[1]
+        em, rf = self._scan_sfc(em, rf, emiss, reflc, nprof, npath, nwn)
+        O = _np(O, dt)
+        if O.shape != (nprof, lm, nwn):
+            raise ValueError(f"O must be [{nprof}, {lm}, {nwn}], got {O.shape}")
+        z = lambda *s: np.zeros((nprof, npath) + s, dt)  # noqa: E731
+        out = dict(rad=z(nwn), tb=z(nwn), k_o=z(lm, nwn), k_path=z(lm, nwn), k_t=z(lm, nwn), k_tz=z(lm + 1, nwn), k_sfc=z(3, nwn))
+        wn = _np(profiles[0].wn)
+        self._chk(self.lib.monortm_hip_rtm_scan_jac(self.ctx, nprof, npath, nwn, _ptr(wn), _ptr(nlay), lm, _ptr(irt), _quantity(quantity),
+                                                    _ptr(T), _ptr(TZ), _ptr(O), _ptr(f), _ptr(ts), int(em.ndim == 3), _ptr(em), _ptr(rf),
+                                                    *[_ptr(out[k]) for k in SCAN_JAC_RTM_FIELDS]))
+        return out
+
+    def scan_jacobian(self, profiles: list[Profile], path, mols=(1,), quantity="tb", emiss=None, reflc=None) -> dict:
+        """MODM (the base and the perturbed states of jacobian(), ONCE) + RTM with Jacobians along npath paths per profile (real_kind
+        8): the fields of rtm_scan_jacobian with the optical-depth term in k_t, plus o [nprof, nlay_max, nwn] (the vertical optical
+        depths), k_w [nprof, npath, nlay_max, len(mols), nwn] and k_clw [nprof, npath, nlay_max, nwn] - derivatives with respect to
+        the batch's own (vertical) ln WKL and CLW."""
+        p0 = profiles[0]
+        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
+        nmol, dt = p0.nmol, self.dtype
+        f = self._path(path, nprof, lm)
+        npath = f.shape[1]
+        em, rf = self._scan_sfc(em, rf, emiss, reflc, nprof, npath, nwn)
+
+        def pack(get, width=None):
+            out = np.zeros((nprof, lm) if width is None else (nprof, lm, width), dt)
+            for i, p in enumerate(profiles):
+                out[i, : p.nlay] = get(p)
+            return out
+
+        P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
+        WKL = pack(lambda p: p.wkl, nmol)
+        jm = np.ascontiguousarray(np.asarray(mols, np.int32).reshape(-1))
+        nj = len(jm)
+        z = lambda *s: np.zeros((nprof, npath) + s, dt)  # noqa: E731
+        out = dict(o=np.zeros((nprof, lm, nwn), dt), rad=z(nwn), tb=z(nwn), k_t=z(lm, nwn), k_tz=z(lm + 1, nwn), k_w=z(lm, nj, nwn),
+                   k_clw=z(lm, nwn), k_o=z(lm, nwn), k_path=z(lm, nwn), k_sfc=z(3, nwn))
+        wn, fac = _np(p0.wn), _np(p0.cntnm)
+        self._chk(self.lib.monortm_hip_scan_jacobian(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T),
+                                                     _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd,
+                                                     _ptr(irt), _ptr(TZ), _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj,
+                                                     _ptr(jm) if nj else None, npath, _ptr(f), int(em.ndim == 3),
+                                                     *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS]))
+        return out
+
     # ---- the C-ABI gather of a profile-sharded job (RCCL; what a C / Fortran caller uses instead of torch.distributed) ------
     @staticmethod
     def comm_unique_id() -> bytes:
@@ -580,6 +654,44 @@ class DeviceBatch:
                                              d(self.T), d(self.TZ), d(self.O), d(fd), d(self.tmpsfc), 0, d(self.emiss), d(self.reflc),
                                              d(rup), d(rdn), d(trtot), d(rad), d(tb), d(tmr), sp))
         return blk
+
+    # ---- Jacobians of path scans on the resident batch (monortm_hip_scan_jacobian_dev) ----------------------------------------------
+    def scan_jacobian(self, path, mols=(1,), quantity="tb", stream=None) -> dict:
+        """K along npath paths per profile on the current (or the given) stream, asynchronously: a dict of torch tensors with the
+        fields and shapes of MonoRTM.scan_jacobian.  The outputs and the device copy of the factors are allocated at the first call
+        for (npath, mols, quantity) and overwritten by every later one, so that a graph capture of the call (after one warm call, with
+        the factors in a tensor on the batch's device) replays into the same tensors.  path as DeviceBatch.scan; TMPSFC is the
+        profiles' own (input only).  Bad factors surface through check()."""
+        t = self.torch
+        real = t.float32 if self.rt.real_kind == 4 else t.float64  # dtype of the REAL arrays
+        f = t.as_tensor(path)
+        if f.dim() == 2:
+            f = f.unsqueeze(0).expand(self.nprof, -1, -1)
+        if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
+            raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
+        npath = int(f.shape[1])
+        key = (npath, tuple(int(m) for m in mols), _quantity(quantity))
+        cache = self.__dict__.setdefault("_scan_jac", {})
+        if key not in cache:
+            n, lm, nw, nj = self.nprof, self.lm, self.nwn, len(key[1])
+            z = lambda *s: t.zeros(*s, dtype=real, device=self.dev)  # noqa: E731
+            zp = lambda *s: z(n, npath, *s)  # noqa: E731
+            cache[key] = (dict(o=z(n, lm, nw), rad=zp(nw), tb=zp(nw), k_t=zp(lm, nw), k_tz=zp(lm + 1, nw), k_w=zp(lm, nj, nw), k_clw=zp(lm, nw),
+                               k_o=zp(lm, nw), k_path=zp(lm, nw), k_sfc=zp(3, nw)), np.ascontiguousarray(key[1], np.int32), z(n, npath, lm))
+        out, jm, fd = cache[key]
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        with t.cuda.stream(s):
+            fd.copy_(f, non_blocking=True)
+        p0, lib, rt = self.p0, self.rt.lib, self.rt
+        d = lambda x: _vp(x.data_ptr())  # noqa: E731
+        nj = len(jm)
+        rt._chk(lib.monortm_hip_scan_jacobian_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol,
+                                                  d(self.P), d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl,
+                                                  p0.sclhw, p0.y0res, p0.ibrd, d(self.irt), d(self.TZ), d(self.tmpsfc0), d(self.emiss),
+                                                  d(self.reflc), key[2], nj, _ptr(jm) if nj else None, npath, d(fd), 0,
+                                                  *[d(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS],
+                                                  _ptr(self.wn_ends), _vp(s.cuda_stream)))
+        return out
 
     # ---- HIP graph: the three launches of a step recorded once, replayed with a single call ------------------
     def capture(self):

@@ -336,7 +336,7 @@ namespace {
 int decode_flag(Ctx *c, int flag, hipStream_t s) {
     if (!flag) return MONORTM_OK;
     HIPCHK(c, hipMemsetAsync(c->errflag, 0, sizeof(int), s));
-    if (flag & ERRBIT_ARG) { c->err = "device arguments: nlay[p] outside 1..nlay_max, wavenumbers not ascending or not the grid dvset promises, or a negative / non-finite path factor (monortm_hip_rtm_scan_dev)"; return MONORTM_EARG; }
+    if (flag & ERRBIT_ARG) { c->err = "device arguments: nlay[p] outside 1..nlay_max, wavenumbers not ascending or not the grid dvset promises, or a negative / non-finite path factor (monortm_hip_rtm_scan_dev, monortm_hip_rtm_scan_jac_dev, monortm_hip_scan_jacobian_dev)"; return MONORTM_EARG; }
     if (flag & ERRBIT_TEMP) { c->err = "TIPS: layer temperature outside 70-3000 K / partition sum <= 0 (reference STOP, tips_2003.f90:277)"; return MONORTM_ETEMP; }
     c->err = "SDVOIGT: REAL(v) < 0 (reference STOP, modm.f90:1062)";
     return MONORTM_ESDV;
@@ -588,6 +588,23 @@ int jac_check_mol(Ctx *c, int nmol, int njac, const int *jac_mol, const void *K_
     return MONORTM_OK;
 }
 
+// what the MODM passes of a full Jacobian call refuse, on host arrays: wavenumbers that do not ascend, and T +- jac_dt outside the TIPS
+// range (the MODM kernels would flag the latter as well)
+int jac_check_states(Ctx *c, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const void *T) {
+    for (int i = 1; i < nwn; i++)
+        if (!(wn[i] >= wn[i - 1])) { c->err = "wavenumbers must be ascending (the reference takes v1 = wn(1), v2 = wn(nwn), modm.f90:180-181)"; return MONORTM_EARG; }
+    const double h = c->opt.jac_dt, *Tp = static_cast<const double *>(T);
+    for (int p = 0; p < nprof; p++)
+        for (int k = 0; k < nlay[p]; k++) {
+            const double t = Tp[(size_t)p * nlay_max + k];
+            if (!(t - h >= 70. && t + h <= 3000.)) {
+                c->err = "layer temperature +- jac_dt outside 70-3000 K (TIPS, tips_2003.f90:277): profile " + std::to_string(p) + " layer " + std::to_string(k);
+                return MONORTM_ETEMP;
+            }
+        }
+    return MONORTM_OK;
+}
+
 static int rtm_jac_host(Ctx *c, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
                         const void *T, const void *TZ, const void *O, const void *tmpsfc, const void *emiss, const void *reflc,
                         void *RAD, void *TB, void *K_O, void *K_T, void *K_TZ, void *K_SFC, std::function<int()> *defer) {
@@ -636,19 +653,7 @@ static int jac_host(Ctx *c, int nprof, int nwn, const double *wn, double dvset, 
     if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
     if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
     if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
-    for (int i = 1; i < nwn; i++)
-        if (!(wn[i] >= wn[i - 1])) { c->err = "wavenumbers must be ascending (the reference takes v1 = wn(1), v2 = wn(nwn), modm.f90:180-181)"; return MONORTM_EARG; }
-    {   // the perturbed states' temperatures must stay inside the TIPS range (the MODM kernels would flag them as well)
-        const double h = c->opt.jac_dt, *Tp = static_cast<const double *>(T);
-        for (int p = 0; p < nprof; p++)
-            for (int k = 0; k < nlay[p]; k++) {
-                const double t = Tp[(size_t)p * nlay_max + k];
-                if (!(t - h >= 70. && t + h <= 3000.)) {
-                    c->err = "layer temperature +- jac_dt outside 70-3000 K (TIPS, tips_2003.f90:277): profile " + std::to_string(p) + " layer " + std::to_string(k);
-                    return MONORTM_ETEMP;
-                }
-            }
-    }
+    if (int rc = jac_check_states(c, nprof, nwn, wn, nlay, nlay_max, T)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn;
     const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_w = npl * nmol * d,
@@ -685,6 +690,170 @@ static int jac_host(Ctx *c, int nprof, int nwn, const double *wn, double dvset, 
         memcpy(K_TZ, ho + o_ktz, b_tzw); memcpy(K_CLW, ho + o_kc, b_o); memcpy(K_SFC, ho + o_ks, 3 * b_pw);
         if (njac) memcpy(K_W, ho + o_kw, b_kw);
         if (K_O) memcpy(K_O, ho + o_ko, b_o);
+        return MONORTM_OK;
+    };
+    if (defer) { *defer = complete; return MONORTM_OK; }
+    return complete();
+}
+
+// The MODM part of a Jacobian call (monortm_hip_jacobian_dev, monortm_hip_scan_jacobian_dev): jac_perturb_kernel, then MODM of the base
+// and the 2 (1 + njac) perturbed states.  Small batches (single-profile retrievals underfill the GPU) go through ONE extended MODM launch
+// of all states; larger ones through one launch of nprof profiles per state, of the shapes of a plain MODM call - so that alternating
+// Jacobian and plain calls never resizes the MODM workspaces (an extended launch is only taken while its line-physics records stay below
+// the 64 MB under which MODM keeps them).  O gets the base state; *xO_out: the states' optical depths in the context's workspace (state k
+// at xO + k st, k >= 1), *st_out: elements of one state.
+static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
+                      const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
+                      double y0res, int ibrd, int njac, const int *jac_mol, void *O, const double *wn_ends, hipStream_t s, double **xO_out,
+                      size_t *st_out) {
+    double vends[2];
+    if (wn_ends) { vends[0] = wn_ends[0]; vends[1] = wn_ends[1]; }
+    else {   // once here, not in every MODM call below
+        HIPCHK(c, hipMemcpyAsync(&vends[0], wn, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&vends[1], wn + nwn - 1, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    const int nstate = 3 + 2 * njac;
+    const size_t npl = (size_t)nprof * nlay_max, st = npl * nwn;
+    const bool ext = (long long)nstate * nprof <= 64 && (size_t)nstate * npl * c->host.size() * 48 <= (64u << 20);
+    const size_t nj = ext ? nstate : 1;   // states whose unused MODM outputs are held at once
+    Arena ws;
+    const size_t w_P = ws.add(nstate * npl * 8), w_T = ws.add(nstate * npl * 8), w_C = ws.add(nstate * npl * 8), w_B = ws.add(nstate * npl * 8),
+                 w_W = ws.add(nstate * npl * nmol * 8), w_nl = ws.add(nstate * (size_t)nprof * sizeof(int)), w_O = ws.add(nstate * st * 8),
+                 w_OM = ws.add(nj * st * nmol * 8), w_OC = ws.add(nj * st * MONORTM_NCONT * 8), w_OL = ws.add(nj * st * 8);
+    if (ws.size > c->jac_ws_bytes) {
+        if (c->jac_ws) HIPCHK(c, hipFree(c->jac_ws));
+        c->jac_ws = nullptr;
+        c->jac_ws_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->jac_ws, ws.size));
+        c->jac_ws_bytes = ws.size;
+    }
+    char *wb = static_cast<char *>(c->jac_ws);
+    double *xO = reinterpret_cast<double *>(wb + w_O);
+    *xO_out = xO;
+    *st_out = st;
+    JacPerturbArgs pa{};
+    pa.nstate = nstate; pa.nprof = nprof; pa.nlay_max = nlay_max; pa.nmol = nmol; pa.dt = c->opt.jac_dt; pa.dlnw = c->opt.jac_dlnw;
+    for (int i = 0; i < njac; i++) pa.jac_mol[i] = jac_mol[i];
+    pa.P = static_cast<const double *>(P); pa.T = static_cast<const double *>(T); pa.CLW = static_cast<const double *>(CLW);
+    pa.WKL = static_cast<const double *>(WKL); pa.WBRODL = static_cast<const double *>(WBRODL); pa.nlay = nlay;
+    pa.xP = reinterpret_cast<double *>(wb + w_P); pa.xT = reinterpret_cast<double *>(wb + w_T); pa.xCLW = reinterpret_cast<double *>(wb + w_C);
+    pa.xWBRODL = reinterpret_cast<double *>(wb + w_B); pa.xWKL = reinterpret_cast<double *>(wb + w_W); pa.xnlay = reinterpret_cast<int *>(wb + w_nl);
+    launch_jac_perturb(pa, s);
+    HIPCHK(c, hipGetLastError());
+    auto modm = [&](int n, int s0, void *Oout, int slot) {   // MODM of n profiles of the state arrays from state s0 on
+        const size_t l0 = (size_t)s0 * npl;
+        return monortm_hip_modm_xs_dev(c, n, nwn, wn, dvset, pa.xnlay + (size_t)s0 * nprof, nlay_max, nmol, pa.xP + l0, pa.xT + l0, pa.xCLW + l0,
+                                       pa.xWKL + l0 * nmol, pa.xWBRODL + l0, cntnm_fac, sclcpl, sclhw, y0res, ibrd, 0, nullptr, nullptr, Oout,
+                                       wb + w_OM + slot * st * nmol * 8, wb + w_OC + slot * st * MONORTM_NCONT * 8, wb + w_OL + slot * st * 8,
+                                       vends, s);
+    };
+    if (ext) {
+        if (int rc = modm(nstate * nprof, 0, xO, 0)) return rc;
+        HIPCHK(c, hipMemcpyAsync(O, xO, st * 8, hipMemcpyDeviceToDevice, s));
+    } else {
+        // the base state straight from the caller's arrays, into the caller's O: what monortm_hip_modm_dev returns for them
+        if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw,
+                                             y0res, ibrd, 0, nullptr, nullptr, O, wb + w_OM, wb + w_OC, wb + w_OL, vends, s))
+            return rc;
+        for (int k = 1; k < nstate; k++)
+            if (int rc = modm(nprof, k, xO + k * st, 0)) return rc;
+    }
+    return MONORTM_OK;
+}
+
+// ---- Jacobians of path scans on host buffers: the staging slots of the Jacobian entries (8-11).  The arguments
+// are those the entry points have checked for the whole call (scan_check_args, scan_check_path, the quantity).
+static int rtm_scan_jac_host(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                             int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path,
+                             const void *emiss, const void *reflc, void *RAD, void *TB, void *K_O, void *K_PATH, void *K_T, void *K_TZ,
+                             void *K_SFC, std::function<int()> *defer) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn, ppw = pw * npath;
+    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_tz = (size_t)nprof * (nlay_max + 1) * d,
+                 b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d, b_sfc = (sfc_per_path ? ppw : pw) * d, b_q = ppw * d,
+                 b_k = b_o * npath, b_kz = b_tz * npath * nwn;
+    Arena in, out;
+    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_T = in.add(b_l), i_TZ = in.add(b_tz), i_O = in.add(b_o),
+                 i_f = in.add(b_f), i_ts = in.add(b_p), i_em = in.add(b_sfc), i_rf = in.add(b_sfc);
+    const size_t o_rad = out.add(b_q), o_tb = out.add(b_q), o_ko = K_O ? out.add(b_k) : 0, o_kp = K_PATH ? out.add(b_k) : 0, o_kt = out.add(b_k),
+                 o_ktz = out.add(b_kz), o_ks = out.add(3 * b_q);
+    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
+    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
+    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
+    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
+    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
+    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
+    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_T, T, b_l);
+    memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_O, O, b_o); memcpy(h + i_f, path, b_f); memcpy(h + i_ts, tmpsfc, b_p);
+    memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
+    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
+    int rc = monortm_hip_rtm_scan_jac_dev(c, nprof, npath, nwn, (double *)(dv + i_wn), (int *)(dv + i_nl), nlay_max, (int *)(dv + i_irt), quantity,
+                                          dv + i_T, dv + i_TZ, dv + i_O, dv + i_f, dv + i_ts, sfc_per_path, dv + i_em, dv + i_rf, dz + o_rad,
+                                          dz + o_tb, K_O ? dz + o_ko : nullptr, K_PATH ? dz + o_kp : nullptr, dz + o_kt, dz + o_ktz, dz + o_ks,
+                                          c->hs);
+    if (rc) return rc;
+    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs));
+    auto complete = [=]() mutable -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->hs));
+        const char *ho = static_cast<const char *>(hout);
+        memcpy(RAD, ho + o_rad, b_q); memcpy(TB, ho + o_tb, b_q); memcpy(K_T, ho + o_kt, b_k); memcpy(K_TZ, ho + o_ktz, b_kz);
+        memcpy(K_SFC, ho + o_ks, 3 * b_q);
+        if (K_O) memcpy(K_O, ho + o_ko, b_k);
+        if (K_PATH) memcpy(K_PATH, ho + o_kp, b_k);
+        return MONORTM_OK;
+    };
+    if (defer) { *defer = complete; return MONORTM_OK; }
+    return complete();
+}
+
+static int scan_jac_host(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
+                         const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl,
+                         double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc, const void *emiss,
+                         const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path, int sfc_per_path, void *O,
+                         void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_PATH, void *K_SFC,
+                         std::function<int()> *defer) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npl = (size_t)nprof * nlay_max, d = 8, pw = (size_t)nprof * nwn, ppw = pw * npath;
+    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_w = npl * nmol * d,
+                 b_tz = (size_t)nprof * (nlay_max + 1) * d, b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d,
+                 b_sfc = (sfc_per_path ? ppw : pw) * d, b_q = ppw * d, b_k = b_o * npath, b_kz = b_tz * npath * nwn, b_kw = b_k * njac;
+    Arena in, out;
+    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_P = in.add(b_l), i_T = in.add(b_l), i_C = in.add(b_l),
+                 i_W = in.add(b_w), i_B = in.add(b_l), i_TZ = in.add(b_tz), i_f = in.add(b_f), i_ts = in.add(b_p), i_em = in.add(b_sfc),
+                 i_rf = in.add(b_sfc);
+    const size_t o_O = out.add(b_o), o_rad = out.add(b_q), o_tb = out.add(b_q), o_kt = out.add(b_k), o_ktz = out.add(b_kz),
+                 o_kw = out.add(b_kw), o_kc = out.add(b_k), o_ko = K_O ? out.add(b_k) : 0, o_kp = K_PATH ? out.add(b_k) : 0,
+                 o_ks = out.add(3 * b_q);
+    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
+    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
+    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
+    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
+    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
+    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
+    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_P, P, b_l); memcpy(h + i_T, T, b_l);
+    memcpy(h + i_C, CLW, b_l); memcpy(h + i_W, WKL, b_w); memcpy(h + i_B, WBRODL, b_l); memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_f, path, b_f);
+    memcpy(h + i_ts, tmpsfc, b_p); memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
+    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
+    const double ends[2] = {wn[0], wn[nwn - 1]};
+    int rc = monortm_hip_scan_jacobian_dev(c, nprof, nwn, (double *)(dv + i_wn), dvset, (int *)(dv + i_nl), nlay_max, nmol, dv + i_P, dv + i_T,
+                                           dv + i_C, dv + i_W, dv + i_B, cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)(dv + i_irt), dv + i_TZ,
+                                           dv + i_ts, dv + i_em, dv + i_rf, quantity, njac, jac_mol, npath, dv + i_f, sfc_per_path, dz + o_O,
+                                           dz + o_rad, dz + o_tb, dz + o_kt, dz + o_ktz, njac ? dz + o_kw : nullptr, dz + o_kc,
+                                           K_O ? dz + o_ko : nullptr, K_PATH ? dz + o_kp : nullptr, dz + o_ks, ends, c->hs);
+    if (rc) return rc;
+    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs, c->errflag, c->errflag_host));
+    auto complete = [=]() mutable -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->hs));
+        if (int rcf = decode_flag(c, *c->errflag_host, c->hs)) return rcf;
+        const char *ho = static_cast<const char *>(hout);
+        memcpy(O, ho + o_O, b_o); memcpy(RAD, ho + o_rad, b_q); memcpy(TB, ho + o_tb, b_q); memcpy(K_T, ho + o_kt, b_k);
+        memcpy(K_TZ, ho + o_ktz, b_kz); memcpy(K_CLW, ho + o_kc, b_k); memcpy(K_SFC, ho + o_ks, 3 * b_q);
+        if (njac) memcpy(K_W, ho + o_kw, b_kw);
+        if (K_O) memcpy(K_O, ho + o_ko, b_k);
+        if (K_PATH) memcpy(K_PATH, ho + o_kp, b_k);
         return MONORTM_OK;
     };
     if (defer) { *defer = complete; return MONORTM_OK; }
@@ -1798,10 +1967,7 @@ int monortm_hip_rtm_jac_dev(void *ctx, int nprof, int nwn, const double *wn, con
     return MONORTM_OK;
 }
 
-// MODM of the base and the 2 (1 + njac) perturbed states, then the adjoint chained with their differences.  Small batches (single-
-// profile retrievals underfill the GPU) go through ONE extended MODM launch of all states; larger ones through one launch of nprof
-// profiles per state, of the shapes of a plain MODM call - so that alternating Jacobian and plain calls never resizes the MODM
-// workspaces (an extended launch is only taken while its line-physics records stay below the 64 MB under which MODM keeps them).
+// MODM of the base and the 2 (1 + njac) perturbed states (jac_states), then the adjoint chained with their differences.
 int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
                              const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
                              double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
@@ -1823,57 +1989,11 @@ int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, do
     if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
     if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
-    double vends[2];
-    if (wn_ends) { vends[0] = wn_ends[0]; vends[1] = wn_ends[1]; }
-    else {   // once here, not in every MODM call below
-        HIPCHK(c, hipMemcpyAsync(&vends[0], wn, sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&vends[1], wn + nwn - 1, sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    const int nstate = 3 + 2 * njac;
-    const size_t npl = (size_t)nprof * nlay_max, st = npl * nwn;
-    const bool ext = (long long)nstate * nprof <= 64 && (size_t)nstate * npl * c->host.size() * 48 <= (64u << 20);
-    const size_t nj = ext ? nstate : 1;   // states whose unused MODM outputs are held at once
-    Arena ws;
-    const size_t w_P = ws.add(nstate * npl * 8), w_T = ws.add(nstate * npl * 8), w_C = ws.add(nstate * npl * 8), w_B = ws.add(nstate * npl * 8),
-                 w_W = ws.add(nstate * npl * nmol * 8), w_nl = ws.add(nstate * (size_t)nprof * sizeof(int)), w_O = ws.add(nstate * st * 8),
-                 w_OM = ws.add(nj * st * nmol * 8), w_OC = ws.add(nj * st * MONORTM_NCONT * 8), w_OL = ws.add(nj * st * 8);
-    if (ws.size > c->jac_ws_bytes) {
-        if (c->jac_ws) HIPCHK(c, hipFree(c->jac_ws));
-        c->jac_ws = nullptr;
-        c->jac_ws_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->jac_ws, ws.size));
-        c->jac_ws_bytes = ws.size;
-    }
-    char *wb = static_cast<char *>(c->jac_ws);
-    double *xO = reinterpret_cast<double *>(wb + w_O);
-    JacPerturbArgs pa{};
-    pa.nstate = nstate; pa.nprof = nprof; pa.nlay_max = nlay_max; pa.nmol = nmol; pa.dt = c->opt.jac_dt; pa.dlnw = c->opt.jac_dlnw;
-    for (int i = 0; i < njac; i++) pa.jac_mol[i] = jac_mol[i];
-    pa.P = static_cast<const double *>(P); pa.T = static_cast<const double *>(T); pa.CLW = static_cast<const double *>(CLW);
-    pa.WKL = static_cast<const double *>(WKL); pa.WBRODL = static_cast<const double *>(WBRODL); pa.nlay = nlay;
-    pa.xP = reinterpret_cast<double *>(wb + w_P); pa.xT = reinterpret_cast<double *>(wb + w_T); pa.xCLW = reinterpret_cast<double *>(wb + w_C);
-    pa.xWBRODL = reinterpret_cast<double *>(wb + w_B); pa.xWKL = reinterpret_cast<double *>(wb + w_W); pa.xnlay = reinterpret_cast<int *>(wb + w_nl);
-    launch_jac_perturb(pa, s);
-    HIPCHK(c, hipGetLastError());
-    auto modm = [&](int n, int s0, void *Oout, int slot) {   // MODM of n profiles of the state arrays from state s0 on
-        const size_t l0 = (size_t)s0 * npl;
-        return monortm_hip_modm_xs_dev(c, n, nwn, wn, dvset, pa.xnlay + (size_t)s0 * nprof, nlay_max, nmol, pa.xP + l0, pa.xT + l0, pa.xCLW + l0,
-                                       pa.xWKL + l0 * nmol, pa.xWBRODL + l0, cntnm_fac, sclcpl, sclhw, y0res, ibrd, 0, nullptr, nullptr, Oout,
-                                       wb + w_OM + slot * st * nmol * 8, wb + w_OC + slot * st * MONORTM_NCONT * 8, wb + w_OL + slot * st * 8,
-                                       vends, s);
-    };
-    if (ext) {
-        if (int rc = modm(nstate * nprof, 0, xO, 0)) return rc;
-        HIPCHK(c, hipMemcpyAsync(O, xO, st * 8, hipMemcpyDeviceToDevice, s));
-    } else {
-        // the base state straight from the caller's arrays, into the caller's O: what monortm_hip_modm_dev returns for them
-        if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw,
-                                             y0res, ibrd, 0, nullptr, nullptr, O, wb + w_OM, wb + w_OC, wb + w_OL, vends, s))
-            return rc;
-        for (int k = 1; k < nstate; k++)
-            if (int rc = modm(nprof, k, xO + k * st, 0)) return rc;
-    }
+    double *xO = nullptr;
+    size_t st = 0;
+    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, njac,
+                            jac_mol, O, wn_ends, s, &xO, &st))
+        return rc;
     RtmJacArgs a{};
     a.nprof = nprof; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = 8; a.njac = njac;
     a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
@@ -1956,6 +2076,173 @@ int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double
                                off(tmpsfc, p0 * d), off(emiss, p0 * v), off(reflc, p0 * v), quantity, njac, jac_mol, off(O, p0 * w), off(RAD, p0 * v),
                                off(TB, p0 * v), off(K_T, p0 * w), off(K_TZ, p0 * wz), njac ? off(K_W, p0 * w * njac) : nullptr, off(K_CLW, p0 * w),
                                K_O ? off(K_O, p0 * w) : nullptr, off(K_SFC, p0 * 3 * v), &fin[g]);
+        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
+    }
+    for (int g = 0; g < G; g++)
+        if (fin[g]) {
+            const int r = fin[g]();
+            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
+        }
+    return rc;
+}
+
+// ---- Jacobians of path scans ----------------------------------------------------------------------
+int monortm_hip_rtm_scan_jac_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                                 int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc,
+                                 int sfc_per_path, const void *emiss, const void *reflc, void *RAD, void *TB, void *K_O, void *K_PATH,
+                                 void *K_T, void *K_TZ, void *K_SFC, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !RAD || !TB || !K_T || !K_TZ || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (int rcd = check_device(c)) return rcd;
+    RtmScanJacArgs a{};
+    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = c->real_kind;
+    a.sfc_per_path = sfc_per_path;
+    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_PATH = K_PATH; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
+    a.errflag = c->errflag;
+    launch_rtm_scan_jac(a, false, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+// MODM of the base and the 2 (1 + njac) perturbed states ONCE (jac_states: what monortm_hip_jacobian_dev runs), then one launch of the
+// adjoint along every path, chained with the states' differences.
+int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                                  const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL,
+                                  const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd, const int *irt,
+                                  const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
+                                  const int *jac_mol, int npath, const void *path, int sfc_per_path, void *O, void *RAD, void *TB, void *K_T,
+                                  void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_PATH, void *K_SFC, const double *wn_ends,
+                                  void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (c->real_kind != 8) { c->err = "monortm_hip_scan_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !RAD ||
+        !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (int rcd = check_device(c)) return rcd;
+    double *xO = nullptr;
+    size_t st = 0;
+    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, njac,
+                            jac_mol, O, wn_ends, s, &xO, &st))
+        return rc;
+    RtmScanJacArgs a{};
+    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = 8; a.njac = njac;
+    a.sfc_per_path = sfc_per_path;
+    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_PATH = K_PATH; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC; a.K_W = K_W; a.K_CLW = K_CLW;
+    a.Opert = xO + st;
+    a.state_stride = st;
+    a.dt = c->opt.jac_dt;
+    a.dlnw = c->opt.jac_dlnw;
+    a.errflag = c->errflag;
+    launch_rtm_scan_jac(a, true, s);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+int monortm_hip_rtm_scan_jac(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                             int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc,
+                             int sfc_per_path, const void *emiss, const void *reflc, void *RAD, void *TB, void *K_O, void *K_PATH, void *K_T,
+                             void *K_TZ, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    DeviceGuard guard;
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !RAD || !TB || !K_T || !K_TZ || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
+    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
+    if (c->shards.empty())
+        return rtm_scan_jac_host(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, RAD,
+                                 TB, K_O, K_PATH, K_T, K_TZ, K_SFC, nullptr);
+    const int G = (int)c->shards.size();
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
+    const size_t f = l * npath, vo = v * npath, vs = sfc_per_path ? vo : v, wo = w * npath, wz = (size_t)(nlay_max + 1) * nwn * d * npath;
+    std::vector<std::function<int()>> fin(G);
+    int rc = MONORTM_OK;
+    for (int g = 0; g < G; g++) {
+        int p0, n;
+        shard_block(nprof, G, g, &p0, &n);
+        if (n < 1) continue;
+        Ctx *s = c->shards[g];
+        const int r = rtm_scan_jac_host(s, n, npath, nwn, wn, nlay + p0, nlay_max, irt + p0, quantity, off(T, p0 * l), off(TZ, p0 * (l + d)),
+                                        off(O, p0 * w), off(path, p0 * f), off(tmpsfc, p0 * d), sfc_per_path, off(emiss, p0 * vs),
+                                        off(reflc, p0 * vs), off(RAD, p0 * vo), off(TB, p0 * vo), K_O ? off(K_O, p0 * wo) : nullptr,
+                                        K_PATH ? off(K_PATH, p0 * wo) : nullptr, off(K_T, p0 * wo), off(K_TZ, p0 * wz), off(K_SFC, p0 * 3 * vo),
+                                        &fin[g]);
+        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
+    }
+    for (int g = 0; g < G; g++)
+        if (fin[g]) {
+            const int r = fin[g]();
+            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
+        }
+    return rc;
+}
+
+int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                              const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                              double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                              const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
+                              int sfc_per_path, void *O, void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O,
+                              void *K_PATH, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (c->real_kind != 8) { c->err = "monortm_hip_scan_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
+    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !RAD ||
+        !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    DeviceGuard guard;
+    // the whole call is checked before the first device is touched: a refusal launches nothing anywhere
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
+    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
+    if (int rc = jac_check_states(c, nprof, nwn, wn, nlay, nlay_max, T)) return rc;
+    if (c->shards.empty())
+        return scan_jac_host(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt, TZ,
+                             tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, O, RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O,
+                             K_PATH, K_SFC, nullptr);
+    const int G = (int)c->shards.size();
+    const size_t d = 8, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
+    const size_t f = l * npath, vo = v * npath, vs = sfc_per_path ? vo : v, wo = w * npath, wz = (size_t)(nlay_max + 1) * nwn * d * npath;
+    std::vector<std::function<int()>> fin(G);
+    int rc = MONORTM_OK;
+    for (int g = 0; g < G; g++) {
+        int p0, n;
+        shard_block(nprof, G, g, &p0, &n);
+        if (n < 1) continue;
+        Ctx *s = c->shards[g];
+        const int r = scan_jac_host(s, n, nwn, wn, dvset, nlay + p0, nlay_max, nmol, off(P, p0 * l), off(T, p0 * l), off(CLW, p0 * l),
+                                    off(WKL, p0 * l * nmol), off(WBRODL, p0 * l), cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt + p0,
+                                    off(TZ, p0 * (l + d)), off(tmpsfc, p0 * d), off(emiss, p0 * vs), off(reflc, p0 * vs), quantity, njac, jac_mol,
+                                    npath, off(path, p0 * f), sfc_per_path, off(O, p0 * w), off(RAD, p0 * vo), off(TB, p0 * vo), off(K_T, p0 * wo),
+                                    off(K_TZ, p0 * wz), njac ? off(K_W, p0 * wo * njac) : nullptr, off(K_CLW, p0 * wo),
+                                    K_O ? off(K_O, p0 * wo) : nullptr, K_PATH ? off(K_PATH, p0 * wo) : nullptr, off(K_SFC, p0 * 3 * vo), &fin[g]);
         if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
     }
     for (int g = 0; g < G; g++)

@@ -224,6 +224,21 @@ struct RtmJacArgs {
     size_t state_stride;   // elements of one state's O: nprof x nlay_max x nwn
     double dt, dlnw;
 };
+// Jacobians of path scans (rtm_scan_jac_kernel.hip): the adjoint of RTM along npath paths per profile from ONE
+// set of optical depths; path, emiss, reflc, sfc_per_path and errflag as RtmScanArgs, the others as RtmJacArgs with a path axis behind
+// the profile's: RAD, TB [nprof][npath][nwn], K_O (= factor x dq/dtau, may be null), K_PATH (= O x dq/dtau, may be null), K_T, K_CLW
+// [nprof][npath][nlay_max][nwn], K_TZ [nprof][npath][nlay_max + 1][nwn], K_SFC [nprof][npath][3][nwn], K_W [nprof][npath][nlay_max][njac][nwn].
+struct RtmScanJacArgs {
+    int nprof, npath, nwn, nlay_max, quantity, real_kind, njac, sfc_per_path;
+    const double *wn;
+    const void *T, *TZ, *O, *path, *tmpsfc, *emiss, *reflc;
+    const int *nlay, *irt;
+    void *RAD, *TB, *K_O, *K_PATH, *K_T, *K_TZ, *K_SFC, *K_W, *K_CLW;
+    const void *Opert;
+    size_t state_stride;   // elements of one state's O: nprof x nlay_max x nwn
+    double dt, dlnw;
+    int *errflag;
+};
 // the MODM inputs of the base (state 0) and the perturbed states, [nstate][nprof][nlay_max](x nmol), real_kind 8
 struct JacPerturbArgs {
     int nstate, nprof, nlay_max, nmol;
@@ -270,6 +285,15 @@ __device__ __forceinline__ double rcp2(double x) {
 __device__ __forceinline__ double planck(double c3, double v, double fbeta) {
     const double e = exp_cw(v * fbeta) - 1.;
     return (e == __builtin_inf()) ? 0. : c3 * rcp2(e);
+}
+// B(T) and dB/dT from the same exp_cw(x) - 1 as planck(): x = hc v / kT = v fbeta, fbeta = RADCN2 / T,
+// dB/dT = B (e + 1) / e x / T = B (e + 1) / e v fbeta^2 / RADCN2
+__device__ __forceinline__ void planck_d(double c3, double v, double fbeta, double *B, double *dB) {
+    const double e = exp_cw(v * fbeta) - 1.;
+    if (e == __builtin_inf()) { *B = 0.; *dB = 0.; return; }
+    const double r = rcp2(e), b = c3 * r;
+    *B = b;
+    *dB = b * ((e + 1.) * r) * (v * fbeta * fbeta * (1. / K_RADCN2));
 }
 // ---- the arithmetic rtm_kernel, rtm_scan_kernel and rtm_jac_kernel's forward pass share --------------------------------------------------------------------------
 // A scan path with factor 1 is monortm_hip_rtm's result bit for bit (tests/test_rtm_extremes.py).  Left to the compiler, which
@@ -405,5 +429,7 @@ void launch_rtm_scan(const RtmScanArgs &a, hipStream_t s);
 // jacobian_kernel.hip (full = FULL instantiation, real_kind 8)
 void launch_jac_perturb(const JacPerturbArgs &a, hipStream_t s);
 void launch_rtm_jac(const RtmJacArgs &a, bool full, hipStream_t s);
+// rtm_scan_jac_kernel.hip (full = FULL instantiation, real_kind 8)
+void launch_rtm_scan_jac(const RtmScanJacArgs &a, bool full, hipStream_t s);
 
 }  // namespace monortm_dev

@@ -31,15 +31,7 @@ __global__ __launch_bounds__(256) void jac_perturb_kernel(JacPerturbArgs a) {
     if (k == 0) a.xnlay[(size_t)s * a.nprof + prof] = a.nlay[prof];
 }
 
-// B(T) and dB/dT from the same exp_cw(x) - 1 as planck() (device_common.hpp): x = hc v / kT = v fbeta, fbeta = RADCN2 / T,
-// dB/dT = B (e + 1) / e x / T = B (e + 1) / e v fbeta^2 / RADCN2
-__device__ __forceinline__ void planck_d(double c3, double v, double fbeta, double *B, double *dB) {
-    const double e = exp_cw(v * fbeta) - 1.;
-    if (e == __builtin_inf()) { *B = 0.; *dB = 0.; return; }
-    const double r = rcp2(e), b = c3 * r;
-    *B = b;
-    *dB = b * ((e + 1.) * r) * (v * fbeta * fbeta * (1. / K_RADCN2));
-}
+// planck_d (B(T) and dB/dT): device_common.hpp, shared with rtm_scan_jac_kernel.hip
 
 // ------------------------------------------------------------------------------------------------
 // rtm_jac_kernel: block = 64 wavenumbers x G layer groups of one profile, as rtm_kernel.  With tau = O_k, t = exp(-tau),
