@@ -1080,10 +1080,32 @@ static double xs_xspd(int i1 /*1-based*/, int nptsx, double coef1, double coef2,
     double vv = v1x + (double)(i1 - 1) * delvx; /* :1712 */
     return coef1 * d1[i1 - 1] / radfn(vv, xkt1) + coef2 * d2[i1 - 1] / radfn(vv, xkt2);
 }
-int orc_xsec(int nwn, const double *wn, int nlay, const double *P, const double *T, int nxs, int nreg, const double *reg,
-             const double *temps, const double *pres, const long long *offs, const double *pool, const double *xamnt,
-             double *odxsec) {
+/* orc_xsec_trace: the same walk with optional records per (region, layer, wavenumber), each [nreg][nlay][nwn] or NULL:
+ *   branch      0 region not processed, 1 wavenumber outside the header range, 2 walk, 3 linear interpolation
+ *   trips       walk: j at the stop
+ *   stopkind    walk: 1 the criterion was met with a grid point of the pair still inside (v1x, v2x), 2 both points of the pair
+ *               lay outside (the pair is all zero: the walk ran off both ends)
+ *   thr         walk: ratio x 1e-6
+ *   crit_margin walk: min over all trips of |(xincr / answer) / thr - 1| (a 0/0 trip, NaN, leaves it as it is)
+ *   idx_margin  walk: distance of wn_v1x / step from the nearest integer; linear: of wn_v1x / delvx
+ *   npts_margin both: distance of (v2x - v1x) / (0.25 hwb) from the nearest integer (what int() of :1775 sees unless the step
+ *               is clipped to delvx)
+ *   sw_margin   both: min of |hwd / hwpave - 1| (:1768, before hwpave is replaced), |0.25 hwb / delvx - 1| (:1774) and
+ *               |(hwb / hwd) / 0.1 - 1| (:1788): the distance of the layer from its three switches
+ * A build that contracts a*b+c can differ from this file in the last bits of pd, hwd and hwb; the margins say whether that
+ * can reach an index, a branch or the stopping trip.  The arithmetic of the result is that of orc_xsec, which calls this. */
+static double xs_frac_dist(double x) { return fabs(x - floor(x + 0.5)); }
+int orc_xsec_trace(int nwn, const double *wn, int nlay, const double *P, const double *T, int nxs, int nreg, const double *reg,
+                   const double *temps, const double *pres, const long long *offs, const double *pool, const double *xamnt,
+                   double *odxsec, int *t_branch, int *t_trips, int *t_stopkind, double *t_thr, double *t_crit, double *t_idx,
+                   double *t_npts, double *t_sw) {
     const double dvbuf = 1.0, p0 = 1013.;
+    const size_t ncell = (size_t)(nreg > 0 ? nreg : 0) * nlay * nwn;
+    if (t_branch) memset(t_branch, 0, sizeof(int) * ncell);
+    if (t_trips) memset(t_trips, 0, sizeof(int) * ncell);
+    if (t_stopkind) memset(t_stopkind, 0, sizeof(int) * ncell);
+    { double *z[5] = {t_thr, t_crit, t_idx, t_npts, t_sw};
+      for (int k = 0; k < 5; k++) if (z[k]) memset(z[k], 0, sizeof(double) * ncell); }
     double *xstot = calloc((size_t)nwn * nlay, sizeof(double)), *xsmoltot = calloc((size_t)nwn * nlay, sizeof(double));
     for (int ixmol = 0; ixmol < nxs; ixmol++) {
         memset(xsmoltot, 0, sizeof(double) * (size_t)nwn * nlay);
@@ -1124,9 +1146,14 @@ int orc_xsec(int nwn, const double *wn, int nlay, const double *P, const double 
                 double hwpave = 0.1 * (pave / p0) * (273.15 / tave);
                 double hwd = 0.1 * (pd / p0) * (273.15 / tave);
                 hwd = hwd > hwdop ? hwd : hwdop;
+                const double hwpave0 = hwpave;
                 if (hwd > hwpave) hwpave = 1.001 * hwd;
                 const double hwb = hwpave - hwd;
                 double ratio = 0.25, step = ratio * hwb;
+                const double m_npts = xs_frac_dist((v2x - v1x) / step);
+                double m_sw = fabs(hwd / hwpave0 - 1.);
+                if (fabs(step / delvx - 1.) < m_sw) m_sw = fabs(step / delvx - 1.);
+                if (fabs((hwb / hwd) / 0.1 - 1.) < m_sw) m_sw = fabs((hwb / hwd) / 0.1 - 1.);
                 if (step > delvx) step = delvx;
                 const int npts = (int)((v2x - v1x) / step);
                 step = (v2x - v1x) / (double)npts;
@@ -1134,7 +1161,10 @@ int orc_xsec(int nwn, const double *wn, int nlay, const double *P, const double 
                 const double hwb2 = hwb * hwb;
                 for (int iwn = 0; iwn < nwn; iwn++) {
                     double res;
-                    if (wn[iwn] < v1x || wn[iwn] > v2x) res = 0.;
+                    const size_t tc = ((size_t)r * nlay + il) * nwn + iwn;
+                    if (t_npts) t_npts[tc] = m_npts;
+                    if (t_sw) t_sw[tc] = m_sw;
+                    if (wn[iwn] < v1x || wn[iwn] > v2x) { res = 0.; if (t_branch) t_branch[tc] = 1; }
                     else if (hwb / hwd > 0.1) {
                         /* xspd_int(i) = (1-coef) xspd(ind+1) + coef xspd(ind+2), ind = int(i step / delvx)  (:1779-1785) */
 #define XSI(i, out) do { double vv_ = v1x + (double)(i) * step; double delvv_ = vv_ - v1x; int ind_ = (int)(delvv_ / delvx); \
@@ -1145,6 +1175,8 @@ int orc_xsec(int nwn, const double *wn, int nlay, const double *P, const double 
                         double x0, x1;
                         XSI(ind, x0); XSI(ind + 1, x1);
                         double answer = (hwb / (hwb2 + dvlo * dvlo)) * x0 + (hwb / (hwb2 + dvhi * dvhi)) * x1;
+                        double m_crit = HUGE_VAL;
+                        int jstop = 0, kstop = 0;
                         for (int j = 1;; j++) {
                             double contlo, conthi;
                             const double vlo = v1x + (double)(ind - j) * step;
@@ -1154,9 +1186,16 @@ int orc_xsec(int nwn, const double *wn, int nlay, const double *P, const double 
                             if (vhi < v2x) { dvhi = wn[iwn] - vhi; double xv; XSI(ind + j + 1, xv); conthi = (hwb / (hwb2 + dvhi * dvhi)) * xv; }
                             else conthi = 0.;
                             const double xincr = contlo + conthi;
-                            if ((xincr / answer) < ratio * 1e-6) break;
+                            { const double m_ = fabs((xincr / answer) / (ratio * 1e-6) - 1.); if (m_ < m_crit) m_crit = m_; }
+                            if ((xincr / answer) < ratio * 1e-6) { jstop = j; kstop = (vlo > v1x || vhi < v2x) ? 1 : 2; break; }
                             answer = answer + xincr;
                         }
+                        if (t_branch) t_branch[tc] = 2;
+                        if (t_trips) t_trips[tc] = jstop;
+                        if (t_stopkind) t_stopkind[tc] = kstop;
+                        if (t_thr) t_thr[tc] = ratio * 1e-6;
+                        if (t_crit) t_crit[tc] = m_crit;
+                        if (t_idx) t_idx[tc] = xs_frac_dist(wn_v1x / step);
                         res = answer * step / 3.14159;
                     } else {
                         /* linearly interpolated values - with xspd(ind), xspd(ind+1), one element below the resampling
@@ -1165,6 +1204,8 @@ int orc_xsec(int nwn, const double *wn, int nlay, const double *P, const double 
                         const int ind = (int)(wn_v1x / delvx);
                         const double coef = (wn_v1x - (double)ind * delvx) / delvx;
                         res = (1. - coef) * XSPD(ind) + coef * XSPD(ind + 1);
+                        if (t_branch) t_branch[tc] = 3;
+                        if (t_idx) t_idx[tc] = xs_frac_dist(wn_v1x / delvx);
                     }
                     xsmoltot[(size_t)il * nwn + iwn] += res;
                 }
@@ -1182,6 +1223,12 @@ int orc_xsec(int nwn, const double *wn, int nlay, const double *P, const double 
     }
     free(xstot); free(xsmoltot);
     return ORC_OK;
+}
+int orc_xsec(int nwn, const double *wn, int nlay, const double *P, const double *T, int nxs, int nreg, const double *reg,
+             const double *temps, const double *pres, const long long *offs, const double *pool, const double *xamnt,
+             double *odxsec) {
+    return orc_xsec_trace(nwn, wn, nlay, P, T, nxs, nreg, reg, temps, pres, offs, pool, xamnt, odxsec, NULL, NULL, NULL, NULL, NULL,
+                          NULL, NULL, NULL);
 }
 /* the optional ODXSEC term of the next orc_modm call (modm.f90:197, :268); reset by that call */
 static const double *g_odxsec = NULL;

@@ -51,6 +51,9 @@ def lib():
         _lp = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
         L.orc_xsec.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _lp, _dp, _dp, _dp]
         L.orc_xsec.restype = C.c_int
+        _ip = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+        L.orc_xsec_trace.argtypes = L.orc_xsec.argtypes + [_ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
+        L.orc_xsec_trace.restype = C.c_int
         L.orc_set_odxsec.argtypes = [C.c_void_p]
         L.orc_set_odxsec.restype = None
         L.orc_iso_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]
@@ -146,6 +149,38 @@ class Oracle:
         self.L.orc_rtm(pr.iout, pr.irt, nwn, pr.wn, nlay, pr.t, pr.tz, o, C.byref(ts), rup, trtot, rdn,
                        pr.reflc, pr.emiss, rad, tb)
         return Dump(o, obm, oc, oclw, rup, rdn, trtot, rad, tb, tmr, ts.value, odx)
+
+
+XS_BRANCHES = ("unprocessed", "outside", "walk", "linear")     # values of XsTrace.branch
+XS_STOP_CRITERION, XS_STOP_BOTH_ENDS = 1, 2                   # values of XsTrace.stopkind
+
+
+def xsec_trace(wn, p, t, tabs, xamnt, trace: bool = True):
+    """MONORTM_XSEC_SUB of the oracle on tables held in memory (monortm_amd.xsec.XsTables): -> (odxsec [nlay, nwn], trace).
+    The trace (orc_xsec_trace in monortm_oracle.c) is a namespace of [nreg, nlay, nwn] arrays: branch, trips, stopkind, thr,
+    crit_margin, idx_margin, npts_margin, sw_margin; None with trace = False."""
+    import types
+
+    c = np.ascontiguousarray
+    wn, p, t = c(wn, np.float64), c(p, np.float64), c(t, np.float64)
+    reg, temps, pres, offs, pool = tabs.flatten()
+    nreg, nlay, nwn, nxs = len(reg), len(p), len(wn), len(tabs.names)
+    assert nreg > 0 and len(pool) > 0
+    xamnt = c(xamnt, np.float64).reshape(nlay, nxs)
+    odx = np.zeros((nlay, nwn))
+    args = (nwn, wn, nlay, p, t, nxs, nreg, c(reg), c(temps), c(pres), c(offs), c(pool), xamnt, odx)
+    if not trace:
+        rc = lib().orc_xsec(*args)
+        tr = None
+    else:
+        shape = (nreg, nlay, nwn)
+        ints = {k: np.zeros(shape, np.int32) for k in ("branch", "trips", "stopkind")}
+        dbls = {k: np.zeros(shape) for k in ("thr", "crit_margin", "idx_margin", "npts_margin", "sw_margin")}
+        rc = lib().orc_xsec_trace(*args, *ints.values(), *dbls.values())
+        tr = types.SimpleNamespace(**ints, **dbls)
+    if rc:
+        raise OracleError(f"orc_xsec rc={rc}")
+    return odx, tr
 
 
 def kat_wide(which: int, args: np.ndarray) -> np.ndarray:
