@@ -350,6 +350,78 @@ int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *w
                                   monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_O,
                                   monortm_real *K_PATH, monortm_real *K_SFC, const double *wn_ends, void *stream);
 
+/* ---- Channel- and beam-averaged Jacobians of path scans: K per MEASUREMENT (no reference counterpart).  DESIGN.md section 3.9.
+ * An instrument measures a passband, sampled by several wavenumbers, through a beam, sampled by several paths of a scan:
+ *   y[p][v][c] = sum_{j in view v} wpath[j] sum_{i: chan[i] = c} wchan[i] q[p][j][i],   q = RAD or TB by `quantity`.
+ * Every derivative below is taken with respect to a per-layer or per-profile variable that all samples of a measurement share, so
+ * the contraction is exact; it happens inside the kernel that forms the monochromatic per-path terms (rtm_obs_jac_kernel.hip), and
+ * none of those reaches memory.
+ *
+ * The measurement operator is defined once per context: the paths of view v are view_start[v] .. view_start[v + 1] - 1 (CSR: the
+ * paths of a view are adjacent; view_start[0] = 0, non-decreasing, view_start[nview] = npath; an empty view is allowed, its outputs
+ * are 0).  chan[i] in [-1, nchan) is an arbitrary map of wavenumber i to its channel (-1: unused; sidebands may nest, a channel may
+ * have no sample: 0).  The weights are finite doubles of any sign; normalisation is the caller's.  1 <= npath <= 16384, nwn <= 80000,
+ * nview <= 65535, nchan <= 65536.  Everything is checked here, on the host: bad shapes, bad indices or non-finite weights return
+ * MONORTM_EARG with a message and create nothing.  The tables go to the device (of a multi-device context: to every device) once;
+ * the calls below take the handle and copy nothing.  A context holds up to 16 operators; all are released by monortm_hip_finalize.
+ * A stale or foreign handle: MONORTM_EARG.  monortm_hip_obs_destroy waits for the device before it frees the tables. */
+int monortm_hip_obs_create(void *ctx, int npath, int nwn, int nview, int nchan, const int *view_start /*[nview + 1]*/,
+                           const double *wpath /*[npath]*/, const int *chan /*[nwn]*/, const double *wchan /*[nwn]*/, int *handle);
+int monortm_hip_obs_destroy(void *ctx, int handle);
+
+/* Outputs, in the context's real type (arguments, refusals and the meaning of K as monortm_hip_rtm_scan_jac / monortm_hip_scan_jacobian;
+ * npath and nwn must be the operator's, MONORTM_EARG otherwise):
+ *   Y            [nprof][nview][nchan]
+ *   K_T, K_CLW   [nprof][nview][nlay_max][nchan]
+ *   K_TZ         [nprof][nview][nlay_max + 1][nchan]
+ *   K_W          [nprof][nview][nlay_max][njac][nchan]
+ *   K_SFC        [nprof][nview][3][nchan]      dy/dTMPSFC; rows 1, 2: the derivative with respect to a COMMON shift of EMISS (REFLC) of
+ *                                              all samples of the measurement - every wavenumber (and, with sfc_per_path, path) of it
+ * Entries of layers >= nlay[p] and levels > nlay[p] are 0.  There is no K_O and no K_PATH: their variables are per wavenumber or per
+ * path, a contraction over them means nothing (use monortm_hip_scan_jacobian).  The sums are formed in a fixed order - paths ascending
+ * within a tile of 4, wavenumbers ascending within a block of 64, then tiles ascending and blocks ascending within a tile - without
+ * atomics: repeated calls give the same bits, and a profile gives the same bits alone and inside a batch.
+ *
+ * RTM adjoint only, given O: real_kind 8 and 4.  Host buffers: sharded by profile like monortm_hip_rtm_scan_jac, nlay and the factors
+ * of the whole call checked first; with real_kind 4 the sums are held in double and rounded once. */
+int monortm_hip_rtm_obs_jac(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max,
+                            const int *irt, int quantity, const monortm_real *T, const monortm_real *TZ, const monortm_real *O,
+                            const monortm_real *path, const monortm_real *tmpsfc, int sfc_per_path, const monortm_real *emiss,
+                            const monortm_real *reflc, int obs, monortm_real *Y, monortm_real *K_T, monortm_real *K_TZ,
+                            monortm_real *K_SFC);
+/* The same on device pointers, asynchronous on `stream`; one-device context.  Allocates and copies nothing.  A bad factor of an active
+ * layer surfaces through monortm_hip_check (MONORTM_EARG).  With real_kind 4 the outputs themselves hold the running sums: one float
+ * rounding per (tile of paths, block of wavenumbers) that contributes to an element. */
+int monortm_hip_rtm_obs_jac_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max,
+                                const int *irt, int quantity, const monortm_real *T, const monortm_real *TZ, const monortm_real *O,
+                                const monortm_real *path, const monortm_real *tmpsfc, int sfc_per_path, const monortm_real *emiss,
+                                const monortm_real *reflc, int obs, monortm_real *Y, monortm_real *K_T, monortm_real *K_TZ,
+                                monortm_real *K_SFC, void *stream);
+
+/* MODM + RTM with Jacobians per measurement: the 3 + 2 njac MODM passes of monortm_hip_jacobian ONCE, then one launch of the contracting
+ * adjoint.  O returns the vertical optical depths exactly as monortm_hip_scan_jacobian does.  real_kind 8 only (MONORTM_EUNSUPPORTED
+ * otherwise); jac_mol, the half-steps, the factors and the errors as monortm_hip_scan_jacobian; no cross-section molecules. */
+int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
+                             int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
+                             const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac, double sclcpl,
+                             double sclhw, double y0res, int ibrd, const int *irt, const monortm_real *TZ,
+                             const monortm_real *tmpsfc, const monortm_real *emiss, const monortm_real *reflc, int quantity,
+                             int njac, const int *jac_mol, int npath, const monortm_real *path, int sfc_per_path, int obs,
+                             monortm_real *O, monortm_real *Y, monortm_real *K_T, monortm_real *K_TZ, monortm_real *K_W,
+                             monortm_real *K_CLW, monortm_real *K_SFC);
+/* The same on device pointers, asynchronous on `stream`; one-device context.  wn_ends as for monortm_hip_modm_dev.  Device-side
+ * failures (temperature range, bad factors) surface through monortm_hip_check.  After one call, a second of the same shapes
+ * allocates nothing (graph capture); the launch of the adjoint itself never allocates. */
+int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
+                                 int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
+                                 const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac /*host*/,
+                                 double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const monortm_real *TZ,
+                                 const monortm_real *tmpsfc, const monortm_real *emiss, const monortm_real *reflc,
+                                 int quantity, int njac, const int *jac_mol /*host*/, int npath, const monortm_real *path,
+                                 int sfc_per_path, int obs, monortm_real *O, monortm_real *Y, monortm_real *K_T,
+                                 monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_SFC,
+                                 const double *wn_ends, void *stream);
+
 /* Device-side failure flags raised by the kernels of earlier *_dev calls (temperature range, SD-Voigt
  * sign): synchronises `stream`, returns MONORTM_OK or the first error and clears the flags. */
 int monortm_hip_check(void *ctx, void *stream);

@@ -80,6 +80,18 @@ SYMBOLS = {
     "monortm_hip_scan_jacobian_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
                                                 C.c_int, _vp, C.c_int] + [_vp] * 12),
+    "monortm_hip_obs_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _ip]),
+    "monortm_hip_obs_destroy": (C.c_int, [_vp, C.c_int]),
+    "monortm_hip_rtm_obs_jac": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                          _vp, _vp, C.c_int] + [_vp] * 4),
+    "monortm_hip_rtm_obs_jac_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                              C.c_int, _vp, _vp, C.c_int] + [_vp] * 5),
+    "monortm_hip_obs_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
+                                           C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 7),
+    "monortm_hip_obs_jacobian_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
+                                               C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 9),
     "monortm_hip_check": (C.c_int, [_vp, _vp]),
     "monortm_hip_profile": (C.c_int, [_vp, C.c_int]),
     "monortm_hip_kernel_time": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_longlong)]),
@@ -94,6 +106,98 @@ JAC_DLNW = 1e-4
 JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_sfc")
 SCAN_JAC_RTM_FIELDS = ("rad", "tb", "k_o", "k_path", "k_t", "k_tz", "k_sfc")                 # output order of monortm_hip_rtm_scan_jac
 SCAN_JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_path", "k_sfc")   # ... of monortm_hip_scan_jacobian
+OBS_JAC_RTM_FIELDS = ("y", "k_t", "k_tz", "k_sfc")                                           # output order of monortm_hip_rtm_obs_jac
+OBS_JAC_FIELDS = ("o", "y", "k_t", "k_tz", "k_w", "k_clw", "k_sfc")                           # ... of monortm_hip_obs_jacobian
+OBS_MAX_PATHS, OBS_MAX_WN, OBS_MAX_VIEWS, OBS_MAX_CHAN = 16384, 80000, 65535, 65536           # the bounds of monortm_hip_obs_create
+
+
+class ObsOperator:
+    """A measurement operator (monortm_hip_obs_create): views = beams sampled by adjacent paths of a scan,
+    channels = passbands sampled by wavenumbers,
+        y[p, v, c] = sum_{j in view v} wpath[j] sum_{i: chan[i] = c} wchan[i] q[p, j, i].
+    view_start [nview + 1] is CSR (view v holds the paths view_start[v] .. view_start[v + 1] - 1; starts at 0, never decreases, ends at
+    npath; empty views are allowed), chan [nwn] maps every wavenumber to its channel or to -1 (unused), the weights are finite and of
+    any sign; nchan defaults to max(chan) + 1.  The same checks as the C entry, raised as ValueError."""
+
+    def __init__(self, view_start, wpath, chan, wchan, nchan=None):
+        def arr(x, dt, name):
+            a = np.asarray(x)
+            if a.ndim != 1 or not (np.issubdtype(a.dtype, np.integer) if dt == np.int32 else np.issubdtype(a.dtype, np.number)
+                                   and not np.issubdtype(a.dtype, np.complexfloating)):
+                raise ValueError(f"{name}: a 1-D array of {'integers' if dt == np.int32 else 'real numbers'}")
+            if dt == np.int32 and a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise ValueError(f"{name}: out of range")
+            return np.ascontiguousarray(a, dt)
+
+        vs, wp = arr(view_start, np.int32, "view_start"), arr(wpath, np.float64, "wpath")
+        ch, wc = arr(chan, np.int32, "chan"), arr(wchan, np.float64, "wchan")
+        npath, nwn, nview = len(wp), len(ch), len(vs) - 1
+        if not 1 <= npath <= OBS_MAX_PATHS:
+            raise ValueError(f"npath = len(wpath) outside 1..{OBS_MAX_PATHS}")
+        if not 1 <= nwn <= OBS_MAX_WN or len(wc) != nwn:
+            raise ValueError(f"chan and wchan must have the same length nwn in 1..{OBS_MAX_WN}")
+        if not 1 <= nview <= OBS_MAX_VIEWS:
+            raise ValueError(f"view_start must have nview + 1 entries, nview in 1..{OBS_MAX_VIEWS}")
+        if vs[0] != 0 or vs[-1] != npath or np.any(np.diff(vs) < 0):
+            raise ValueError("view_start must start at 0, never decrease and end at npath")
+        if nchan is None:
+            nchan = int(ch.max()) + 1
+        nchan = int(nchan)
+        if not 1 <= nchan <= OBS_MAX_CHAN:
+            raise ValueError(f"nchan outside 1..{OBS_MAX_CHAN}")
+        if ch.min() < -1 or ch.max() >= nchan:
+            raise ValueError("chan must lie in -1..nchan-1")
+        if ((nwn + 63) // 64) * (nchan + 1) > 1 << 26:
+            raise ValueError("nwn / 64 x nchan exceeds the membership table's bound (2^26 entries)")
+        if not (np.all(np.isfinite(wp)) and np.all(np.isfinite(wc))):
+            raise ValueError("the weights must be finite")
+        self.view_start, self.wpath, self.chan, self.wchan = vs, wp, ch, wc
+        self.npath, self.nwn, self.nview, self.nchan = npath, nwn, nview, nchan
+        for a in (vs, wp, ch, wc):
+            a.setflags(write=False)
+
+    def dense(self) -> np.ndarray:
+        """The [nview * nchan, npath * nwn] weight matrix W: y[p].ravel() = W @ q[p].ravel() for q [npath, nwn]."""
+        vw = np.zeros((self.nview, self.npath))
+        for v in range(self.nview):
+            j = slice(self.view_start[v], self.view_start[v + 1])
+            vw[v, j] = self.wpath[j]
+        cw = np.zeros((self.nchan, self.nwn))
+        used = self.chan >= 0
+        cw[self.chan[used], np.nonzero(used)[0]] = self.wchan[used]
+        return np.einsum("vj,ci->vcji", vw, cw).reshape(self.nview * self.nchan, self.npath * self.nwn)
+
+    @classmethod
+    def from_sets(cls, views, channels, npath=None, nwn=None):
+        """Uniform normalised weights from index sets: views = [[paths of view 0], ...] (every path in at most one view), channels =
+        [[wavenumbers of channel 0], ...] (every wavenumber in at most one channel).  Path j of a view of n paths gets 1 / n, sample i
+        of a channel of m samples 1 / m.  The paths are reordered into CSR: returns (operator, perm) with perm[k] = the caller's index
+        of the operator's path k - hand path[..., perm, :] (and emiss / reflc per path likewise) to the calls.  The operator holds the
+        paths of the views only (its npath is len(perm)): a path in no view is not handed over at all, so whatever lies along it - a
+        non-finite radiance included - cannot reach a measurement.  npath, where given, is the caller's number of paths (the bound
+        of the indices)."""
+        views = [[int(j) for j in v] for v in views]
+        channels = [[int(i) for i in c] for c in channels]
+        if not views or not channels:
+            raise ValueError("at least one view and one channel")
+        flat = [j for v in views for j in v]
+        npath = (max(flat) + 1 if flat else 1) if npath is None else int(npath)
+        fl = [i for c in channels for i in c]
+        nwn = (max(fl) + 1 if fl else 1) if nwn is None else int(nwn)
+        if len(set(flat)) != len(flat) or any(not 0 <= j < npath for j in flat):
+            raise ValueError("views: every path index in 0..npath-1 and in at most one view")
+        if len(set(fl)) != len(fl) or any(not 0 <= i < nwn for i in fl):
+            raise ValueError("channels: every wavenumber index in 0..nwn-1 and in at most one channel")
+        if not flat:
+            raise ValueError("views: at least one view must hold a path")
+        perm = np.array(flat, np.int64)
+        vs = np.concatenate([[0], np.cumsum([len(v) for v in views])]).astype(np.int32)
+        wp = np.concatenate([np.full(len(v), 1.0 / len(v)) for v in views if v])
+        ch, wc = np.full(nwn, -1, np.int32), np.zeros(nwn)
+        for c, members in enumerate(channels):
+            ch[members] = c
+            wc[members] = 1.0 / max(len(members), 1)
+        return cls(vs, wp, ch, wc, nchan=len(channels)), perm
 
 
 def _quantity(q) -> int:
@@ -462,6 +566,79 @@ class MonoRTM:
                                                      *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS]))
         return out
 
+    # ---- channel- and beam-averaged Jacobians (monortm_hip_obs_create / _rtm_obs_jac / _obs_jacobian) ------------
+    def obs_create(self, op: ObsOperator) -> int:
+        """The operator's tables go to the device(s) once; returns the handle the calls below take (up to 16 per context)."""
+        h = C.c_int(0)
+        self._chk(self.lib.monortm_hip_obs_create(self.ctx, op.npath, op.nwn, op.nview, op.nchan, _ptr(op.view_start), _ptr(op.wpath),
+                                                  _ptr(op.chan), _ptr(op.wchan), C.byref(h)))
+        self.__dict__.setdefault("_obs", {})[h.value] = op
+        return h.value
+
+    def obs_destroy(self, handle: int) -> None:
+        self._chk(self.lib.monortm_hip_obs_destroy(self.ctx, int(handle)))
+        self.__dict__.get("_obs", {}).pop(int(handle), None)
+
+    def _obs_shape(self, handle: int):
+        op = self.__dict__.get("_obs", {}).get(int(handle))
+        if op is None:
+            raise MonoRTMError(6, "obs: not a handle of this context (never created here, or destroyed)")
+        return op.nview, op.nchan
+
+    def rtm_obs_jacobian(self, profiles: list[Profile], O: np.ndarray, path, obs: int, quantity="tb", emiss=None, reflc=None) -> dict:
+        """The adjoint of RTM per measurement from one O [nprof, nlay_max, nwn]: the terms of rtm_scan_jacobian contracted with the
+        operator `obs` (a handle of obs_create) inside the kernel.  Dict of y [nprof, nview, nchan], k_t (Planck term only)
+        [nprof, nview, nlay_max, nchan], k_tz [nprof, nview, nlay_max + 1, nchan], k_sfc [nprof, nview, 3, nchan] (the emissivity and
+        reflectivity rows: with respect to a common shift of all samples of the measurement)."""
+        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
+        dt = self.dtype
+        f = self._path(path, nprof, lm)
+        npath = f.shape[1]
+        em, rf = self._scan_sfc(em, rf, emiss, reflc, nprof, npath, nwn)
+        O = _np(O, dt)
+        if O.shape != (nprof, lm, nwn):
+            raise ValueError(f"O must be [{nprof}, {lm}, {nwn}], got {O.shape}")
+        nv, nc = self._obs_shape(obs)
+        z = lambda *s: np.zeros((nprof, nv) + s + (nc,), dt)  # noqa: E731
+        out = dict(y=z(), k_t=z(lm), k_tz=z(lm + 1), k_sfc=z(3))
+        wn = _np(profiles[0].wn)
+        self._chk(self.lib.monortm_hip_rtm_obs_jac(self.ctx, nprof, npath, nwn, _ptr(wn), _ptr(nlay), lm, _ptr(irt), _quantity(quantity),
+                                                   _ptr(T), _ptr(TZ), _ptr(O), _ptr(f), _ptr(ts), int(em.ndim == 3), _ptr(em), _ptr(rf),
+                                                   int(obs), *[_ptr(out[k]) for k in OBS_JAC_RTM_FIELDS]))
+        return out
+
+    def obs_jacobian(self, profiles: list[Profile], path, obs: int, mols=(1,), quantity="tb", emiss=None, reflc=None) -> dict:
+        """MODM (the base and the perturbed states of jacobian(), ONCE) + RTM with Jacobians per measurement (real_kind 8): the fields
+        of rtm_obs_jacobian with the optical-depth term in k_t, plus o [nprof, nlay_max, nwn] (the vertical optical depths, as
+        scan_jacobian returns them), k_w [nprof, nview, nlay_max, len(mols), nchan] and k_clw [nprof, nview, nlay_max, nchan]."""
+        p0 = profiles[0]
+        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
+        nmol, dt = p0.nmol, self.dtype
+        f = self._path(path, nprof, lm)
+        npath = f.shape[1]
+        em, rf = self._scan_sfc(em, rf, emiss, reflc, nprof, npath, nwn)
+
+        def pack(get, width=None):
+            out = np.zeros((nprof, lm) if width is None else (nprof, lm, width), dt)
+            for i, p in enumerate(profiles):
+                out[i, : p.nlay] = get(p)
+            return out
+
+        P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
+        WKL = pack(lambda p: p.wkl, nmol)
+        jm = np.ascontiguousarray(np.asarray(mols, np.int32).reshape(-1))
+        nj = len(jm)
+        nv, nc = self._obs_shape(obs)
+        z = lambda *s: np.zeros((nprof, nv) + s + (nc,), dt)  # noqa: E731
+        out = dict(o=np.zeros((nprof, lm, nwn), dt), y=z(), k_t=z(lm), k_tz=z(lm + 1), k_w=z(lm, nj), k_clw=z(lm), k_sfc=z(3))
+        wn, fac = _np(p0.wn), _np(p0.cntnm)
+        self._chk(self.lib.monortm_hip_obs_jacobian(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T),
+                                                    _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd,
+                                                    _ptr(irt), _ptr(TZ), _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj,
+                                                    _ptr(jm) if nj else None, npath, _ptr(f), int(em.ndim == 3), int(obs),
+                                                    *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS]))
+        return out
+
     # ---- the C-ABI gather of a profile-sharded job (RCCL; what a C / Fortran caller uses instead of torch.distributed) ------
     @staticmethod
     def comm_unique_id() -> bytes:
@@ -691,6 +868,49 @@ class DeviceBatch:
                                                   d(self.reflc), key[2], nj, _ptr(jm) if nj else None, npath, d(fd), 0,
                                                   *[d(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS],
                                                   _ptr(self.wn_ends), _vp(s.cuda_stream)))
+        return out
+
+    # ---- channel- and beam-averaged Jacobians on the resident batch (monortm_hip_obs_jacobian_dev) --------------------------------------
+    def obs_jacobian(self, path, obs: int, mols=(1,), quantity="tb", stream=None) -> dict:
+        """K per measurement on the current (or the given) stream, asynchronously: a dict of torch tensors with the fields and shapes
+        of MonoRTM.obs_jacobian; obs is a handle of rt.obs_create.  The outputs and the device copy of the factors are allocated at
+        the first call for (obs, npath, mols, quantity), overwritten by every later one and dropped at the first call after
+        rt.obs_destroy(obs), so that a graph capture of the call (after
+        one warm call, with the factors in a tensor on the batch's device) replays into the same tensors.  path as DeviceBatch.scan;
+        no monochromatic or per-path K is allocated anywhere.  Bad factors surface through check()."""
+        t = self.torch
+        real = t.float32 if self.rt.real_kind == 4 else t.float64  # dtype of the REAL arrays
+        f = t.as_tensor(path)
+        if f.dim() == 2:
+            f = f.unsqueeze(0).expand(self.nprof, -1, -1)
+        if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
+            raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
+        npath = int(f.shape[1])
+        key = (int(obs), npath, tuple(int(m) for m in mols), _quantity(quantity))
+        cache = self.__dict__.setdefault("_obs_jac", {})
+        live = self.rt.__dict__.get("_obs", {})
+        for k in [k for k in cache if k[0] not in live]:   # operators destroyed since: handles are never reused, let their tensors go
+            del cache[k]
+        if key not in cache:
+            nv, nc = self.rt._obs_shape(obs)
+            n, lm, nw, nj = self.nprof, self.lm, self.nwn, len(key[2])
+            z = lambda *s: t.zeros(*s, dtype=real, device=self.dev)  # noqa: E731
+            zv = lambda *s: z(n, nv, *s, nc)  # noqa: E731
+            cache[key] = (dict(o=z(n, lm, nw), y=zv(), k_t=zv(lm), k_tz=zv(lm + 1), k_w=zv(lm, nj), k_clw=zv(lm), k_sfc=zv(3)),
+                          np.ascontiguousarray(key[2], np.int32), z(n, npath, lm))
+        out, jm, fd = cache[key]
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        with t.cuda.stream(s):
+            fd.copy_(f, non_blocking=True)
+        p0, lib, rt = self.p0, self.rt.lib, self.rt
+        d = lambda x: _vp(x.data_ptr())  # noqa: E731
+        nj = len(jm)
+        rt._chk(lib.monortm_hip_obs_jacobian_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol,
+                                                 d(self.P), d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl,
+                                                 p0.sclhw, p0.y0res, p0.ibrd, d(self.irt), d(self.TZ), d(self.tmpsfc0), d(self.emiss),
+                                                 d(self.reflc), key[3], nj, _ptr(jm) if nj else None, npath, d(fd), 0, int(obs),
+                                                 *[d(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS],
+                                                 _ptr(self.wn_ends), _vp(s.cuda_stream)))
         return out
 
     # ---- HIP graph: the three launches of a step recorded once, replayed with a single call ------------------

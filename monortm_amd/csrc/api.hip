@@ -1,6 +1,7 @@
 // api.hip - host side of the C ABI (include/monortm_hip.h): context, TAPE3 -> device line table, model tables,
 // launch configuration, host-buffer front ends for the Fortran shim.
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -87,6 +88,18 @@ struct Ctx {
     // that the Jacobian does not use, grown on demand and kept (a second call of the same shapes allocates nothing)
     void *jac_ws = nullptr;
     size_t jac_ws_bytes = 0;
+    // measurement operators (monortm_hip_obs_create): the device tables of up to kMaxObs operators, checked on
+    // the host when they were created - the kernel never sees an unchecked index, and a call that takes a handle copies nothing
+    struct Obs {
+        int handle = 0;   // 0 = free
+        int npath = 0, nwn = 0, nview = 0, nchan = 0;
+        void *dev = nullptr;   // one allocation: wpath, mw, view_start, mstart, mlane
+        const int *view_start = nullptr, *mstart = nullptr, *mlane = nullptr;
+        const double *wpath = nullptr, *mw = nullptr;
+        std::vector<int> shard;   // multi-device context: the operator's handle on every shard
+    };
+    static constexpr int kMaxObs = 16;
+    Obs obs[kMaxObs];
     // The host-buffer entry points run on their own stream: one asynchronous upload, the kernels, one asynchronous
     // download (+ the 4-byte error flag) and a single synchronisation per call.
     hipStream_t hs = nullptr;
@@ -1033,6 +1046,8 @@ void monortm_hip_finalize(void *ctx) {
         if (e) hipEventDestroy(e);
     c->mw_cache.release();
     if (c->jac_ws) hipFree(c->jac_ws);
+    for (auto &ob : c->obs)
+        if (ob.dev) hipFree(ob.dev);
     for (int i = 0; i < 12; i++)
         if (c->stage[i].p) {
             if (i % 2 == 0) hipHostFree(c->stage[i].p);  // even slots: pinned host arenas
@@ -2243,6 +2258,453 @@ int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, d
                                     npath, off(path, p0 * f), sfc_per_path, off(O, p0 * w), off(RAD, p0 * vo), off(TB, p0 * vo), off(K_T, p0 * wo),
                                     off(K_TZ, p0 * wz), njac ? off(K_W, p0 * wo * njac) : nullptr, off(K_CLW, p0 * wo),
                                     K_O ? off(K_O, p0 * wo) : nullptr, K_PATH ? off(K_PATH, p0 * wo) : nullptr, off(K_SFC, p0 * 3 * vo), &fin[g]);
+        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
+    }
+    for (int g = 0; g < G; g++)
+        if (fin[g]) {
+            const int r = fin[g]();
+            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
+        }
+    return rc;
+}
+
+
+// ---- channel- and beam-averaged Jacobians of path scans ---------------------------------------------
+}  // extern "C"
+
+namespace {
+constexpr int kObsMaxViews = 65535, kObsMaxChan = 65536;
+constexpr size_t kObsMaxTable = size_t(1) << 26;   // entries of the per-block membership table (256 MB of int)
+
+Ctx::Obs *obs_find(Ctx *c, int handle) {
+    if (handle <= 0) return nullptr;
+    Ctx::Obs &ob = c->obs[handle % Ctx::kMaxObs];
+    return ob.handle == handle ? &ob : nullptr;
+}
+int obs_bad_handle(Ctx *c) {
+    c->err = "obs: not a handle of this context (never created here, or destroyed)";
+    return MONORTM_EARG;
+}
+// the handle's operator, and that the call's npath and nwn are the operator's
+int obs_for_call(Ctx *c, int handle, int npath, int nwn, Ctx::Obs **out) {
+    Ctx::Obs *ob = obs_find(c, handle);
+    if (!ob) return obs_bad_handle(c);
+    if (ob->npath != npath || ob->nwn != nwn) {
+        c->err = "the measurement operator was created for npath = " + std::to_string(ob->npath) + ", nwn = " + std::to_string(ob->nwn) +
+                 "; the call has npath = " + std::to_string(npath) + ", nwn = " + std::to_string(nwn);
+        return MONORTM_EARG;
+    }
+    *out = ob;
+    return MONORTM_OK;
+}
+
+// everything monortm_hip_obs_create refuses, on host arrays
+int obs_check(Ctx *c, int npath, int nwn, int nview, int nchan, const int *view_start, const double *wpath, const int *chan,
+              const double *wchan) {
+    if (!view_start || !wpath || !chan || !wchan) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (npath < 1 || npath > kScanMaxPaths) { c->err = "npath outside 1.." + std::to_string(kScanMaxPaths); return MONORTM_EARG; }
+    if (nwn < 1 || nwn > 80000) { c->err = "nwn outside 1..80000 (NWNMX, RTMmono.f90:10)"; return MONORTM_EARG; }
+    if (nview < 1 || nview > kObsMaxViews) { c->err = "nview outside 1.." + std::to_string(kObsMaxViews); return MONORTM_EARG; }
+    if (nchan < 1 || nchan > kObsMaxChan) { c->err = "nchan outside 1.." + std::to_string(kObsMaxChan); return MONORTM_EARG; }
+    if ((size_t)((nwn + 63) / 64) * (size_t)(nchan + 1) > kObsMaxTable) { c->err = "nwn / 64 x nchan exceeds the membership table's bound (2^26 entries)"; return MONORTM_EARG; }
+    if (view_start[0] != 0 || view_start[nview] != npath) { c->err = "view_start[0] must be 0 and view_start[nview] must be npath"; return MONORTM_EARG; }
+    for (int v = 0; v < nview; v++)
+        if (view_start[v + 1] < view_start[v]) { c->err = "view_start must not decrease (view " + std::to_string(v) + ")"; return MONORTM_EARG; }
+    for (int j = 0; j < npath; j++)
+        if (!std::isfinite(wpath[j])) { c->err = "wpath[" + std::to_string(j) + "] is not finite"; return MONORTM_EARG; }
+    for (int i = 0; i < nwn; i++) {
+        if (chan[i] < -1 || chan[i] >= nchan) { c->err = "chan[" + std::to_string(i) + "] outside -1..nchan-1"; return MONORTM_EARG; }
+        if (!std::isfinite(wchan[i])) { c->err = "wchan[" + std::to_string(i) + "] is not finite"; return MONORTM_EARG; }
+    }
+    return MONORTM_OK;
+}
+
+// One device's copy of a checked operator: wpath, the members' weights, view_start, and per block of 64 wavenumbers the members of every
+// channel in ascending wavenumber (mstart [nblk][nchan + 1] into mlane / mw) - what rtm_obs_jac_kernel's owner lanes walk.
+int obs_upload(Ctx *c, Ctx::Obs &ob, const int *view_start, const double *wpath, const int *chan, const double *wchan) {
+    const int nblk = (ob.nwn + 63) / 64, nchan = ob.nchan;
+    std::vector<int> mstart((size_t)nblk * (nchan + 1)), mlane;
+    std::vector<double> mw;
+    std::vector<int> cnt(nchan + 1);
+    for (int b = 0; b < nblk; b++) {
+        const int i0 = b * 64, i1 = std::min(ob.nwn, i0 + 64);
+        std::fill(cnt.begin(), cnt.end(), 0);
+        for (int i = i0; i < i1; i++)
+            if (chan[i] >= 0) cnt[chan[i] + 1]++;
+        int *ms = mstart.data() + (size_t)b * (nchan + 1);
+        ms[0] = (int)mlane.size();
+        for (int ch = 0; ch < nchan; ch++) ms[ch + 1] = ms[ch] + cnt[ch + 1];
+        mlane.resize(ms[nchan]);
+        mw.resize(ms[nchan]);
+        std::vector<int> fillp(ms, ms + nchan);
+        for (int i = i0; i < i1; i++)   // ascending wavenumber within every channel
+            if (chan[i] >= 0) {
+                const int at = fillp[chan[i]]++;
+                mlane[at] = i - i0;
+                mw[at] = wchan[i];
+            }
+    }
+    const size_t nm = std::max<size_t>(mlane.size(), 1);
+    Arena ar;
+    const size_t o_wp = ar.add(ob.npath * sizeof(double)), o_mw = ar.add(nm * sizeof(double)), o_vs = ar.add((ob.nview + 1) * sizeof(int)),
+                 o_ms = ar.add(mstart.size() * sizeof(int)), o_ml = ar.add(nm * sizeof(int));
+    std::vector<char> h(ar.size, 0);
+    memcpy(h.data() + o_wp, wpath, ob.npath * sizeof(double));
+    if (!mw.empty()) memcpy(h.data() + o_mw, mw.data(), mw.size() * sizeof(double));
+    memcpy(h.data() + o_vs, view_start, (ob.nview + 1) * sizeof(int));
+    memcpy(h.data() + o_ms, mstart.data(), mstart.size() * sizeof(int));
+    if (!mlane.empty()) memcpy(h.data() + o_ml, mlane.data(), mlane.size() * sizeof(int));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMalloc(&ob.dev, ar.size));
+    if (hipMemcpy(ob.dev, h.data(), ar.size, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(ob.dev);
+        ob.dev = nullptr;
+        c->err = "monortm_hip_obs_create: the copy of the operator's tables to the device failed";
+        return MONORTM_EHIP;
+    }
+    const char *d = static_cast<const char *>(ob.dev);
+    ob.wpath = reinterpret_cast<const double *>(d + o_wp);
+    ob.mw = reinterpret_cast<const double *>(d + o_mw);
+    ob.view_start = reinterpret_cast<const int *>(d + o_vs);
+    ob.mstart = reinterpret_cast<const int *>(d + o_ms);
+    ob.mlane = reinterpret_cast<const int *>(d + o_ml);
+    return MONORTM_OK;
+}
+
+void obs_args(RtmObsJacArgs &a, const Ctx::Obs &ob) {
+    a.nview = ob.nview; a.nchan = ob.nchan;
+    a.view_start = ob.view_start; a.wpath = ob.wpath; a.mstart = ob.mstart; a.mlane = ob.mlane; a.mw = ob.mw;
+}
+
+// monortm_hip_rtm_obs_jac_dev with the element size of the outputs as an argument: the host entry of a real_kind = 4 context has the
+// kernel accumulate in double and rounds once, when it unpacks
+int rtm_obs_jac_dev_impl(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
+                         const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path,
+                         const void *emiss, const void *reflc, int obs, void *Y, void *K_T, void *K_TZ, void *K_SFC, int out_kind,
+                         void *stream) {
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !Y || !K_T || !K_TZ || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
+    if (int rcd = check_device(c)) return rcd;
+    RtmObsJacArgs a{};
+    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = c->real_kind;
+    a.sfc_per_path = sfc_per_path;
+    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    a.Y = Y; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
+    a.errflag = c->errflag;
+    obs_args(a, *ob);
+    launch_rtm_obs_jac(a, false, out_kind, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+// double -> the context's REAL kind, rounded once (real_kind = 4), or a plain copy
+void obs_unpack(void *dst, const char *src, size_t n, int real_kind) {
+    if (real_kind == 8) { memcpy(dst, src, n * 8); return; }
+    const double *s = reinterpret_cast<const double *>(src);
+    float *d = static_cast<float *>(dst);
+    for (size_t i = 0; i < n; i++) d[i] = (float)s[i];
+}
+
+// One device's share of the host entries: the staging slots of the Jacobian entries (8-11).  The arguments are those the entry points
+// have checked for the whole call; obs is the operator's handle on THIS context.
+int rtm_obs_jac_host(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
+                     const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path, const void *emiss,
+                     const void *reflc, int obs, void *Y, void *K_T, void *K_TZ, void *K_SFC, std::function<int()> *defer) {
+    HIPCHK(c, hipSetDevice(c->device));
+    Ctx::Obs *ob = obs_find(c, obs);
+    if (!ob) return obs_bad_handle(c);
+    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn, ppw = pw * npath;
+    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_tz = (size_t)nprof * (nlay_max + 1) * d,
+                 b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d, b_sfc = (sfc_per_path ? ppw : pw) * d;
+    const size_t n_y = (size_t)nprof * ob->nview * ob->nchan, n_k = n_y * nlay_max, n_kz = n_y * (nlay_max + 1);   // elements, held as double
+    Arena in, out;
+    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_T = in.add(b_l), i_TZ = in.add(b_tz), i_O = in.add(b_o),
+                 i_f = in.add(b_f), i_ts = in.add(b_p), i_em = in.add(b_sfc), i_rf = in.add(b_sfc);
+    const size_t o_y = out.add(n_y * 8), o_kt = out.add(n_k * 8), o_ktz = out.add(n_kz * 8), o_ks = out.add(3 * n_y * 8);
+    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
+    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
+    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
+    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
+    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
+    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
+    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_T, T, b_l);
+    memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_O, O, b_o); memcpy(h + i_f, path, b_f); memcpy(h + i_ts, tmpsfc, b_p);
+    memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
+    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
+    int rc = rtm_obs_jac_dev_impl(c, nprof, npath, nwn, (double *)(dv + i_wn), (int *)(dv + i_nl), nlay_max, (int *)(dv + i_irt), quantity,
+                                  dv + i_T, dv + i_TZ, dv + i_O, dv + i_f, dv + i_ts, sfc_per_path, dv + i_em, dv + i_rf, obs, dz + o_y,
+                                  dz + o_kt, dz + o_ktz, dz + o_ks, 8, c->hs);
+    if (rc) return rc;
+    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs));
+    const int rk = c->real_kind;
+    auto complete = [=]() mutable -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->hs));
+        const char *ho = static_cast<const char *>(hout);
+        obs_unpack(Y, ho + o_y, n_y, rk); obs_unpack(K_T, ho + o_kt, n_k, rk); obs_unpack(K_TZ, ho + o_ktz, n_kz, rk);
+        obs_unpack(K_SFC, ho + o_ks, 3 * n_y, rk);
+        return MONORTM_OK;
+    };
+    if (defer) { *defer = complete; return MONORTM_OK; }
+    return complete();
+}
+
+int obs_jac_host(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
+                 const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
+                 double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity,
+                 int njac, const int *jac_mol, int npath, const void *path, int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ,
+                 void *K_W, void *K_CLW, void *K_SFC, std::function<int()> *defer) {
+    HIPCHK(c, hipSetDevice(c->device));
+    Ctx::Obs *ob = obs_find(c, obs);
+    if (!ob) return obs_bad_handle(c);
+    const size_t npl = (size_t)nprof * nlay_max, d = 8, pw = (size_t)nprof * nwn, ppw = pw * npath;
+    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_w = npl * nmol * d,
+                 b_tz = (size_t)nprof * (nlay_max + 1) * d, b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d,
+                 b_sfc = (sfc_per_path ? ppw : pw) * d;
+    const size_t b_y = (size_t)nprof * ob->nview * ob->nchan * d, b_k = b_y * nlay_max, b_kz = b_y * (nlay_max + 1), b_kw = b_k * njac;
+    Arena in, out;
+    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_P = in.add(b_l), i_T = in.add(b_l), i_C = in.add(b_l),
+                 i_W = in.add(b_w), i_B = in.add(b_l), i_TZ = in.add(b_tz), i_f = in.add(b_f), i_ts = in.add(b_p), i_em = in.add(b_sfc),
+                 i_rf = in.add(b_sfc);
+    const size_t o_O = out.add(b_o), o_y = out.add(b_y), o_kt = out.add(b_k), o_ktz = out.add(b_kz), o_kw = out.add(b_kw), o_kc = out.add(b_k),
+                 o_ks = out.add(3 * b_y);
+    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
+    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
+    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
+    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
+    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
+    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
+    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_P, P, b_l); memcpy(h + i_T, T, b_l);
+    memcpy(h + i_C, CLW, b_l); memcpy(h + i_W, WKL, b_w); memcpy(h + i_B, WBRODL, b_l); memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_f, path, b_f);
+    memcpy(h + i_ts, tmpsfc, b_p); memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
+    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
+    const double ends[2] = {wn[0], wn[nwn - 1]};
+    int rc = monortm_hip_obs_jacobian_dev(c, nprof, nwn, (double *)(dv + i_wn), dvset, (int *)(dv + i_nl), nlay_max, nmol, dv + i_P, dv + i_T,
+                                          dv + i_C, dv + i_W, dv + i_B, cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)(dv + i_irt), dv + i_TZ,
+                                          dv + i_ts, dv + i_em, dv + i_rf, quantity, njac, jac_mol, npath, dv + i_f, sfc_per_path, obs, dz + o_O,
+                                          dz + o_y, dz + o_kt, dz + o_ktz, njac ? dz + o_kw : nullptr, dz + o_kc, dz + o_ks, ends, c->hs);
+    if (rc) return rc;
+    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs, c->errflag, c->errflag_host));
+    auto complete = [=]() mutable -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->hs));
+        if (int rcf = decode_flag(c, *c->errflag_host, c->hs)) return rcf;
+        const char *ho = static_cast<const char *>(hout);
+        memcpy(O, ho + o_O, b_o); memcpy(Y, ho + o_y, b_y); memcpy(K_T, ho + o_kt, b_k); memcpy(K_TZ, ho + o_ktz, b_kz);
+        memcpy(K_CLW, ho + o_kc, b_k); memcpy(K_SFC, ho + o_ks, 3 * b_y);
+        if (njac) memcpy(K_W, ho + o_kw, b_kw);
+        return MONORTM_OK;
+    };
+    if (defer) { *defer = complete; return MONORTM_OK; }
+    return complete();
+}
+}  // namespace
+
+extern "C" {
+
+int monortm_hip_obs_create(void *ctx, int npath, int nwn, int nview, int nchan, const int *view_start, const double *wpath, const int *chan,
+                           const double *wchan, int *handle) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!handle) { c->err = "null handle pointer"; return MONORTM_EARG; }
+    *handle = 0;
+    if (int rc = obs_check(c, npath, nwn, nview, nchan, view_start, wpath, chan, wchan)) return rc;
+    int slot = -1;
+    for (int i = 0; i < Ctx::kMaxObs && slot < 0; i++)
+        if (!c->obs[i].handle) slot = i;
+    if (slot < 0) { c->err = "all " + std::to_string(Ctx::kMaxObs) + " measurement operators of the context are in use: destroy one"; return MONORTM_EARG; }
+    DeviceGuard guard;
+    Ctx::Obs ob;
+    ob.npath = npath; ob.nwn = nwn; ob.nview = nview; ob.nchan = nchan;
+    if (!c->shards.empty()) {
+        for (Ctx *sh : c->shards) {
+            int hs = 0;
+            const int rc = monortm_hip_obs_create(sh, npath, nwn, nview, nchan, view_start, wpath, chan, wchan, &hs);
+            if (rc) {
+                c->err = "device " + std::to_string(sh->device) + ": " + sh->err;
+                for (size_t g = 0; g < ob.shard.size(); g++) monortm_hip_obs_destroy(c->shards[g], ob.shard[g]);
+                return rc;
+            }
+            ob.shard.push_back(hs);
+        }
+    } else if (int rc = obs_upload(c, ob, view_start, wpath, chan, wchan)) {
+        return rc;
+    }
+    // a handle is never given out twice in a process: a stale one and one of another context are both told apart
+    static std::atomic<unsigned> seq{0};
+    const unsigned q = seq.fetch_add(1) % 0x3ffffffu + 1;
+    ob.handle = (int)(q * Ctx::kMaxObs + slot);
+    c->obs[slot] = ob;
+    *handle = ob.handle;
+    return MONORTM_OK;
+}
+
+int monortm_hip_obs_destroy(void *ctx, int handle) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    Ctx::Obs *ob = obs_find(c, handle);
+    if (!ob) return obs_bad_handle(c);
+    DeviceGuard guard;
+    for (size_t g = 0; g < ob->shard.size(); g++) monortm_hip_obs_destroy(c->shards[g], ob->shard[g]);
+    if (ob->dev) {
+        hipSetDevice(c->device);
+        hipDeviceSynchronize();   // no launch that reads the tables is still in flight
+        hipFree(ob->dev);
+    }
+    *ob = Ctx::Obs();
+    return MONORTM_OK;
+}
+
+int monortm_hip_rtm_obs_jac_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                                int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc,
+                                int sfc_per_path, const void *emiss, const void *reflc, int obs, void *Y, void *K_T, void *K_TZ, void *K_SFC,
+                                void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    return rtm_obs_jac_dev_impl(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, obs,
+                                Y, K_T, K_TZ, K_SFC, c->real_kind, stream);
+}
+
+// MODM of the base and the 2 (1 + njac) perturbed states ONCE (jac_states), then one launch of the contracting adjoint
+int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                                 const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                                 double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                                 const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
+                                 int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_SFC,
+                                 const double *wn_ends, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (c->real_kind != 8) { c->err = "monortm_hip_obs_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !Y ||
+        !K_T || !K_TZ || !K_CLW || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
+    if (int rcd = check_device(c)) return rcd;
+    double *xO = nullptr;
+    size_t st = 0;
+    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, njac,
+                            jac_mol, O, wn_ends, s, &xO, &st))
+        return rc;
+    RtmObsJacArgs a{};
+    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = 8; a.njac = njac;
+    a.sfc_per_path = sfc_per_path;
+    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    a.Y = Y; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC; a.K_W = K_W; a.K_CLW = K_CLW;
+    a.Opert = xO + st;
+    a.state_stride = st;
+    a.dt = c->opt.jac_dt;
+    a.dlnw = c->opt.jac_dlnw;
+    a.errflag = c->errflag;
+    obs_args(a, *ob);
+    launch_rtm_obs_jac(a, true, 8, s);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+int monortm_hip_rtm_obs_jac(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                            int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path,
+                            const void *emiss, const void *reflc, int obs, void *Y, void *K_T, void *K_TZ, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    DeviceGuard guard;
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !Y || !K_T || !K_TZ || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
+    // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
+    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
+    if (c->shards.empty())
+        return rtm_obs_jac_host(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, obs, Y,
+                                K_T, K_TZ, K_SFC, nullptr);
+    const int G = (int)c->shards.size();
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
+    const size_t f = l * npath, vs = sfc_per_path ? v * npath : v, y = (size_t)ob->nview * ob->nchan * d;
+    std::vector<std::function<int()>> fin(G);
+    int rc = MONORTM_OK;
+    for (int g = 0; g < G; g++) {
+        int p0, n;
+        shard_block(nprof, G, g, &p0, &n);
+        if (n < 1) continue;
+        Ctx *s = c->shards[g];
+        const int r = rtm_obs_jac_host(s, n, npath, nwn, wn, nlay + p0, nlay_max, irt + p0, quantity, off(T, p0 * l), off(TZ, p0 * (l + d)),
+                                       off(O, p0 * w), off(path, p0 * f), off(tmpsfc, p0 * d), sfc_per_path, off(emiss, p0 * vs),
+                                       off(reflc, p0 * vs), ob->shard[g], off(Y, p0 * y), off(K_T, p0 * y * nlay_max),
+                                       off(K_TZ, p0 * y * (nlay_max + 1)), off(K_SFC, p0 * 3 * y), &fin[g]);
+        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
+    }
+    for (int g = 0; g < G; g++)
+        if (fin[g]) {
+            const int r = fin[g]();
+            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
+        }
+    return rc;
+}
+
+int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                             const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                             double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                             const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
+                             int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (c->real_kind != 8) { c->err = "monortm_hip_obs_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
+    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !Y ||
+        !K_T || !K_TZ || !K_CLW || !K_SFC) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    DeviceGuard guard;
+    // the whole call is checked before the first device is touched: a refusal launches nothing anywhere
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
+    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
+    if (int rc = jac_check_states(c, nprof, nwn, wn, nlay, nlay_max, T)) return rc;
+    if (c->shards.empty())
+        return obs_jac_host(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt, TZ,
+                            tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, obs, O, Y, K_T, K_TZ, K_W, K_CLW, K_SFC,
+                            nullptr);
+    const int G = (int)c->shards.size();
+    const size_t d = 8, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
+    const size_t f = l * npath, vs = sfc_per_path ? v * npath : v, y = (size_t)ob->nview * ob->nchan * d, yk = y * nlay_max;
+    std::vector<std::function<int()>> fin(G);
+    int rc = MONORTM_OK;
+    for (int g = 0; g < G; g++) {
+        int p0, n;
+        shard_block(nprof, G, g, &p0, &n);
+        if (n < 1) continue;
+        Ctx *s = c->shards[g];
+        const int r = obs_jac_host(s, n, nwn, wn, dvset, nlay + p0, nlay_max, nmol, off(P, p0 * l), off(T, p0 * l), off(CLW, p0 * l),
+                                   off(WKL, p0 * l * nmol), off(WBRODL, p0 * l), cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt + p0,
+                                   off(TZ, p0 * (l + d)), off(tmpsfc, p0 * d), off(emiss, p0 * vs), off(reflc, p0 * vs), quantity, njac, jac_mol,
+                                   npath, off(path, p0 * f), sfc_per_path, ob->shard[g], off(O, p0 * w), off(Y, p0 * y), off(K_T, p0 * yk),
+                                   off(K_TZ, p0 * (yk + y)), njac ? off(K_W, p0 * yk * njac) : nullptr, off(K_CLW, p0 * yk), off(K_SFC, p0 * 3 * y),
+                                   &fin[g]);
         if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
     }
     for (int g = 0; g < G; g++)

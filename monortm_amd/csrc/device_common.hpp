@@ -239,6 +239,25 @@ struct RtmScanJacArgs {
     double dt, dlnw;
     int *errflag;
 };
+// Channel- and beam-averaged Jacobians of path scans (rtm_obs_jac_kernel.hip): the inputs of RtmScanJacArgs and the
+// device tables of a measurement operator (monortm_hip_obs_create, checked on the host): view_start [nview + 1] (the paths of view v are
+// view_start[v] .. view_start[v + 1] - 1), wpath [npath]; per block b of 64 wavenumbers the members of every channel, ascending in
+// wavenumber: mstart [nblk][nchan + 1] into mlane (lane of the member within its block) and mw (its wchan).  Outputs Y [nprof][nview][nchan],
+// K_T, K_CLW [nprof][nview][nlay_max][nchan], K_TZ [nprof][nview][nlay_max + 1][nchan], K_SFC [nprof][nview][3][nchan],
+// K_W [nprof][nview][nlay_max][njac][nchan].
+struct RtmObsJacArgs {
+    int nprof, npath, nwn, nlay_max, quantity, real_kind, njac, sfc_per_path, nview, nchan;
+    const double *wn;
+    const void *T, *TZ, *O, *path, *tmpsfc, *emiss, *reflc;
+    const int *nlay, *irt;
+    const int *view_start, *mstart, *mlane;
+    const double *wpath, *mw;
+    void *Y, *K_T, *K_TZ, *K_SFC, *K_W, *K_CLW;
+    const void *Opert;
+    size_t state_stride;   // elements of one state's O: nprof x nlay_max x nwn
+    double dt, dlnw;
+    int *errflag;
+};
 // the MODM inputs of the base (state 0) and the perturbed states, [nstate][nprof][nlay_max](x nmol), real_kind 8
 struct JacPerturbArgs {
     int nstate, nprof, nlay_max, nmol;
@@ -431,5 +450,8 @@ void launch_jac_perturb(const JacPerturbArgs &a, hipStream_t s);
 void launch_rtm_jac(const RtmJacArgs &a, bool full, hipStream_t s);
 // rtm_scan_jac_kernel.hip (full = FULL instantiation, real_kind 8)
 void launch_rtm_scan_jac(const RtmScanJacArgs &a, bool full, hipStream_t s);
+// rtm_obs_jac_kernel.hip (full = FULL instantiation, real_kind 8; out_kind: element size of the outputs - 8 with a.real_kind = 4 is the
+// host entry's double accumulation)
+void launch_rtm_obs_jac(const RtmObsJacArgs &a, bool full, int out_kind, hipStream_t s);
 
 }  // namespace monortm_dev
