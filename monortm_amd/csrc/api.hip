@@ -77,13 +77,16 @@ struct Ctx {
     size_t osum_elems = 0;
     DevXsec xs{};             // cross-section tables (monortm_hip_xsec_tables); xs_buf holds them, replaced as a whole
     std::vector<void *> xs_buf;
-    // staging buffers of the host-buffer entry points, one per argument, grown on demand and kept: a caller that loops
-    // over profiles (the reference's driver does) pays for device allocations once, not per call
+    // staging arenas of the host-buffer entry points (HostCall), grown on demand and kept: a caller that loops over profiles (the
+    // reference's driver does) pays for device allocations once, not per call.  Twelve slots = three groups of four (pinned host
+    // input arena, device input arena, pinned host output arena, device output arena; even slots are the pinned ones): 0-3 MODM, 4-7
+    // RTM and the path scans, 8-11 every Jacobian entry - so that lastO, which points into slots 2 and 3, stays valid across a
+    // Jacobian call made between a MODM and an RTM call
     struct Stage {
         void *p = nullptr;
         size_t bytes = 0;
     };
-    Stage stage[12];  // modm: host in, device in, host out, device out; rtm: the same four; the Jacobian entries: the same four
+    Stage stage[12];
     // monortm_hip_jacobian_dev: the MODM inputs and optical depths of the base and the perturbed states, and the outputs of MODM
     // that the Jacobian does not use, grown on demand and kept (a second call of the same shapes allocates nothing)
     void *jac_ws = nullptr;
@@ -312,15 +315,18 @@ struct Arena {  // layout helper: 256-byte aligned pieces of one buffer
         return off;
     }
 };
-struct HostClock {  // phase timer of a host-buffer call (only when MONORTM_HOST_TIMING=1)
-    Ctx *c;
-    int k;
+struct HostClock {  // phase timer of a host-buffer call (only when MONORTM_HOST_TIMING=1, and for the entries that have a row of Ctx::ht)
+    Ctx *c = nullptr;
+    int k = -1;
     std::chrono::steady_clock::time_point t;
-    HostClock(Ctx *c_, int k_) : c(c_), k(k_) {
-        if (c->host_timing) { t = std::chrono::steady_clock::now(); c->ht_calls[k]++; }
+    void start(Ctx *c_, int k_) {
+        if (k_ < 0 || !c_->host_timing) return;
+        c = c_; k = k_;
+        t = std::chrono::steady_clock::now();
+        c->ht_calls[k]++;
     }
     void mark(int phase) {
-        if (!c->host_timing) return;
+        if (!c) return;
         const auto n = std::chrono::steady_clock::now();
         c->ht[k][phase] += std::chrono::duration<double>(n - t).count();
         t = n;
@@ -357,140 +363,7 @@ int decode_flag(Ctx *c, int flag, hipStream_t s) {
 }  // namespace
 
 namespace {
-// One device's share of a host-buffer MODM call.  With `defer` the call returns once everything is enqueued on the
-// context's stream and *defer completes it (wait, error flags, unpack): a multi-device context enqueues on every device
-// before it waits for the first.
-static int modm_host(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
-                     int nmol, const void *P, const void *T, const void *CLW, const void *WKL,
-                     const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd,
-                     int ixsect, const void *XAMNT, void *ODXSEC, void *O, void *O_BY_MOL, void *OC, void *O_CLW,
-                     std::function<int()> *defer) {
-    void *ctx = c;
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !O || !O_BY_MOL || !OC || !O_CLW) { c->err = "null array argument"; return MONORTM_EARG; }
-    if (nprof < 1 || nwn < 1 || nlay_max < 1 || nmol < 1) { c->err = "bad nprof/nwn/nlay_max/nmol"; return MONORTM_EARG; }
-    for (int i = 1; i < nwn; i++)
-        if (!(wn[i] >= wn[i - 1])) { c->err = "wavenumbers must be ascending (the reference takes v1 = wn(1), v2 = wn(nwn), modm.f90:180-181)"; return MONORTM_EARG; }
-    // dvset /= 0: what the kernels rely on is the nearest grid index within +-1 (line_records) and the continuum at V1 + i dvset
-    // as the reference's own CONTNM call places it - so the bound is on the cumulative drift, not on consecutive differences: the
-    // reference's "sgl" driver forms WN(J) = V1 + (J-1)*DVSET with a REAL*4 product (src/monortm_sub.F90:287), which moves
-    // point J by up to 6e-8 J DVSET
-    if (dvset != 0.)
-        for (int i = 1; i < nwn; i++)
-            if (!(std::fabs(wn[i] - (wn[0] + i * dvset)) <= 0.25 * std::fabs(dvset))) { c->err = "dvset /= 0 promises the grid wn[i] = wn[0] + i dvset (COMMON /MANE/ DVSET of the reference driver)"; return MONORTM_EARG; }
-    for (int p = 0; p < nprof; p++)
-        if (nlay[p] < 1 || nlay[p] > nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
-    HIPCHK(c, hipSetDevice(c->device));
-    c->lastO.dev = nullptr;  // before any arena can move or fail to regrow: nothing may point into a freed arena afterwards
-    c->lastO.host = nullptr;
-    const double ends[2] = {wn[0], wn[nwn - 1]};
-    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind;
-    Arena in, out;
-    const size_t b_wn = nwn * sizeof(double), b_nl = nprof * sizeof(int), b_l = npl * d, b_w = npl * nmol * d;
-    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_nl), i_P = in.add(b_l), i_T = in.add(b_l), i_C = in.add(b_l), i_W = in.add(b_w),
-                 i_B = in.add(b_l);
-    const bool xs = ixsect == 1;
-    if (xs && (!XAMNT || !ODXSEC || c->xs.nxs < 1)) { c->err = "IXSECT = 1: XAMNT / ODXSEC / cross-section tables missing"; return MONORTM_EARG; }
-    const size_t b_xa = xs ? npl * (size_t)c->xs.nxs * d : 0, i_XA = xs ? in.add(b_xa) : 0;
-    const size_t b_o = npl * nwn * d, b_om = npl * nmol * nwn * d, b_oc = npl * MONORTM_NCONT * nwn * d;
-    const size_t o_O = out.add(b_o), o_OM = out.add(b_om), o_OC = out.add(b_oc), o_OL = out.add(b_o), o_OX = xs ? out.add(b_o) : 0;
-    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
-    HIPCHK(c, stage_get(c, 0, in.size, true, &hin));
-    HIPCHK(c, stage_get(c, 1, in.size, false, &din));
-    HIPCHK(c, stage_get(c, 2, out.size, true, &hout));
-    HIPCHK(c, stage_get(c, 3, out.size, false, &dout));
-    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
-    HostClock hc(c, 0);
-    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_nl); memcpy(h + i_P, P, b_l); memcpy(h + i_T, T, b_l);
-    memcpy(h + i_C, CLW, b_l); memcpy(h + i_W, WKL, b_w); memcpy(h + i_B, WBRODL, b_l);
-    if (xs) memcpy(h + i_XA, XAMNT, b_xa);
-    hc.mark(0);
-    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
-    int rc = monortm_hip_modm_xs_dev(ctx, nprof, nwn, (double *)(dv + i_wn), dvset, (int *)(dv + i_nl), nlay_max, nmol, dv + i_P, dv + i_T,
-                                     dv + i_C, dv + i_W, dv + i_B, cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect,
-                                     xs ? dv + i_XA : nullptr, xs ? dz + o_OX : nullptr, dz + o_O, dz + o_OM, dz + o_OC, dz + o_OL, ends, c->hs);
-    if (rc) return rc;
-    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs, c->errflag, c->errflag_host));
-    hc.mark(1);
-    auto complete = [=]() mutable -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->hs));
-        hc.mark(2);
-        if (int rcf = decode_flag(c, *c->errflag_host, c->hs)) return rcf;
-        const char *ho = static_cast<const char *>(hout);
-        memcpy(O, ho + o_O, b_o); memcpy(O_BY_MOL, ho + o_OM, b_om); memcpy(OC, ho + o_OC, b_oc); memcpy(O_CLW, ho + o_OL, b_o);
-        if (xs) memcpy(ODXSEC, ho + o_OX, b_o);
-        hc.mark(3);
-        c->lastO.dev = dz + o_O; c->lastO.host = ho + o_O; c->lastO.bytes = b_o;
-        c->lastO.nprof = nprof; c->lastO.nwn = nwn; c->lastO.nlay_max = nlay_max;
-        return MONORTM_OK;
-    };
-    if (defer) { *defer = complete; return MONORTM_OK; }
-    return complete();
-}
-
-
-
-static int rtm_host(Ctx *c, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
-                    int iout, const void *T, const void *TZ, const void *O, void *tmpsfc, const void *emiss,
-                    const void *reflc, void *RUP, void *RDN, void *TRTOT, void *RAD, void *TB, void *TMR,
-                    std::function<int()> *defer) {
-    void *ctx = c;
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !tmpsfc || !emiss || !reflc || !RUP || !RDN || !TRTOT || !RAD || !TB) { c->err = "null array argument"; return MONORTM_EARG; }
-    for (int p = 0; p < nprof; p++)
-        if (nlay[p] < 1 || nlay[p] > nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
-    if (nprof < 1 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn;
-    Arena in, out;
-    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_tz = (size_t)nprof * (nlay_max + 1) * d,
-                 b_o = npl * nwn * d, b_p = nprof * d, b_pw = pw * d;
-    // O straight from the preceding MODM call?  Then it is still on the device (see Ctx::lastO): no second upload
-    const bool resident = c->lastO.dev && c->lastO.nprof == nprof && c->lastO.nwn == nwn && c->lastO.nlay_max == nlay_max &&
-                          c->lastO.bytes == npl * nwn * d && memcmp(O, c->lastO.host, c->lastO.bytes) == 0;
-    if (resident) c->o_reused++;
-    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_T = in.add(b_l), i_TZ = in.add(b_tz),
-                 i_em = in.add(b_pw), i_rf = in.add(b_pw), i_ts = in.add(b_p), i_O = resident ? 0 : in.add(b_o);
-    // tmpsfc is in/out: it lives in the output arena and is seeded from the host before the launch
-    const size_t o_up = out.add(b_pw), o_dn = out.add(b_pw), o_tr = out.add(b_pw), o_rad = out.add(b_pw), o_tb = out.add(b_pw),
-                 o_tmr = out.add(b_pw), o_ts = out.add(b_p);
-    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
-    HIPCHK(c, stage_get(c, 4, in.size, true, &hin));
-    HIPCHK(c, stage_get(c, 5, in.size, false, &din));
-    HIPCHK(c, stage_get(c, 6, out.size, true, &hout));
-    HIPCHK(c, stage_get(c, 7, out.size, false, &dout));
-    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
-    HostClock hc(c, 1);
-    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_T, T, b_l);
-    memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_em, emiss, b_pw); memcpy(h + i_rf, reflc, b_pw); memcpy(h + i_ts, tmpsfc, b_p);
-    if (!resident) memcpy(h + i_O, O, b_o);
-    hc.mark(0);
-    // (tmpsfc is in/out: its piece of the input arena also seeds the output arena)
-    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs, nullptr, nullptr, dz + o_ts, h + i_ts, (b_p + 255) & ~size_t(255)));
-    if (iout != 1) HIPCHK(c, hipMemsetAsync(dz + o_tb, 0, b_pw, c->hs));
-    const void *dO = resident ? c->lastO.dev : static_cast<const void *>(dv + i_O);
-    int rc = monortm_hip_rtm_dev(ctx, nprof, nwn, (double *)(dv + i_wn), (int *)(dv + i_nl), nlay_max, (int *)(dv + i_irt), iout,
-                                 dv + i_T, dv + i_TZ, dO, dz + o_ts, dv + i_em, dv + i_rf, dz + o_up, dz + o_dn, dz + o_tr,
-                                 dz + o_rad, dz + o_tb, TMR ? dz + o_tmr : nullptr, c->hs);
-    if (rc) return rc;
-    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs));
-    hc.mark(1);
-    auto complete = [=]() mutable -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->hs));
-        hc.mark(2);
-        const char *ho = static_cast<const char *>(hout);
-        memcpy(RUP, ho + o_up, b_pw); memcpy(RDN, ho + o_dn, b_pw); memcpy(TRTOT, ho + o_tr, b_pw); memcpy(RAD, ho + o_rad, b_pw);
-        if (iout == 1) memcpy(TB, ho + o_tb, b_pw);
-        if (TMR) memcpy(TMR, ho + o_tmr, b_pw);
-        memcpy(tmpsfc, ho + o_ts, b_p);
-        hc.mark(3);
-        return MONORTM_OK;
-    };
-    if (defer) { *defer = complete; return MONORTM_OK; }
-    return complete();
-}
-
-// ---- path scans: the staging slots of rtm_host (4-7; the resident O of the last MODM call is in slot 3)
+// ---- path scans: what the scan entries check on host arguments
 constexpr int kScanMaxPaths = 16384;   // 4096 path tiles: inside the grid's z range
 int scan_check_args(Ctx *c, int nprof, int npath, int nwn, int nlay_max, int sfc_per_path) {
     if (nprof < 1 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
@@ -525,68 +398,20 @@ int scan_check_path(Ctx *c, int nprof, int npath, const int *nlay, int nlay_max,
     return MONORTM_OK;
 }
 
-// One device's share of a host-buffer scan.  The arguments are those monortm_hip_rtm_scan has checked (scan_check_args,
-// scan_check_path) for the whole call.
-static int rtm_scan_host(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int iout,
-                         const void *T, const void *TZ, const void *O, const void *path, void *tmpsfc, int sfc_per_path, const void *emiss,
-                         const void *reflc, void *RUP, void *RDN, void *TRTOT, void *RAD, void *TB, void *TMR, std::function<int()> *defer) {
-    void *ctx = c;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn, ppw = pw * npath;
-    Arena in, out;
-    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_tz = (size_t)nprof * (nlay_max + 1) * d,
-                 b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d, b_sfc = (sfc_per_path ? ppw : pw) * d, b_out = ppw * d;
-    // O straight from the preceding MODM call?  Then it is still on the device (see Ctx::lastO): no second upload
-    const bool resident = c->lastO.dev && c->lastO.nprof == nprof && c->lastO.nwn == nwn && c->lastO.nlay_max == nlay_max &&
-                          c->lastO.bytes == npl * nwn * d && memcmp(O, c->lastO.host, c->lastO.bytes) == 0;
-    if (resident) c->o_reused_scan++;
-    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_T = in.add(b_l), i_TZ = in.add(b_tz), i_f = in.add(b_f),
-                 i_em = in.add(b_sfc), i_rf = in.add(b_sfc), i_ts = in.add(b_p), i_O = resident ? 0 : in.add(b_o);
-    const size_t o_up = out.add(b_out), o_dn = out.add(b_out), o_tr = out.add(b_out), o_rad = out.add(b_out), o_tb = out.add(b_out),
-                 o_tmr = out.add(b_out), o_ts = out.add(b_p);
-    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
-    HIPCHK(c, stage_get(c, 4, in.size, true, &hin));
-    HIPCHK(c, stage_get(c, 5, in.size, false, &din));
-    HIPCHK(c, stage_get(c, 6, out.size, true, &hout));
-    HIPCHK(c, stage_get(c, 7, out.size, false, &dout));
-    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
-    HostClock hc(c, 2);
-    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_T, T, b_l);
-    memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_f, path, b_f); memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
-    memcpy(h + i_ts, tmpsfc, b_p);
-    if (!resident) memcpy(h + i_O, O, b_o);
-    hc.mark(0);
-    // (tmpsfc is in/out: its piece of the input arena also seeds the output arena)
-    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs, nullptr, nullptr, dz + o_ts, h + i_ts, (b_p + 255) & ~size_t(255)));
-    if (iout != 1) HIPCHK(c, hipMemsetAsync(dz + o_tb, 0, b_out, c->hs));
-    const void *dO = resident ? c->lastO.dev : static_cast<const void *>(dv + i_O);
-    int rc = monortm_hip_rtm_scan_dev(ctx, nprof, npath, nwn, (double *)(dv + i_wn), (int *)(dv + i_nl), nlay_max, (int *)(dv + i_irt), iout,
-                                      dv + i_T, dv + i_TZ, dO, dv + i_f, dz + o_ts, sfc_per_path, dv + i_em, dv + i_rf, dz + o_up, dz + o_dn,
-                                      dz + o_tr, dz + o_rad, dz + o_tb, TMR ? dz + o_tmr : nullptr, c->hs);
-    if (rc) return rc;
-    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs));
-    hc.mark(1);
-    auto complete = [=]() mutable -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->hs));
-        hc.mark(2);
-        const char *ho = static_cast<const char *>(hout);
-        memcpy(RUP, ho + o_up, b_out); memcpy(RDN, ho + o_dn, b_out); memcpy(TRTOT, ho + o_tr, b_out); memcpy(RAD, ho + o_rad, b_out);
-        if (iout == 1) memcpy(TB, ho + o_tb, b_out);
-        if (TMR) memcpy(TMR, ho + o_tmr, b_out);
-        memcpy(tmpsfc, ho + o_ts, b_p);
-        hc.mark(3);
-        return MONORTM_OK;
-    };
-    if (defer) { *defer = complete; return MONORTM_OK; }
-    return complete();
+// ---- the Jacobian entries: what they check on host arguments
+int check_quantity(Ctx *c, int quantity) {
+    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    return MONORTM_OK;
 }
-
-// ---- the Jacobian entries on host buffers: one upload, the *_dev call, one download (staging slots 8-11, so that the resident O of
-// the last MODM call - Ctx::lastO, in slot 3 - stays valid across a Jacobian call)
+// the full Jacobians difference optical depths: double arrays only (entry: the public name the message gives)
+int need_real8(Ctx *c, const char *entry) {
+    if (c->real_kind == 8) return MONORTM_OK;
+    c->err = std::string(entry) + " needs a real_kind = 8 context (its differences of optical depths need double arrays)";
+    return MONORTM_EUNSUPPORTED;
+}
 int jac_check_args(Ctx *c, int nprof, int nwn, const int *nlay, int nlay_max, int quantity) {
     if (nprof < 1 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
-    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rcq = check_quantity(c, quantity)) return rcq;
     for (int p = 0; p < nprof; p++)
         if (nlay[p] < 1 || nlay[p] > nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
     return MONORTM_OK;
@@ -616,97 +441,6 @@ int jac_check_states(Ctx *c, int nprof, int nwn, const double *wn, const int *nl
             }
         }
     return MONORTM_OK;
-}
-
-static int rtm_jac_host(Ctx *c, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
-                        const void *T, const void *TZ, const void *O, const void *tmpsfc, const void *emiss, const void *reflc,
-                        void *RAD, void *TB, void *K_O, void *K_T, void *K_TZ, void *K_SFC, std::function<int()> *defer) {
-    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn;
-    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_tz = (size_t)nprof * (nlay_max + 1) * d,
-                 b_o = npl * nwn * d, b_p = nprof * d, b_pw = pw * d, b_tzw = b_tz * nwn;
-    Arena in, out;
-    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_T = in.add(b_l), i_TZ = in.add(b_tz), i_O = in.add(b_o),
-                 i_ts = in.add(b_p), i_em = in.add(b_pw), i_rf = in.add(b_pw);
-    const size_t o_rad = out.add(b_pw), o_tb = out.add(b_pw), o_ko = out.add(b_o), o_kt = out.add(b_o), o_ktz = out.add(b_tzw),
-                 o_ks = out.add(3 * b_pw);
-    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
-    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
-    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
-    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
-    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
-    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
-    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_T, T, b_l);
-    memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_O, O, b_o); memcpy(h + i_ts, tmpsfc, b_p); memcpy(h + i_em, emiss, b_pw);
-    memcpy(h + i_rf, reflc, b_pw);
-    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
-    int rc = monortm_hip_rtm_jac_dev(c, nprof, nwn, (double *)(dv + i_wn), (int *)(dv + i_nl), nlay_max, (int *)(dv + i_irt), quantity,
-                                     dv + i_T, dv + i_TZ, dv + i_O, dv + i_ts, dv + i_em, dv + i_rf, dz + o_rad, dz + o_tb, dz + o_ko,
-                                     dz + o_kt, dz + o_ktz, dz + o_ks, c->hs);
-    if (rc) return rc;
-    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs));
-    auto complete = [=]() mutable -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->hs));
-        const char *ho = static_cast<const char *>(hout);
-        memcpy(RAD, ho + o_rad, b_pw); memcpy(TB, ho + o_tb, b_pw); memcpy(K_O, ho + o_ko, b_o); memcpy(K_T, ho + o_kt, b_o);
-        memcpy(K_TZ, ho + o_ktz, b_tzw); memcpy(K_SFC, ho + o_ks, 3 * b_pw);
-        return MONORTM_OK;
-    };
-    if (defer) { *defer = complete; return MONORTM_OK; }
-    return complete();
-}
-
-static int jac_host(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
-                    const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl,
-                    double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc, const void *emiss,
-                    const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD, void *TB, void *K_T, void *K_TZ,
-                    void *K_W, void *K_CLW, void *K_O, void *K_SFC, std::function<int()> *defer) {
-    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
-    if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
-    if (int rc = jac_check_states(c, nprof, nwn, wn, nlay, nlay_max, T)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn;
-    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_w = npl * nmol * d,
-                 b_tz = (size_t)nprof * (nlay_max + 1) * d, b_o = npl * nwn * d, b_p = nprof * d, b_pw = pw * d, b_tzw = b_tz * nwn,
-                 b_kw = b_o * njac;
-    Arena in, out;
-    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_P = in.add(b_l), i_T = in.add(b_l), i_C = in.add(b_l),
-                 i_W = in.add(b_w), i_B = in.add(b_l), i_TZ = in.add(b_tz), i_ts = in.add(b_p), i_em = in.add(b_pw), i_rf = in.add(b_pw);
-    const size_t o_O = out.add(b_o), o_rad = out.add(b_pw), o_tb = out.add(b_pw), o_kt = out.add(b_o), o_ktz = out.add(b_tzw),
-                 o_kw = out.add(b_kw), o_kc = out.add(b_o), o_ko = K_O ? out.add(b_o) : 0, o_ks = out.add(3 * b_pw);
-    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
-    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
-    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
-    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
-    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
-    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
-    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_P, P, b_l); memcpy(h + i_T, T, b_l);
-    memcpy(h + i_C, CLW, b_l); memcpy(h + i_W, WKL, b_w); memcpy(h + i_B, WBRODL, b_l); memcpy(h + i_TZ, TZ, b_tz);
-    memcpy(h + i_ts, tmpsfc, b_p); memcpy(h + i_em, emiss, b_pw); memcpy(h + i_rf, reflc, b_pw);
-    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
-    const double ends[2] = {wn[0], wn[nwn - 1]};
-    int rc = monortm_hip_jacobian_dev(c, nprof, nwn, (double *)(dv + i_wn), dvset, (int *)(dv + i_nl), nlay_max, nmol, dv + i_P, dv + i_T,
-                                      dv + i_C, dv + i_W, dv + i_B, cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)(dv + i_irt), dv + i_TZ,
-                                      dv + i_ts, dv + i_em, dv + i_rf, quantity, njac, jac_mol, dz + o_O, dz + o_rad, dz + o_tb, dz + o_kt,
-                                      dz + o_ktz, njac ? dz + o_kw : nullptr, dz + o_kc, K_O ? dz + o_ko : nullptr, dz + o_ks, ends, c->hs);
-    if (rc) return rc;
-    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs, c->errflag, c->errflag_host));
-    auto complete = [=]() mutable -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->hs));
-        if (int rcf = decode_flag(c, *c->errflag_host, c->hs)) return rcf;
-        const char *ho = static_cast<const char *>(hout);
-        memcpy(O, ho + o_O, b_o); memcpy(RAD, ho + o_rad, b_pw); memcpy(TB, ho + o_tb, b_pw); memcpy(K_T, ho + o_kt, b_o);
-        memcpy(K_TZ, ho + o_ktz, b_tzw); memcpy(K_CLW, ho + o_kc, b_o); memcpy(K_SFC, ho + o_ks, 3 * b_pw);
-        if (njac) memcpy(K_W, ho + o_kw, b_kw);
-        if (K_O) memcpy(K_O, ho + o_ko, b_o);
-        return MONORTM_OK;
-    };
-    if (defer) { *defer = complete; return MONORTM_OK; }
-    return complete();
 }
 
 // The MODM part of a Jacobian call (monortm_hip_jacobian_dev, monortm_hip_scan_jacobian_dev): jac_perturb_kernel, then MODM of the base
@@ -775,102 +509,26 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
     return MONORTM_OK;
 }
 
-// ---- Jacobians of path scans on host buffers: the staging slots of the Jacobian entries (8-11).  The arguments
-// are those the entry points have checked for the whole call (scan_check_args, scan_check_path, the quantity).
-static int rtm_scan_jac_host(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
-                             int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path,
-                             const void *emiss, const void *reflc, void *RAD, void *TB, void *K_O, void *K_PATH, void *K_T, void *K_TZ,
-                             void *K_SFC, std::function<int()> *defer) {
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn, ppw = pw * npath;
-    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_tz = (size_t)nprof * (nlay_max + 1) * d,
-                 b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d, b_sfc = (sfc_per_path ? ppw : pw) * d, b_q = ppw * d,
-                 b_k = b_o * npath, b_kz = b_tz * npath * nwn;
-    Arena in, out;
-    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_T = in.add(b_l), i_TZ = in.add(b_tz), i_O = in.add(b_o),
-                 i_f = in.add(b_f), i_ts = in.add(b_p), i_em = in.add(b_sfc), i_rf = in.add(b_sfc);
-    const size_t o_rad = out.add(b_q), o_tb = out.add(b_q), o_ko = K_O ? out.add(b_k) : 0, o_kp = K_PATH ? out.add(b_k) : 0, o_kt = out.add(b_k),
-                 o_ktz = out.add(b_kz), o_ks = out.add(3 * b_q);
-    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
-    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
-    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
-    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
-    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
-    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
-    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_T, T, b_l);
-    memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_O, O, b_o); memcpy(h + i_f, path, b_f); memcpy(h + i_ts, tmpsfc, b_p);
-    memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
-    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
-    int rc = monortm_hip_rtm_scan_jac_dev(c, nprof, npath, nwn, (double *)(dv + i_wn), (int *)(dv + i_nl), nlay_max, (int *)(dv + i_irt), quantity,
-                                          dv + i_T, dv + i_TZ, dv + i_O, dv + i_f, dv + i_ts, sfc_per_path, dv + i_em, dv + i_rf, dz + o_rad,
-                                          dz + o_tb, K_O ? dz + o_ko : nullptr, K_PATH ? dz + o_kp : nullptr, dz + o_kt, dz + o_ktz, dz + o_ks,
-                                          c->hs);
-    if (rc) return rc;
-    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs));
-    auto complete = [=]() mutable -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->hs));
-        const char *ho = static_cast<const char *>(hout);
-        memcpy(RAD, ho + o_rad, b_q); memcpy(TB, ho + o_tb, b_q); memcpy(K_T, ho + o_kt, b_k); memcpy(K_TZ, ho + o_ktz, b_kz);
-        memcpy(K_SFC, ho + o_ks, 3 * b_q);
-        if (K_O) memcpy(K_O, ho + o_ko, b_k);
-        if (K_PATH) memcpy(K_PATH, ho + o_kp, b_k);
-        return MONORTM_OK;
-    };
-    if (defer) { *defer = complete; return MONORTM_OK; }
-    return complete();
+// What the full-Jacobian *_dev entries (monortm_hip_jacobian_dev, _scan_jacobian_dev, _obs_jacobian_dev) refuse first, and the chain
+// fields their adjoint launches share: the perturbed states' optical depths (jac_states) and the half-steps of the differences.
+int jac_full_check(Ctx *c, const char *entry, bool any_null, int nprof, int nwn, int nlay_max, int nmol, int quantity, int njac,
+                   const int *jac_mol, const void *K_W) {
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (int rc = need_real8(c, entry)) return rc;
+    if (any_null) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (int rc = check_quantity(c, quantity)) return rc;
+    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    return MONORTM_OK;
 }
-
-static int scan_jac_host(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
-                         const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl,
-                         double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc, const void *emiss,
-                         const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path, int sfc_per_path, void *O,
-                         void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_PATH, void *K_SFC,
-                         std::function<int()> *defer) {
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npl = (size_t)nprof * nlay_max, d = 8, pw = (size_t)nprof * nwn, ppw = pw * npath;
-    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_w = npl * nmol * d,
-                 b_tz = (size_t)nprof * (nlay_max + 1) * d, b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d,
-                 b_sfc = (sfc_per_path ? ppw : pw) * d, b_q = ppw * d, b_k = b_o * npath, b_kz = b_tz * npath * nwn, b_kw = b_k * njac;
-    Arena in, out;
-    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_P = in.add(b_l), i_T = in.add(b_l), i_C = in.add(b_l),
-                 i_W = in.add(b_w), i_B = in.add(b_l), i_TZ = in.add(b_tz), i_f = in.add(b_f), i_ts = in.add(b_p), i_em = in.add(b_sfc),
-                 i_rf = in.add(b_sfc);
-    const size_t o_O = out.add(b_o), o_rad = out.add(b_q), o_tb = out.add(b_q), o_kt = out.add(b_k), o_ktz = out.add(b_kz),
-                 o_kw = out.add(b_kw), o_kc = out.add(b_k), o_ko = K_O ? out.add(b_k) : 0, o_kp = K_PATH ? out.add(b_k) : 0,
-                 o_ks = out.add(3 * b_q);
-    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
-    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
-    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
-    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
-    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
-    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
-    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_P, P, b_l); memcpy(h + i_T, T, b_l);
-    memcpy(h + i_C, CLW, b_l); memcpy(h + i_W, WKL, b_w); memcpy(h + i_B, WBRODL, b_l); memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_f, path, b_f);
-    memcpy(h + i_ts, tmpsfc, b_p); memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
-    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
-    const double ends[2] = {wn[0], wn[nwn - 1]};
-    int rc = monortm_hip_scan_jacobian_dev(c, nprof, nwn, (double *)(dv + i_wn), dvset, (int *)(dv + i_nl), nlay_max, nmol, dv + i_P, dv + i_T,
-                                           dv + i_C, dv + i_W, dv + i_B, cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)(dv + i_irt), dv + i_TZ,
-                                           dv + i_ts, dv + i_em, dv + i_rf, quantity, njac, jac_mol, npath, dv + i_f, sfc_per_path, dz + o_O,
-                                           dz + o_rad, dz + o_tb, dz + o_kt, dz + o_ktz, njac ? dz + o_kw : nullptr, dz + o_kc,
-                                           K_O ? dz + o_ko : nullptr, K_PATH ? dz + o_kp : nullptr, dz + o_ks, ends, c->hs);
-    if (rc) return rc;
-    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs, c->errflag, c->errflag_host));
-    auto complete = [=]() mutable -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->hs));
-        if (int rcf = decode_flag(c, *c->errflag_host, c->hs)) return rcf;
-        const char *ho = static_cast<const char *>(hout);
-        memcpy(O, ho + o_O, b_o); memcpy(RAD, ho + o_rad, b_q); memcpy(TB, ho + o_tb, b_q); memcpy(K_T, ho + o_kt, b_k);
-        memcpy(K_TZ, ho + o_ktz, b_kz); memcpy(K_CLW, ho + o_kc, b_k); memcpy(K_SFC, ho + o_ks, 3 * b_q);
-        if (njac) memcpy(K_W, ho + o_kw, b_kw);
-        if (K_O) memcpy(K_O, ho + o_ko, b_k);
-        if (K_PATH) memcpy(K_PATH, ho + o_kp, b_k);
-        return MONORTM_OK;
-    };
-    if (defer) { *defer = complete; return MONORTM_OK; }
-    return complete();
+template <class Args>   // RtmJacArgs, RtmScanJacArgs, RtmObsJacArgs
+void jac_chain_args(Args &a, const Ctx *c, int njac, void *K_W, void *K_CLW, const double *xO, size_t st) {
+    a.real_kind = 8; a.njac = njac; a.K_W = K_W; a.K_CLW = K_CLW;
+    a.Opert = xO + st;
+    a.state_stride = st;
+    a.dt = c->opt.jac_dt;
+    a.dlnw = c->opt.jac_dlnw;
 }
 
 // ---- sharding of a host-buffer call over the devices of a multi-device context (monortm_hip_init_multi) ------------
@@ -882,8 +540,190 @@ void shard_block(int nprof, int G, int g, int *p0, int *n) {
     *p0 = std::min(nprof, g * per);
     *n = std::min(nprof, *p0 + per) - *p0;
 }
-const char *off(const void *p, size_t bytes) { return static_cast<const char *>(p) + bytes; }
-char *off(void *p, size_t bytes) { return static_cast<char *>(p) + bytes; }
+
+// double -> the context's REAL kind, rounded once (real_kind = 4), or a plain copy
+void obs_unpack(void *dst, const char *src, size_t n, int real_kind) {
+    if (real_kind == 8) { memcpy(dst, src, n * 8); return; }
+    const double *s = reinterpret_cast<const double *>(src);
+    float *d = static_cast<float *>(dst);
+    for (size_t i = 0; i < n; i++) d[i] = (float)s[i];
+}
+
+// ---- the arrays of a host-buffer call, declared ONCE ----------------------------------------------------
+// Every public host-buffer entry lists its array arguments here - host pointer, bytes per profile, direction - and run() does the
+// rest from that one list: it lays the pieces of one device's share out in the two arenas, packs ptr + p0 stride for n stride bytes,
+// uploads once, hands the entry's launch lambda the device address of every declared array, downloads once and, when the stream has
+// drained, unpacks to ptr + p0 stride.  A multi-device context runs one share per shard (shard_block), enqueues on every device before
+// it waits for the first, and reports the first error as "device N: ...".  A null pointer declares an absent array (the optional
+// outputs; the entries' own checks have refused a null anywhere else): no piece, and the launch lambda gets null for it.
+struct HostCall {
+    static constexpr int kMaxFields = 24;
+    enum Dir { IN, OUT, INOUT };
+    struct Field {
+        const void *in = nullptr;   // the caller's array: read (IN, INOUT) ...
+        void *out = nullptr;        // ... and written (OUT, INOUT)
+        size_t stride = 0;          // bytes per profile on the device; of a shared array: all of it
+        Dir dir = IN;
+        bool shared = false;        // the same for every profile (wn): never shifted, uploaded whole to every device
+        bool zeroed = false;        // output cleared on the device and NOT copied back (TB of an RTM call with iout /= 1)
+        bool widened = false;       // output held as double on the device, rounded once to the context's REAL kind when unpacked
+    };
+    // one share in flight: what finish() needs once everything is enqueued
+    struct Pending {
+        Ctx *s = nullptr;
+        int p0 = 0, n = 0;
+        char *hout = nullptr, *dout = nullptr;
+        size_t off[kMaxFields] = {0};   // the fields' pieces of the output arena
+        HostClock hc;
+    };
+    using PreFn = int (*)(const void *, Ctx *, int, int);
+    using LaunchFn = int (*)(const void *, Ctx *, int, int, char *const *);
+
+    Field f[kMaxFields];
+    int nf = 0;
+    int slot0;            // the first of the call's four staging slots (Ctx::stage)
+    int clock;            // row of Ctx::ht (MONORTM_HOST_TIMING), -1: an entry without phase marks
+    bool flag = false;    // the kernels' error flag comes back with the output arena and is decoded (decode_flag)
+    // the total optical depths O and Ctx::lastO: a MODM call leaves them resident, an RTM / scan call reads them where it finds them
+    enum { O_NONE, O_LEAVES, O_READS } o_role = O_NONE;
+    int o_field = -1, o_nwn = 0, o_nlay_max = 0;
+    long long Ctx::*o_counter = nullptr;
+
+    HostCall(int slot0_, int clock_ = -1) : slot0(slot0_), clock(clock_) {}
+    int add(const void *in, void *out, size_t stride, Dir dir) {
+        const int i = std::min(nf++, kMaxFields - 1);   // (run() refuses a call that declared more than kMaxFields)
+        f[i].in = in; f[i].out = out; f[i].stride = stride; f[i].dir = dir;
+        return i;
+    }
+    int in(const void *p, size_t per_profile) { return add(p, nullptr, per_profile, IN); }
+    int in_shared(const void *p, size_t bytes) { const int i = add(p, nullptr, bytes, IN); f[i].shared = true; return i; }
+    int out(void *p, size_t per_profile) { return add(nullptr, p, per_profile, OUT); }
+    int inout(void *p, size_t per_profile) { return add(p, p, per_profile, INOUT); }
+    int out_zeroed(void *p, size_t per_profile) { const int i = out(p, per_profile); f[i].zeroed = true; return i; }
+    int out_widened(void *p, size_t elems_per_profile) { const int i = out(p, elems_per_profile * 8); f[i].widened = true; return i; }
+    void leaves_O(int field, int nwn, int nlay_max) { o_role = O_LEAVES; o_field = field; o_nwn = nwn; o_nlay_max = nlay_max; }
+    void reads_O(int field, int nwn, int nlay_max, long long Ctx::*counter) {
+        o_role = O_READS; o_field = field; o_nwn = nwn; o_nlay_max = nlay_max; o_counter = counter;
+    }
+
+    bool absent(const Field &x) const { return x.dir == IN ? !x.in : !x.out; }
+    size_t bytes(const Field &x, int n) const { return x.shared ? x.stride : (size_t)n * x.stride; }
+    // the caller's array from profile p0 on (an input; host_out: an output, whose elements may be narrower than the device's)
+    const char *host(int i, int p0) const { return static_cast<const char *>(f[i].in) + (f[i].shared ? 0 : (size_t)p0 * f[i].stride); }
+    char *host_out(const Field &x, int p0, int real_kind) const {
+        return static_cast<char *>(x.out) + (size_t)p0 * (x.widened ? x.stride / 8 * (size_t)real_kind : x.stride);
+    }
+
+    // One device's share, profiles [p0, p0 + n): returns once everything is enqueued on the context's stream; finish() completes it.
+    int enqueue(Ctx *s, int g, int p0, int n, const void *pre_obj, PreFn pre, const void *launch_obj, LaunchFn launch, Pending *pd) const {
+        HIPCHK(s, hipSetDevice(s->device));
+        if (int rc = pre(pre_obj, s, p0, n)) return rc;
+        // O straight from the preceding MODM call?  Then it is still on the device (see Ctx::lastO): no second upload
+        bool resident = false;
+        if (o_role == O_READS) {
+            const size_t b = bytes(f[o_field], n);
+            resident = s->lastO.dev && s->lastO.nprof == n && s->lastO.nwn == o_nwn && s->lastO.nlay_max == o_nlay_max && s->lastO.bytes == b &&
+                       memcmp(host(o_field, p0), s->lastO.host, b) == 0;
+            if (resident) (s->*o_counter)++;
+        }
+        // an in/out array lives in the output arena and is seeded from its piece of the input arena (move_arena's second piece)
+        Arena in, out;
+        size_t ioff[kMaxFields] = {0};
+        int seed = -1;
+        for (int i = 0; i < nf; i++) {
+            if (absent(f[i])) continue;
+            if (f[i].dir != OUT && !(resident && i == o_field)) ioff[i] = in.add(bytes(f[i], n));
+            if (f[i].dir != IN) pd->off[i] = out.add(bytes(f[i], n));
+            if (f[i].dir == INOUT) seed = i;
+        }
+        void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
+        HIPCHK(s, stage_get(s, slot0, in.size, true, &hin));
+        HIPCHK(s, stage_get(s, slot0 + 1, in.size, false, &din));
+        HIPCHK(s, stage_get(s, slot0 + 2, out.size, true, &hout));
+        HIPCHK(s, stage_get(s, slot0 + 3, out.size, false, &dout));
+        char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
+        pd->hc.start(s, clock);
+        char *dev[kMaxFields] = {nullptr};
+        for (int i = 0; i < nf; i++) {
+            if (absent(f[i])) continue;
+            const bool packed = f[i].dir != OUT && !(resident && i == o_field);
+            if (packed) memcpy(h + ioff[i], host(i, p0), bytes(f[i], n));
+            dev[i] = f[i].dir != IN ? dz + pd->off[i] : (packed ? dv + ioff[i] : static_cast<char *>(const_cast<void *>(s->lastO.dev)));
+        }
+        pd->hc.mark(0);
+        if (seed >= 0)
+            HIPCHK(s, move_arena(din, hin, in.size, hipMemcpyHostToDevice, s->hs, nullptr, nullptr, dev[seed], h + ioff[seed],
+                                 (bytes(f[seed], n) + 255) & ~size_t(255)));
+        else HIPCHK(s, move_arena(din, hin, in.size, hipMemcpyHostToDevice, s->hs));
+        for (int i = 0; i < nf; i++)
+            if (f[i].zeroed && !absent(f[i])) HIPCHK(s, hipMemsetAsync(dev[i], 0, bytes(f[i], n), s->hs));
+        if (int rc = launch(launch_obj, s, g, n, dev)) return rc;
+        HIPCHK(s, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, s->hs, flag ? s->errflag : nullptr, flag ? s->errflag_host : nullptr));
+        pd->hc.mark(1);
+        pd->s = s; pd->p0 = p0; pd->n = n;
+        pd->hout = static_cast<char *>(hout); pd->dout = dz;
+        return MONORTM_OK;
+    }
+
+    // wait for the share's stream, decode the error flag where the entry asks for it, unpack into the caller's arrays
+    int finish(Pending &pd) const {
+        Ctx *s = pd.s;
+        HIPCHK(s, hipSetDevice(s->device));
+        HIPCHK(s, hipStreamSynchronize(s->hs));
+        pd.hc.mark(2);
+        if (flag)
+            if (int rc = decode_flag(s, *s->errflag_host, s->hs)) return rc;
+        for (int i = 0; i < nf; i++) {
+            if (absent(f[i]) || f[i].dir == IN || f[i].zeroed) continue;
+            char *dst = host_out(f[i], pd.p0, s->real_kind);
+            if (f[i].widened) obs_unpack(dst, pd.hout + pd.off[i], bytes(f[i], pd.n) / 8, s->real_kind);
+            else memcpy(dst, pd.hout + pd.off[i], bytes(f[i], pd.n));
+        }
+        pd.hc.mark(3);
+        if (o_role == O_LEAVES) {
+            const size_t o = pd.off[o_field];
+            s->lastO.dev = pd.dout + o; s->lastO.host = pd.hout + o; s->lastO.bytes = bytes(f[o_field], pd.n);
+            s->lastO.nprof = pd.n; s->lastO.nwn = o_nwn; s->lastO.nlay_max = o_nlay_max;
+        }
+        return MONORTM_OK;
+    }
+
+    int run_shares(Ctx *c, int nprof, const void *pre_obj, PreFn pre, const void *launch_obj, LaunchFn launch) const {
+        if (nf > kMaxFields) { c->err = "HostCall: more arrays declared than kMaxFields"; return MONORTM_EARG; }
+        if (c->shards.empty()) {
+            Pending pd;
+            if (int rc = enqueue(c, -1, 0, nprof, pre_obj, pre, launch_obj, launch, &pd)) return rc;
+            return finish(pd);
+        }
+        const int G = (int)c->shards.size();
+        std::vector<Pending> pend(G);
+        int rc = MONORTM_OK;
+        auto failed = [&](int r, Ctx *s) {   // the first error wins
+            if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
+        };
+        for (int g = 0; g < G; g++) {
+            int p0, n;
+            shard_block(nprof, G, g, &p0, &n);
+            if (n < 1) continue;
+            failed(enqueue(c->shards[g], g, p0, n, pre_obj, pre, launch_obj, launch, &pend[g]), c->shards[g]);   // (pend[g].s stays null)
+        }
+        for (int g = 0; g < G; g++)
+            if (pend[g].s) failed(finish(pend[g]), c->shards[g]);
+        return rc;
+    }
+
+    // pre(s, p0, n): what the entry checks or prepares per share, before anything of it is staged; launch(s, g, n, dev): the *_dev call
+    // of the share on shard g (-1: the context itself) with dev[i] the device address of the array declared as i
+    template <class Pre, class Launch>
+    int run(Ctx *c, int nprof, const Pre &pre, const Launch &launch) const {
+        return run_shares(c, nprof, &pre, [](const void *o, Ctx *s, int p0, int n) { return (*static_cast<const Pre *>(o))(s, p0, n); }, &launch,
+                          [](const void *o, Ctx *s, int g, int n, char *const *dev) { return (*static_cast<const Launch *>(o))(s, g, n, dev); });
+    }
+    template <class Launch>
+    int run(Ctx *c, int nprof, const Launch &launch) const {
+        return run(c, nprof, [](Ctx *, int, int) { return (int)MONORTM_OK; }, launch);
+    }
+};
 
 }  // namespace
 
@@ -1830,35 +1670,47 @@ int monortm_hip_modm_xs(void *ctx, int nprof, int nwn, const double *wn, double 
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
     DeviceGuard guard;
-    if (c->shards.empty())
-        return modm_host(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd,
-                         ixsect, XAMNT, ODXSEC, O, O_BY_MOL, OC, O_CLW, nullptr);
-    if (!nlay || !P || !T || !CLW || !WKL || !WBRODL || !O || !O_BY_MOL || !OC || !O_CLW || nprof < 1 || nwn < 1 || nlay_max < 1 || nmol < 1) {
+    const bool multi = !c->shards.empty();
+    if (multi && (!nlay || !P || !T || !CLW || !WKL || !WBRODL || !O || !O_BY_MOL || !OC || !O_CLW || nprof < 1 || nwn < 1 || nlay_max < 1 || nmol < 1)) {
         c->err = "bad or null argument";
         return MONORTM_EARG;
     }
-    const int G = (int)c->shards.size();
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d;
-    std::vector<std::function<int()>> fin(G);
-    int rc = MONORTM_OK;
-    for (int g = 0; g < G; g++) {
-        int p0, n;
-        shard_block(nprof, G, g, &p0, &n);
-        if (n < 1) continue;
-        Ctx *s = c->shards[g];
-        const int nxs = s->xs.nxs;
-        const int r = modm_host(s, n, nwn, wn, dvset, nlay + p0, nlay_max, nmol, off(P, p0 * l), off(T, p0 * l), off(CLW, p0 * l),
-                                off(WKL, p0 * l * nmol), off(WBRODL, p0 * l), cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect,
-                                XAMNT ? off(XAMNT, p0 * l * nxs) : nullptr, ODXSEC ? off(ODXSEC, p0 * w) : nullptr, off(O, p0 * w),
-                                off(O_BY_MOL, p0 * w * nmol), off(OC, p0 * w * MONORTM_NCONT), off(O_CLW, p0 * w), &fin[g]);
-        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
-    }
-    for (int g = 0; g < G; g++)
-        if (fin[g]) {
-            const int r = fin[g]();
-            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
-        }
-    return rc;
+    const bool xs = ixsect == 1;
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = l * nwn;
+    const int nxs = (multi ? c->shards[0] : c)->xs.nxs;
+    HostCall hc(0, 0);
+    hc.flag = true;
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_P = hc.in(P, l), i_T = hc.in(T, l),
+              i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l), i_XA = hc.in(xs ? XAMNT : nullptr, l * nxs);
+    const int o_O = hc.out(O, w), o_OM = hc.out(O_BY_MOL, w * nmol), o_OC = hc.out(OC, w * MONORTM_NCONT), o_OL = hc.out(O_CLW, w),
+              o_OX = hc.out(xs ? ODXSEC : nullptr, w);
+    hc.leaves_O(o_O, nwn, nlay_max);
+    // every share is checked on its own device's context, before anything of it is staged
+    auto pre = [&](Ctx *s, int p0, int n) -> int {
+        if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !O || !O_BY_MOL || !OC || !O_CLW) { s->err = "null array argument"; return MONORTM_EARG; }
+        if (n < 1 || nwn < 1 || nlay_max < 1 || nmol < 1) { s->err = "bad nprof/nwn/nlay_max/nmol"; return MONORTM_EARG; }
+        for (int i = 1; i < nwn; i++)
+            if (!(wn[i] >= wn[i - 1])) { s->err = "wavenumbers must be ascending (the reference takes v1 = wn(1), v2 = wn(nwn), modm.f90:180-181)"; return MONORTM_EARG; }
+        // dvset /= 0: what the kernels rely on is the nearest grid index within +-1 (line_records) and the continuum at V1 + i dvset
+        // as the reference's own CONTNM call places it - so the bound is on the cumulative drift, not on consecutive differences: the
+        // reference's "sgl" driver forms WN(J) = V1 + (J-1)*DVSET with a REAL*4 product (src/monortm_sub.F90:287), which moves
+        // point J by up to 6e-8 J DVSET
+        if (dvset != 0.)
+            for (int i = 1; i < nwn; i++)
+                if (!(std::fabs(wn[i] - (wn[0] + i * dvset)) <= 0.25 * std::fabs(dvset))) { s->err = "dvset /= 0 promises the grid wn[i] = wn[0] + i dvset (COMMON /MANE/ DVSET of the reference driver)"; return MONORTM_EARG; }
+        for (int p = p0; p < p0 + n; p++)
+            if (nlay[p] < 1 || nlay[p] > nlay_max) { s->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
+        s->lastO.dev = nullptr;  // before any arena can move or fail to regrow: nothing may point into a freed arena afterwards
+        s->lastO.host = nullptr;
+        if (xs && (!XAMNT || !ODXSEC || s->xs.nxs < 1)) { s->err = "IXSECT = 1: XAMNT / ODXSEC / cross-section tables missing"; return MONORTM_EARG; }
+        return MONORTM_OK;
+    };
+    return hc.run(c, nprof, pre, [&](Ctx *s, int, int n, char *const *dv) {
+        const double ends[2] = {wn[0], wn[nwn - 1]};
+        return monortm_hip_modm_xs_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C], dv[i_W],
+                                       dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, dv[i_XA], dv[o_OX], dv[o_O], dv[o_OM], dv[o_OC],
+                                       dv[o_OL], ends, s->hs);
+    });
 }
 
 int monortm_hip_rtm(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
@@ -1867,33 +1719,30 @@ int monortm_hip_rtm(void *ctx, int nprof, int nwn, const double *wn, const int *
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
     DeviceGuard guard;
-    if (c->shards.empty())
-        return rtm_host(c, nprof, nwn, wn, nlay, nlay_max, irt, iout, T, TZ, O, tmpsfc, emiss, reflc, RUP, RDN, TRTOT, RAD, TB, TMR, nullptr);
-    if (!nlay || !irt || !T || !TZ || !O || !tmpsfc || !emiss || !reflc || !RUP || !RDN || !TRTOT || !RAD || !TB || nprof < 1 || nwn < 1 ||
-        nlay_max < 1) {
+    if (!c->shards.empty() && (!nlay || !irt || !T || !TZ || !O || !tmpsfc || !emiss || !reflc || !RUP || !RDN || !TRTOT || !RAD || !TB ||
+                               nprof < 1 || nwn < 1 || nlay_max < 1)) {
         c->err = "bad or null argument";
         return MONORTM_EARG;
     }
-    const int G = (int)c->shards.size();
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
-    std::vector<std::function<int()>> fin(G);
-    int rc = MONORTM_OK;
-    for (int g = 0; g < G; g++) {
-        int p0, n;
-        shard_block(nprof, G, g, &p0, &n);
-        if (n < 1) continue;
-        Ctx *s = c->shards[g];
-        const int r = rtm_host(s, n, nwn, wn, nlay + p0, nlay_max, irt + p0, iout, off(T, p0 * l), off(TZ, p0 * (l + d)), off(O, p0 * w),
-                               off(tmpsfc, p0 * d), off(emiss, p0 * v), off(reflc, p0 * v), off(RUP, p0 * v), off(RDN, p0 * v),
-                               off(TRTOT, p0 * v), off(RAD, p0 * v), off(TB, p0 * v), TMR ? off(TMR, p0 * v) : nullptr, &fin[g]);
-        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
-    }
-    for (int g = 0; g < G; g++)
-        if (fin[g]) {
-            const int r = fin[g]();
-            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
-        }
-    return rc;
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, v = (size_t)nwn * d;
+    HostCall hc(4, 1);
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
+              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, l * nwn), i_em = hc.in(emiss, v), i_rf = hc.in(reflc, v), io_ts = hc.inout(tmpsfc, d);
+    // TB of a call with iout /= 1: zeroed on the device, the caller's array is left alone
+    const int o_up = hc.out(RUP, v), o_dn = hc.out(RDN, v), o_tr = hc.out(TRTOT, v), o_rad = hc.out(RAD, v),
+              o_tb = iout == 1 ? hc.out(TB, v) : hc.out_zeroed(TB, v), o_tmr = hc.out(TMR, v);
+    hc.reads_O(i_O, nwn, nlay_max, &Ctx::o_reused);
+    auto pre = [&](Ctx *s, int p0, int n) -> int {
+        if (!wn || !nlay || !irt || !T || !TZ || !O || !tmpsfc || !emiss || !reflc || !RUP || !RDN || !TRTOT || !RAD || !TB) { s->err = "null array argument"; return MONORTM_EARG; }
+        for (int p = p0; p < p0 + n; p++)
+            if (nlay[p] < 1 || nlay[p] > nlay_max) { s->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
+        if (n < 1 || nwn < 1 || nlay_max < 1) { s->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+        return MONORTM_OK;
+    };
+    return hc.run(c, nprof, pre, [&](Ctx *s, int, int n, char *const *dv) {
+        return monortm_hip_rtm_dev(s, n, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], iout, dv[i_T], dv[i_TZ], dv[i_O],
+                                   dv[io_ts], dv[i_em], dv[i_rf], dv[o_up], dv[o_dn], dv[o_tr], dv[o_rad], dv[o_tb], dv[o_tmr], s->hs);
+    });
 }
 
 // ---- path scans ---------------------------------------------------------------------------------
@@ -1932,31 +1781,20 @@ int monortm_hip_rtm_scan(void *ctx, int nprof, int npath, int nwn, const double 
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
     // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
     if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
-    if (c->shards.empty())
-        return rtm_scan_host(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, iout, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, RUP, RDN,
-                             TRTOT, RAD, TB, TMR, nullptr);
-    const int G = (int)c->shards.size();
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
-    const size_t f = l * npath, vo = v * npath, vs = sfc_per_path ? vo : v;
-    std::vector<std::function<int()>> fin(G);
-    int rc = MONORTM_OK;
-    for (int g = 0; g < G; g++) {
-        int p0, n;
-        shard_block(nprof, G, g, &p0, &n);
-        if (n < 1) continue;
-        Ctx *s = c->shards[g];
-        const int r = rtm_scan_host(s, n, npath, nwn, wn, nlay + p0, nlay_max, irt + p0, iout, off(T, p0 * l), off(TZ, p0 * (l + d)),
-                                    off(O, p0 * w), off(path, p0 * f), off(tmpsfc, p0 * d), sfc_per_path, off(emiss, p0 * vs),
-                                    off(reflc, p0 * vs), off(RUP, p0 * vo), off(RDN, p0 * vo), off(TRTOT, p0 * vo), off(RAD, p0 * vo),
-                                    off(TB, p0 * vo), TMR ? off(TMR, p0 * vo) : nullptr, &fin[g]);
-        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
-    }
-    for (int g = 0; g < G; g++)
-        if (fin[g]) {
-            const int r = fin[g]();
-            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
-        }
-    return rc;
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vo = (size_t)nwn * npath * d, vs = sfc_per_path ? vo : (size_t)nwn * d;
+    HostCall hc(4, 2);
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
+              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, l * nwn), i_f = hc.in(path, l * npath), i_em = hc.in(emiss, vs), i_rf = hc.in(reflc, vs),
+              io_ts = hc.inout(tmpsfc, d);
+    // TB of a call with iout /= 1: zeroed on the device, the caller's array is left alone
+    const int o_up = hc.out(RUP, vo), o_dn = hc.out(RDN, vo), o_tr = hc.out(TRTOT, vo), o_rad = hc.out(RAD, vo),
+              o_tb = iout == 1 ? hc.out(TB, vo) : hc.out_zeroed(TB, vo), o_tmr = hc.out(TMR, vo);
+    hc.reads_O(i_O, nwn, nlay_max, &Ctx::o_reused_scan);
+    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
+        return monortm_hip_rtm_scan_dev(s, n, npath, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], iout, dv[i_T], dv[i_TZ],
+                                        dv[i_O], dv[i_f], dv[io_ts], sfc_per_path, dv[i_em], dv[i_rf], dv[o_up], dv[o_dn], dv[o_tr], dv[o_rad],
+                                        dv[o_tb], dv[o_tmr], s->hs);
+    });
 }
 
 // ---- Jacobians ----------------------------------------------------------------------------------
@@ -1970,7 +1808,7 @@ int monortm_hip_rtm_jac_dev(void *ctx, int nprof, int nwn, const double *wn, con
         c->err = "null array argument";
         return MONORTM_EARG;
     }
-    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rcq = check_quantity(c, quantity)) return rcq;
     if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
     RtmJacArgs a{};
@@ -1991,18 +1829,10 @@ int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, do
                              void *stream) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    if (!c->shards.empty()) return multi_only_host(c);
-    if (c->real_kind != 8) { c->err = "monortm_hip_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !O || !RAD ||
-        !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
-    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
-    if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    const bool any_null = !wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !O ||
+                          !RAD || !TB || !K_T || !K_TZ || !K_CLW || !K_SFC;
+    if (int rc = jac_full_check(c, "monortm_hip_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W)) return rc;
     if (int rcd = check_device(c)) return rcd;
     double *xO = nullptr;
     size_t st = 0;
@@ -2010,13 +1840,10 @@ int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, do
                             jac_mol, O, wn_ends, s, &xO, &st))
         return rc;
     RtmJacArgs a{};
-    a.nprof = nprof; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = 8; a.njac = njac;
+    a.nprof = nprof; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity;
     a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC; a.K_W = K_W; a.K_CLW = K_CLW;
-    a.Opert = xO + st;
-    a.state_stride = st;
-    a.dt = c->opt.jac_dt;
-    a.dlnw = c->opt.jac_dlnw;
+    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
+    jac_chain_args(a, c, njac, K_W, K_CLW, xO, st);
     launch_rtm_jac(a, true, s);
     HIPCHK(c, hipGetLastError());
     return MONORTM_OK;
@@ -2032,30 +1859,17 @@ int monortm_hip_rtm_jac(void *ctx, int nprof, int nwn, const double *wn, const i
         return MONORTM_EARG;
     }
     DeviceGuard guard;
-    if (c->shards.empty())
-        return rtm_jac_host(c, nprof, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, tmpsfc, emiss, reflc, RAD, TB, K_O, K_T, K_TZ, K_SFC, nullptr);
     if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    const int G = (int)c->shards.size();
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d,
-                 wz = (size_t)(nlay_max + 1) * nwn * d;
-    std::vector<std::function<int()>> fin(G);
-    int rc = MONORTM_OK;
-    for (int g = 0; g < G; g++) {
-        int p0, n;
-        shard_block(nprof, G, g, &p0, &n);
-        if (n < 1) continue;
-        Ctx *s = c->shards[g];
-        const int r = rtm_jac_host(s, n, nwn, wn, nlay + p0, nlay_max, irt + p0, quantity, off(T, p0 * l), off(TZ, p0 * (l + d)), off(O, p0 * w),
-                                   off(tmpsfc, p0 * d), off(emiss, p0 * v), off(reflc, p0 * v), off(RAD, p0 * v), off(TB, p0 * v), off(K_O, p0 * w),
-                                   off(K_T, p0 * w), off(K_TZ, p0 * wz), off(K_SFC, p0 * 3 * v), &fin[g]);
-        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
-    }
-    for (int g = 0; g < G; g++)
-        if (fin[g]) {
-            const int r = fin[g]();
-            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
-        }
-    return rc;
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, v = (size_t)nwn * d, w = l * nwn;
+    HostCall hc(8);
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
+              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, w), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, v), i_rf = hc.in(reflc, v);
+    const int o_rad = hc.out(RAD, v), o_tb = hc.out(TB, v), o_ko = hc.out(K_O, w), o_kt = hc.out(K_T, w), o_ktz = hc.out(K_TZ, (l + d) * nwn),
+              o_ks = hc.out(K_SFC, 3 * v);
+    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
+        return monortm_hip_rtm_jac_dev(s, n, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], quantity, dv[i_T], dv[i_TZ],
+                                       dv[i_O], dv[i_ts], dv[i_em], dv[i_rf], dv[o_rad], dv[o_tb], dv[o_ko], dv[o_kt], dv[o_ktz], dv[o_ks], s->hs);
+    });
 }
 
 int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
@@ -2065,40 +1879,35 @@ int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double
                          void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    if (c->real_kind != 8) { c->err = "monortm_hip_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
+    if (int rc = need_real8(c, "monortm_hip_jacobian")) return rc;
     if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !O || !RAD ||
         !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
         c->err = "null array argument";
         return MONORTM_EARG;
     }
     DeviceGuard guard;
-    if (c->shards.empty())
-        return jac_host(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt, TZ,
-                        tmpsfc, emiss, reflc, quantity, njac, jac_mol, O, RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O, K_SFC, nullptr);
     if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
     if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
-    const int G = (int)c->shards.size();
-    const size_t d = 8, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d, wz = (size_t)(nlay_max + 1) * nwn * d;
-    std::vector<std::function<int()>> fin(G);
-    int rc = MONORTM_OK;
-    for (int g = 0; g < G; g++) {
-        int p0, n;
-        shard_block(nprof, G, g, &p0, &n);
-        if (n < 1) continue;
-        Ctx *s = c->shards[g];
-        const int r = jac_host(s, n, nwn, wn, dvset, nlay + p0, nlay_max, nmol, off(P, p0 * l), off(T, p0 * l), off(CLW, p0 * l),
-                               off(WKL, p0 * l * nmol), off(WBRODL, p0 * l), cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt + p0, off(TZ, p0 * (l + d)),
-                               off(tmpsfc, p0 * d), off(emiss, p0 * v), off(reflc, p0 * v), quantity, njac, jac_mol, off(O, p0 * w), off(RAD, p0 * v),
-                               off(TB, p0 * v), off(K_T, p0 * w), off(K_TZ, p0 * wz), njac ? off(K_W, p0 * w * njac) : nullptr, off(K_CLW, p0 * w),
-                               K_O ? off(K_O, p0 * w) : nullptr, off(K_SFC, p0 * 3 * v), &fin[g]);
-        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
-    }
-    for (int g = 0; g < G; g++)
-        if (fin[g]) {
-            const int r = fin[g]();
-            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
-        }
-    return rc;
+    const size_t d = 8, l = (size_t)nlay_max * d, v = (size_t)nwn * d, w = l * nwn;
+    HostCall hc(8);
+    hc.flag = true;
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
+              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l), i_TZ = hc.in(TZ, l + d),
+              i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, v), i_rf = hc.in(reflc, v);
+    const int o_O = hc.out(O, w), o_rad = hc.out(RAD, v), o_tb = hc.out(TB, v), o_kt = hc.out(K_T, w), o_ktz = hc.out(K_TZ, (l + d) * nwn),
+              o_kw = hc.out(njac ? K_W : nullptr, w * njac), o_kc = hc.out(K_CLW, w), o_ko = hc.out(K_O, w), o_ks = hc.out(K_SFC, 3 * v);
+    // every share's states are checked on its own device's context, before anything of it is staged
+    auto pre = [&](Ctx *s, int p0, int n) -> int {
+        if (nmol < 1) { s->err = "bad nmol"; return MONORTM_EARG; }
+        return jac_check_states(s, n, nwn, wn, nlay + p0, nlay_max, hc.host(i_T, p0));
+    };
+    return hc.run(c, nprof, pre, [&](Ctx *s, int, int n, char *const *dv) {
+        const double ends[2] = {wn[0], wn[nwn - 1]};
+        return monortm_hip_jacobian_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C], dv[i_W],
+                                        dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em], dv[i_rf],
+                                        quantity, njac, jac_mol, dv[o_O], dv[o_rad], dv[o_tb], dv[o_kt], dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ko],
+                                        dv[o_ks], ends, s->hs);
+    });
 }
 
 // ---- Jacobians of path scans ----------------------------------------------------------------------
@@ -2113,7 +1922,7 @@ int monortm_hip_rtm_scan_jac_dev(void *ctx, int nprof, int npath, int nwn, const
         c->err = "null array argument";
         return MONORTM_EARG;
     }
-    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rcq = check_quantity(c, quantity)) return rcq;
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
     if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
@@ -2139,19 +1948,11 @@ int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *w
                                   void *stream) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    if (!c->shards.empty()) return multi_only_host(c);
-    if (c->real_kind != 8) { c->err = "monortm_hip_scan_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !RAD ||
-        !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
-    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    const bool any_null = !wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path ||
+                          !O || !RAD || !TB || !K_T || !K_TZ || !K_CLW || !K_SFC;
+    if (int rc = jac_full_check(c, "monortm_hip_scan_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W)) return rc;
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
     double *xO = nullptr;
     size_t st = 0;
@@ -2159,14 +1960,11 @@ int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *w
                             jac_mol, O, wn_ends, s, &xO, &st))
         return rc;
     RtmScanJacArgs a{};
-    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = 8; a.njac = njac;
+    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity;
     a.sfc_per_path = sfc_per_path;
     a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_PATH = K_PATH; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC; a.K_W = K_W; a.K_CLW = K_CLW;
-    a.Opert = xO + st;
-    a.state_stride = st;
-    a.dt = c->opt.jac_dt;
-    a.dlnw = c->opt.jac_dlnw;
+    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_PATH = K_PATH; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
+    jac_chain_args(a, c, njac, K_W, K_CLW, xO, st);
     a.errflag = c->errflag;
     launch_rtm_scan_jac(a, true, s);
     HIPCHK(c, hipGetLastError());
@@ -2184,36 +1982,23 @@ int monortm_hip_rtm_scan_jac(void *ctx, int nprof, int npath, int nwn, const dou
         c->err = "null array argument";
         return MONORTM_EARG;
     }
-    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rc = check_quantity(c, quantity)) return rc;
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
     // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
     if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
-    if (c->shards.empty())
-        return rtm_scan_jac_host(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, RAD,
-                                 TB, K_O, K_PATH, K_T, K_TZ, K_SFC, nullptr);
-    const int G = (int)c->shards.size();
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
-    const size_t f = l * npath, vo = v * npath, vs = sfc_per_path ? vo : v, wo = w * npath, wz = (size_t)(nlay_max + 1) * nwn * d * npath;
-    std::vector<std::function<int()>> fin(G);
-    int rc = MONORTM_OK;
-    for (int g = 0; g < G; g++) {
-        int p0, n;
-        shard_block(nprof, G, g, &p0, &n);
-        if (n < 1) continue;
-        Ctx *s = c->shards[g];
-        const int r = rtm_scan_jac_host(s, n, npath, nwn, wn, nlay + p0, nlay_max, irt + p0, quantity, off(T, p0 * l), off(TZ, p0 * (l + d)),
-                                        off(O, p0 * w), off(path, p0 * f), off(tmpsfc, p0 * d), sfc_per_path, off(emiss, p0 * vs),
-                                        off(reflc, p0 * vs), off(RAD, p0 * vo), off(TB, p0 * vo), K_O ? off(K_O, p0 * wo) : nullptr,
-                                        K_PATH ? off(K_PATH, p0 * wo) : nullptr, off(K_T, p0 * wo), off(K_TZ, p0 * wz), off(K_SFC, p0 * 3 * vo),
-                                        &fin[g]);
-        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
-    }
-    for (int g = 0; g < G; g++)
-        if (fin[g]) {
-            const int r = fin[g]();
-            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
-        }
-    return rc;
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vo = (size_t)nwn * npath * d, vs = sfc_per_path ? vo : (size_t)nwn * d,
+                 wo = l * nwn * npath;
+    HostCall hc(8);
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
+              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, l * nwn), i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs),
+              i_rf = hc.in(reflc, vs);
+    const int o_rad = hc.out(RAD, vo), o_tb = hc.out(TB, vo), o_ko = hc.out(K_O, wo), o_kp = hc.out(K_PATH, wo), o_kt = hc.out(K_T, wo),
+              o_ktz = hc.out(K_TZ, (l + d) * nwn * npath), o_ks = hc.out(K_SFC, 3 * vo);
+    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
+        return monortm_hip_rtm_scan_jac_dev(s, n, npath, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], quantity, dv[i_T],
+                                            dv[i_TZ], dv[i_O], dv[i_f], dv[i_ts], sfc_per_path, dv[i_em], dv[i_rf], dv[o_rad], dv[o_tb], dv[o_ko],
+                                            dv[o_kp], dv[o_kt], dv[o_ktz], dv[o_ks], s->hs);
+    });
 }
 
 int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
@@ -2224,7 +2009,7 @@ int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, d
                               void *K_PATH, void *K_SFC) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    if (c->real_kind != 8) { c->err = "monortm_hip_scan_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
+    if (int rc = need_real8(c, "monortm_hip_scan_jacobian")) return rc;
     if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !RAD ||
         !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
         c->err = "null array argument";
@@ -2238,34 +2023,22 @@ int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, d
     if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
     if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
     if (int rc = jac_check_states(c, nprof, nwn, wn, nlay, nlay_max, T)) return rc;
-    if (c->shards.empty())
-        return scan_jac_host(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt, TZ,
-                             tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, O, RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O,
-                             K_PATH, K_SFC, nullptr);
-    const int G = (int)c->shards.size();
-    const size_t d = 8, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
-    const size_t f = l * npath, vo = v * npath, vs = sfc_per_path ? vo : v, wo = w * npath, wz = (size_t)(nlay_max + 1) * nwn * d * npath;
-    std::vector<std::function<int()>> fin(G);
-    int rc = MONORTM_OK;
-    for (int g = 0; g < G; g++) {
-        int p0, n;
-        shard_block(nprof, G, g, &p0, &n);
-        if (n < 1) continue;
-        Ctx *s = c->shards[g];
-        const int r = scan_jac_host(s, n, nwn, wn, dvset, nlay + p0, nlay_max, nmol, off(P, p0 * l), off(T, p0 * l), off(CLW, p0 * l),
-                                    off(WKL, p0 * l * nmol), off(WBRODL, p0 * l), cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt + p0,
-                                    off(TZ, p0 * (l + d)), off(tmpsfc, p0 * d), off(emiss, p0 * vs), off(reflc, p0 * vs), quantity, njac, jac_mol,
-                                    npath, off(path, p0 * f), sfc_per_path, off(O, p0 * w), off(RAD, p0 * vo), off(TB, p0 * vo), off(K_T, p0 * wo),
-                                    off(K_TZ, p0 * wz), njac ? off(K_W, p0 * wo * njac) : nullptr, off(K_CLW, p0 * wo),
-                                    K_O ? off(K_O, p0 * wo) : nullptr, K_PATH ? off(K_PATH, p0 * wo) : nullptr, off(K_SFC, p0 * 3 * vo), &fin[g]);
-        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
-    }
-    for (int g = 0; g < G; g++)
-        if (fin[g]) {
-            const int r = fin[g]();
-            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
-        }
-    return rc;
+    const size_t d = 8, l = (size_t)nlay_max * d, w = l * nwn, vo = (size_t)nwn * npath * d, vs = sfc_per_path ? vo : (size_t)nwn * d, wo = w * npath;
+    HostCall hc(8);
+    hc.flag = true;
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
+              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l), i_TZ = hc.in(TZ, l + d),
+              i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs), i_rf = hc.in(reflc, vs);
+    const int o_O = hc.out(O, w), o_rad = hc.out(RAD, vo), o_tb = hc.out(TB, vo), o_kt = hc.out(K_T, wo), o_ktz = hc.out(K_TZ, (l + d) * nwn * npath),
+              o_kw = hc.out(njac ? K_W : nullptr, wo * njac), o_kc = hc.out(K_CLW, wo), o_ko = hc.out(K_O, wo), o_kp = hc.out(K_PATH, wo),
+              o_ks = hc.out(K_SFC, 3 * vo);
+    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
+        const double ends[2] = {wn[0], wn[nwn - 1]};
+        return monortm_hip_scan_jacobian_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C],
+                                             dv[i_W], dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em],
+                                             dv[i_rf], quantity, njac, jac_mol, npath, dv[i_f], sfc_per_path, dv[o_O], dv[o_rad], dv[o_tb], dv[o_kt],
+                                             dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ko], dv[o_kp], dv[o_ks], ends, s->hs);
+    });
 }
 
 
@@ -2387,7 +2160,7 @@ int rtm_obs_jac_dev_impl(Ctx *c, int nprof, int npath, int nwn, const double *wn
         c->err = "null array argument";
         return MONORTM_EARG;
     }
-    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rcq = check_quantity(c, quantity)) return rcq;
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
     if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     Ctx::Obs *ob = nullptr;
@@ -2405,107 +2178,6 @@ int rtm_obs_jac_dev_impl(Ctx *c, int nprof, int npath, int nwn, const double *wn
     return MONORTM_OK;
 }
 
-// double -> the context's REAL kind, rounded once (real_kind = 4), or a plain copy
-void obs_unpack(void *dst, const char *src, size_t n, int real_kind) {
-    if (real_kind == 8) { memcpy(dst, src, n * 8); return; }
-    const double *s = reinterpret_cast<const double *>(src);
-    float *d = static_cast<float *>(dst);
-    for (size_t i = 0; i < n; i++) d[i] = (float)s[i];
-}
-
-// One device's share of the host entries: the staging slots of the Jacobian entries (8-11).  The arguments are those the entry points
-// have checked for the whole call; obs is the operator's handle on THIS context.
-int rtm_obs_jac_host(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
-                     const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path, const void *emiss,
-                     const void *reflc, int obs, void *Y, void *K_T, void *K_TZ, void *K_SFC, std::function<int()> *defer) {
-    HIPCHK(c, hipSetDevice(c->device));
-    Ctx::Obs *ob = obs_find(c, obs);
-    if (!ob) return obs_bad_handle(c);
-    const size_t npl = (size_t)nprof * nlay_max, d = (size_t)c->real_kind, pw = (size_t)nprof * nwn, ppw = pw * npath;
-    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_tz = (size_t)nprof * (nlay_max + 1) * d,
-                 b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d, b_sfc = (sfc_per_path ? ppw : pw) * d;
-    const size_t n_y = (size_t)nprof * ob->nview * ob->nchan, n_k = n_y * nlay_max, n_kz = n_y * (nlay_max + 1);   // elements, held as double
-    Arena in, out;
-    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_T = in.add(b_l), i_TZ = in.add(b_tz), i_O = in.add(b_o),
-                 i_f = in.add(b_f), i_ts = in.add(b_p), i_em = in.add(b_sfc), i_rf = in.add(b_sfc);
-    const size_t o_y = out.add(n_y * 8), o_kt = out.add(n_k * 8), o_ktz = out.add(n_kz * 8), o_ks = out.add(3 * n_y * 8);
-    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
-    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
-    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
-    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
-    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
-    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
-    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_T, T, b_l);
-    memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_O, O, b_o); memcpy(h + i_f, path, b_f); memcpy(h + i_ts, tmpsfc, b_p);
-    memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
-    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
-    int rc = rtm_obs_jac_dev_impl(c, nprof, npath, nwn, (double *)(dv + i_wn), (int *)(dv + i_nl), nlay_max, (int *)(dv + i_irt), quantity,
-                                  dv + i_T, dv + i_TZ, dv + i_O, dv + i_f, dv + i_ts, sfc_per_path, dv + i_em, dv + i_rf, obs, dz + o_y,
-                                  dz + o_kt, dz + o_ktz, dz + o_ks, 8, c->hs);
-    if (rc) return rc;
-    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs));
-    const int rk = c->real_kind;
-    auto complete = [=]() mutable -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->hs));
-        const char *ho = static_cast<const char *>(hout);
-        obs_unpack(Y, ho + o_y, n_y, rk); obs_unpack(K_T, ho + o_kt, n_k, rk); obs_unpack(K_TZ, ho + o_ktz, n_kz, rk);
-        obs_unpack(K_SFC, ho + o_ks, 3 * n_y, rk);
-        return MONORTM_OK;
-    };
-    if (defer) { *defer = complete; return MONORTM_OK; }
-    return complete();
-}
-
-int obs_jac_host(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
-                 const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
-                 double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity,
-                 int njac, const int *jac_mol, int npath, const void *path, int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ,
-                 void *K_W, void *K_CLW, void *K_SFC, std::function<int()> *defer) {
-    HIPCHK(c, hipSetDevice(c->device));
-    Ctx::Obs *ob = obs_find(c, obs);
-    if (!ob) return obs_bad_handle(c);
-    const size_t npl = (size_t)nprof * nlay_max, d = 8, pw = (size_t)nprof * nwn, ppw = pw * npath;
-    const size_t b_wn = nwn * sizeof(double), b_i = nprof * sizeof(int), b_l = npl * d, b_w = npl * nmol * d,
-                 b_tz = (size_t)nprof * (nlay_max + 1) * d, b_o = npl * nwn * d, b_p = nprof * d, b_f = npl * npath * d,
-                 b_sfc = (sfc_per_path ? ppw : pw) * d;
-    const size_t b_y = (size_t)nprof * ob->nview * ob->nchan * d, b_k = b_y * nlay_max, b_kz = b_y * (nlay_max + 1), b_kw = b_k * njac;
-    Arena in, out;
-    const size_t i_wn = in.add(b_wn), i_nl = in.add(b_i), i_irt = in.add(b_i), i_P = in.add(b_l), i_T = in.add(b_l), i_C = in.add(b_l),
-                 i_W = in.add(b_w), i_B = in.add(b_l), i_TZ = in.add(b_tz), i_f = in.add(b_f), i_ts = in.add(b_p), i_em = in.add(b_sfc),
-                 i_rf = in.add(b_sfc);
-    const size_t o_O = out.add(b_o), o_y = out.add(b_y), o_kt = out.add(b_k), o_ktz = out.add(b_kz), o_kw = out.add(b_kw), o_kc = out.add(b_k),
-                 o_ks = out.add(3 * b_y);
-    void *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr;
-    HIPCHK(c, stage_get(c, 8, in.size, true, &hin));
-    HIPCHK(c, stage_get(c, 9, in.size, false, &din));
-    HIPCHK(c, stage_get(c, 10, out.size, true, &hout));
-    HIPCHK(c, stage_get(c, 11, out.size, false, &dout));
-    char *h = static_cast<char *>(hin), *dv = static_cast<char *>(din), *dz = static_cast<char *>(dout);
-    memcpy(h + i_wn, wn, b_wn); memcpy(h + i_nl, nlay, b_i); memcpy(h + i_irt, irt, b_i); memcpy(h + i_P, P, b_l); memcpy(h + i_T, T, b_l);
-    memcpy(h + i_C, CLW, b_l); memcpy(h + i_W, WKL, b_w); memcpy(h + i_B, WBRODL, b_l); memcpy(h + i_TZ, TZ, b_tz); memcpy(h + i_f, path, b_f);
-    memcpy(h + i_ts, tmpsfc, b_p); memcpy(h + i_em, emiss, b_sfc); memcpy(h + i_rf, reflc, b_sfc);
-    HIPCHK(c, move_arena(din, hin, in.size, hipMemcpyHostToDevice, c->hs));
-    const double ends[2] = {wn[0], wn[nwn - 1]};
-    int rc = monortm_hip_obs_jacobian_dev(c, nprof, nwn, (double *)(dv + i_wn), dvset, (int *)(dv + i_nl), nlay_max, nmol, dv + i_P, dv + i_T,
-                                          dv + i_C, dv + i_W, dv + i_B, cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)(dv + i_irt), dv + i_TZ,
-                                          dv + i_ts, dv + i_em, dv + i_rf, quantity, njac, jac_mol, npath, dv + i_f, sfc_per_path, obs, dz + o_O,
-                                          dz + o_y, dz + o_kt, dz + o_ktz, njac ? dz + o_kw : nullptr, dz + o_kc, dz + o_ks, ends, c->hs);
-    if (rc) return rc;
-    HIPCHK(c, move_arena(hout, dout, out.size, hipMemcpyDeviceToHost, c->hs, c->errflag, c->errflag_host));
-    auto complete = [=]() mutable -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->hs));
-        if (int rcf = decode_flag(c, *c->errflag_host, c->hs)) return rcf;
-        const char *ho = static_cast<const char *>(hout);
-        memcpy(O, ho + o_O, b_o); memcpy(Y, ho + o_y, b_y); memcpy(K_T, ho + o_kt, b_k); memcpy(K_TZ, ho + o_ktz, b_kz);
-        memcpy(K_CLW, ho + o_kc, b_k); memcpy(K_SFC, ho + o_ks, 3 * b_y);
-        if (njac) memcpy(K_W, ho + o_kw, b_kw);
-        return MONORTM_OK;
-    };
-    if (defer) { *defer = complete; return MONORTM_OK; }
-    return complete();
-}
 }  // namespace
 
 extern "C" {
@@ -2582,19 +2254,11 @@ int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn
                                  const double *wn_ends, void *stream) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    if (!c->shards.empty()) return multi_only_host(c);
-    if (c->real_kind != 8) { c->err = "monortm_hip_obs_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !Y ||
-        !K_T || !K_TZ || !K_CLW || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
-    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    const bool any_null = !wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path ||
+                          !O || !Y || !K_T || !K_TZ || !K_CLW || !K_SFC;
+    if (int rc = jac_full_check(c, "monortm_hip_obs_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W)) return rc;
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     Ctx::Obs *ob = nullptr;
     if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
     if (int rcd = check_device(c)) return rcd;
@@ -2604,14 +2268,11 @@ int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn
                             jac_mol, O, wn_ends, s, &xO, &st))
         return rc;
     RtmObsJacArgs a{};
-    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = 8; a.njac = njac;
+    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity;
     a.sfc_per_path = sfc_per_path;
     a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.Y = Y; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC; a.K_W = K_W; a.K_CLW = K_CLW;
-    a.Opert = xO + st;
-    a.state_stride = st;
-    a.dt = c->opt.jac_dt;
-    a.dlnw = c->opt.jac_dlnw;
+    a.Y = Y; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
+    jac_chain_args(a, c, njac, K_W, K_CLW, xO, st);
     a.errflag = c->errflag;
     obs_args(a, *ob);
     launch_rtm_obs_jac(a, true, 8, s);
@@ -2629,37 +2290,26 @@ int monortm_hip_rtm_obs_jac(void *ctx, int nprof, int npath, int nwn, const doub
         c->err = "null array argument";
         return MONORTM_EARG;
     }
-    if (quantity != 0 && quantity != 1) { c->err = "quantity must be 0 (RAD) or 1 (TB)"; return MONORTM_EARG; }
+    if (int rc = check_quantity(c, quantity)) return rc;
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
     Ctx::Obs *ob = nullptr;
     if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
     // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
     if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
-    if (c->shards.empty())
-        return rtm_obs_jac_host(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, obs, Y,
-                                K_T, K_TZ, K_SFC, nullptr);
-    const int G = (int)c->shards.size();
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
-    const size_t f = l * npath, vs = sfc_per_path ? v * npath : v, y = (size_t)ob->nview * ob->nchan * d;
-    std::vector<std::function<int()>> fin(G);
-    int rc = MONORTM_OK;
-    for (int g = 0; g < G; g++) {
-        int p0, n;
-        shard_block(nprof, G, g, &p0, &n);
-        if (n < 1) continue;
-        Ctx *s = c->shards[g];
-        const int r = rtm_obs_jac_host(s, n, npath, nwn, wn, nlay + p0, nlay_max, irt + p0, quantity, off(T, p0 * l), off(TZ, p0 * (l + d)),
-                                       off(O, p0 * w), off(path, p0 * f), off(tmpsfc, p0 * d), sfc_per_path, off(emiss, p0 * vs),
-                                       off(reflc, p0 * vs), ob->shard[g], off(Y, p0 * y), off(K_T, p0 * y * nlay_max),
-                                       off(K_TZ, p0 * y * (nlay_max + 1)), off(K_SFC, p0 * 3 * y), &fin[g]);
-        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
-    }
-    for (int g = 0; g < G; g++)
-        if (fin[g]) {
-            const int r = fin[g]();
-            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
-        }
-    return rc;
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vs = (size_t)nwn * (sfc_per_path ? npath : 1) * d;
+    const size_t y = (size_t)ob->nview * ob->nchan;   // measurements of a profile
+    HostCall hc(8);
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
+              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, l * nwn), i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs),
+              i_rf = hc.in(reflc, vs);
+    // the kernel accumulates into double outputs (out_kind 8) whatever the context's REAL kind: rounded once, when they are unpacked
+    const int o_y = hc.out_widened(Y, y), o_kt = hc.out_widened(K_T, y * nlay_max), o_ktz = hc.out_widened(K_TZ, y * (nlay_max + 1)),
+              o_ks = hc.out_widened(K_SFC, 3 * y);
+    return hc.run(c, nprof, [&](Ctx *s, int g, int n, char *const *dv) {   // (every shard holds the operator under a handle of its own)
+        return rtm_obs_jac_dev_impl(s, n, npath, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], quantity, dv[i_T], dv[i_TZ],
+                                    dv[i_O], dv[i_f], dv[i_ts], sfc_per_path, dv[i_em], dv[i_rf], g < 0 ? obs : ob->shard[g], dv[o_y], dv[o_kt],
+                                    dv[o_ktz], dv[o_ks], 8, s->hs);
+    });
 }
 
 int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
@@ -2669,7 +2319,7 @@ int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, do
                              int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_SFC) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    if (c->real_kind != 8) { c->err = "monortm_hip_obs_jacobian needs a real_kind = 8 context (its differences of optical depths need double arrays)"; return MONORTM_EUNSUPPORTED; }
+    if (int rc = need_real8(c, "monortm_hip_obs_jacobian")) return rc;
     if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !Y ||
         !K_T || !K_TZ || !K_CLW || !K_SFC) {
         c->err = "null array argument";
@@ -2685,34 +2335,22 @@ int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, do
     if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
     if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
     if (int rc = jac_check_states(c, nprof, nwn, wn, nlay, nlay_max, T)) return rc;
-    if (c->shards.empty())
-        return obs_jac_host(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt, TZ,
-                            tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, obs, O, Y, K_T, K_TZ, K_W, K_CLW, K_SFC,
-                            nullptr);
-    const int G = (int)c->shards.size();
-    const size_t d = 8, l = (size_t)nlay_max * d, w = (size_t)nlay_max * nwn * d, v = (size_t)nwn * d;
-    const size_t f = l * npath, vs = sfc_per_path ? v * npath : v, y = (size_t)ob->nview * ob->nchan * d, yk = y * nlay_max;
-    std::vector<std::function<int()>> fin(G);
-    int rc = MONORTM_OK;
-    for (int g = 0; g < G; g++) {
-        int p0, n;
-        shard_block(nprof, G, g, &p0, &n);
-        if (n < 1) continue;
-        Ctx *s = c->shards[g];
-        const int r = obs_jac_host(s, n, nwn, wn, dvset, nlay + p0, nlay_max, nmol, off(P, p0 * l), off(T, p0 * l), off(CLW, p0 * l),
-                                   off(WKL, p0 * l * nmol), off(WBRODL, p0 * l), cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt + p0,
-                                   off(TZ, p0 * (l + d)), off(tmpsfc, p0 * d), off(emiss, p0 * vs), off(reflc, p0 * vs), quantity, njac, jac_mol,
-                                   npath, off(path, p0 * f), sfc_per_path, ob->shard[g], off(O, p0 * w), off(Y, p0 * y), off(K_T, p0 * yk),
-                                   off(K_TZ, p0 * (yk + y)), njac ? off(K_W, p0 * yk * njac) : nullptr, off(K_CLW, p0 * yk), off(K_SFC, p0 * 3 * y),
-                                   &fin[g]);
-        if (r && !rc) { rc = r; c->err = "device " + std::to_string(s->device) + ": " + s->err; }
-    }
-    for (int g = 0; g < G; g++)
-        if (fin[g]) {
-            const int r = fin[g]();
-            if (r && !rc) { rc = r; c->err = "device " + std::to_string(c->shards[g]->device) + ": " + c->shards[g]->err; }
-        }
-    return rc;
+    const size_t d = 8, l = (size_t)nlay_max * d, vs = (size_t)nwn * (sfc_per_path ? npath : 1) * d;
+    const size_t y = (size_t)ob->nview * ob->nchan * d, yk = y * nlay_max;   // bytes of a profile's measurements, of their layer derivatives
+    HostCall hc(8);
+    hc.flag = true;
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
+              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l), i_TZ = hc.in(TZ, l + d),
+              i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs), i_rf = hc.in(reflc, vs);
+    const int o_O = hc.out(O, l * nwn), o_y = hc.out(Y, y), o_kt = hc.out(K_T, yk), o_ktz = hc.out(K_TZ, yk + y),
+              o_kw = hc.out(njac ? K_W : nullptr, yk * njac), o_kc = hc.out(K_CLW, yk), o_ks = hc.out(K_SFC, 3 * y);
+    return hc.run(c, nprof, [&](Ctx *s, int g, int n, char *const *dv) {   // (every shard holds the operator under a handle of its own)
+        const double ends[2] = {wn[0], wn[nwn - 1]};
+        return monortm_hip_obs_jacobian_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C],
+                                            dv[i_W], dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em],
+                                            dv[i_rf], quantity, njac, jac_mol, npath, dv[i_f], sfc_per_path, g < 0 ? obs : ob->shard[g], dv[o_O],
+                                            dv[o_y], dv[o_kt], dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ks], ends, s->hs);
+    });
 }
 
 }  // extern "C"
