@@ -121,8 +121,10 @@ int monortm_hip_kat(void *ctx, int which, int n, const double *args, const doubl
  * (a Jacobian call makes several): 2 finish_mw_kernel (last wavenumber < 820 cm-1 and an ABSRB grid of <= 1000 points), 3
  * finish_kernel<HIGH> (last wavenumber > 1340 cm-1), 4 finish_kernel<PAR> (fewer than 16 x compute units (profile, layer) workgroups),
  * 5 finish_kernel<Q4> (four layers per wave: ABSRB grid <= 64 points, <= 128 wavenumbers), 6 finish_kernel with 64 threads (ABSRB
- * grid <= 256 points, <= 128 wavenumbers), 7 finish_kernel with 256 threads.  Counted on the host next to the launch; tests use them
- * to know which variant served a call.  A multi-device context returns the sum over its devices.  -1 for an unknown selector / NULL. */
+ * grid <= 256 points, <= 128 wavenumbers), 7 finish_kernel with 256 threads.  which = 16 .. 19 -> launches of far_kernel (the far field
+ * of dense grids, one launch per level of intervals and MODM evaluation) with 1, 2, 4, 8 waves per workgroup; 8 .. 15 are unknown.
+ * Counted on the host next to the launch; tests use them to know which variant served a call.  A multi-device context returns the
+ * sum over its devices.  -1 for an unknown selector / NULL. */
 long long monortm_hip_counter(void *ctx, int which);
 
 /* Physical line records (IFLG >= 0) held for molecule mol (1..39); mol = 0 -> all molecules.

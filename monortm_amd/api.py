@@ -210,6 +210,9 @@ def _quantity(q) -> int:
 # selectors 2 .. 7 of MonoRTM.counter(): launches of the continuum / cloud / total kernel by variant
 FINISH_VARIANTS = ("mw", "high", "par", "q4", "plain64", "plain256")
 FINISH_COUNTER0 = 2
+# selectors 16 .. 19: launches of far_kernel by waves per workgroup
+FAR_WAVES = (1, 2, 4, 8)
+FAR_COUNTER0 = 16
 
 SCAN_FIELDS = ("rup", "rdn", "trtot", "rad", "tb", "tmr")   # output order of monortm_hip_rtm_scan
 
@@ -428,7 +431,8 @@ class MonoRTM:
     def counter(self, which: int = 0) -> int:
         """monortm_hip_counter: 0 = rtm calls, 1 = rtm_scan calls that found O resident on the device; 2 .. 7 = launches of the
         continuum / cloud / total kernel by variant (FINISH_VARIANTS: finish_mw_kernel, finish_kernel<HIGH>, <PAR>, <Q4>, plain with
-        64 threads, plain with 256), one per MODM evaluation."""
+        64 threads, plain with 256), one per MODM evaluation; 16 .. 19 = launches of far_kernel with 1, 2, 4, 8 waves per workgroup
+        (FAR_WAVES), one per level of intervals and MODM evaluation."""
         return int(self.lib.monortm_hip_counter(self.ctx, which))
 
     def run(self, profiles: list[Profile]) -> list[Dump]:

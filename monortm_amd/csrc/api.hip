@@ -120,6 +120,8 @@ struct Ctx {
     // launches of the continuum / cloud / total kernel by variant (monortm_hip_counter 2 .. 7): finish_mw_kernel, finish_kernel<HIGH>,
     // <PAR>, <Q4>, plain with 64 threads, plain with 256
     long long finish_launches[6] = {0, 0, 0, 0, 0, 0};
+    // launches of far_kernel by waves per workgroup (monortm_hip_counter 16 .. 19): 1, 2, 4, 8 - one per level and MODM evaluation
+    long long far_launches[4] = {0, 0, 0, 0};
     // MONORTM_HOST_TIMING=1: wall time of the host-buffer calls by phase (pack, enqueue, wait, unpack), printed at finalize
     bool host_timing = false;
     double ht[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};   // modm, rtm, rtm_scan
@@ -1115,6 +1117,7 @@ long long monortm_hip_counter(void *ctx, int which) {
     if (which == 0) return c->o_reused;
     if (which == 1) return c->o_reused_scan;
     if (which >= 2 && which <= 7) return c->finish_launches[which - 2];
+    if (which >= 16 && which <= 19) return c->far_launches[which - 16];
     return -1;
 }
 
@@ -1542,7 +1545,7 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
             if (far_on) {
                 HIPCHK(c, hipStreamWaitEvent(s, c->far_ev[1], 0));
                 launch_far(a, c->lines, c->tables, 0.5 * TW * (vends[1] - vends[0]) / (double)std::max(nwn - 1, 1),
-                           c->lines_per_cm > 0. ? c->lines_per_cm : 1., s);
+                           c->lines_per_cm > 0. ? c->lines_per_cm : 1., c->far_launches, s);
             }
         }
     }

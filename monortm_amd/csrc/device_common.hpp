@@ -403,7 +403,8 @@ void launch_physics(const ModmArgs &a, const DevLines &L, const DevTables &tb, i
 // far_kernel.hip: far_plan_kernel (which lines are far for which interval; independent of physics_kernel), then far_kernel per level,
 // top level first (reads the plan and physics_kernel's records)
 void launch_far_plan(const ModmArgs &a, const DevLines &L, const DevTables &tb, hipStream_t s);
-void launch_far(const ModmArgs &a, const DevLines &L, const DevTables &tb, double rho_tile, double lines_per_cm, hipStream_t s);
+void launch_far(const ModmArgs &a, const DevLines &L, const DevTables &tb, double rho_tile, double lines_per_cm, long long *launches,
+                hipStream_t s);   // launches[4]: += 1 per level at the entry of its waves per workgroup (1, 2, 4, 8)
 void launch_lines(const ModmArgs &a, const DevLines &L, const DevTables &tb, int nw, int wpl, bool ibrd, dim3 grid, size_t dyn_lds,
                   hipStream_t s);
 // continuum_kernel.hip: high = spectral range reaches above 1340 cm-1; par = passes side by side in the waves of a

@@ -526,7 +526,9 @@ void launch_far_plan(const ModmArgs &a, const DevLines &L, const DevTables &tb, 
     else hipLaunchKernelGGL(far_plan_kernel<double>, pgrid, dim3(64), 0, s, a, L, tb);
 }
 // rho_tile: half-width of a tile, lines_per_cm: lines of the table per cm-1 (both estimates of the host: they size the workgroups)
-void launch_far(const ModmArgs &a, const DevLines &L, const DevTables &tb, double rho_tile, double lines_per_cm, hipStream_t s) {
+// launches[4]: the caller's count of far_kernel launches by waves per workgroup (1, 2, 4, 8)
+void launch_far(const ModmArgs &a, const DevLines &L, const DevTables &tb, double rho_tile, double lines_per_cm, long long *launches,
+                hipStream_t s) {
     static const int nwf_env = getenv("MONORTM_FAR_WAVES") ? atoi(getenv("MONORTM_FAR_WAVES")) : 0;   // A/B switch for measurements
     for (int l = a.far_levels - 1; l >= 0; l--) {
         const int nint = far_level_count(a.far_ntile, l);
@@ -570,6 +572,7 @@ void launch_far(const ModmArgs &a, const DevLines &L, const DevTables &tb, doubl
         else if (nwf <= 4) FAR_LAUNCH(4);
         else FAR_LAUNCH(8);
 #undef FAR_LAUNCH
+        launches[nwf <= 1 ? 0 : (nwf == 2 ? 1 : (nwf <= 4 ? 2 : 3))]++;
     }
 }
 }  // namespace monortm_dev

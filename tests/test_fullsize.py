@@ -5,15 +5,10 @@ import numpy as np
 import pytest
 
 from common import RTOL, compare
+from far_cases import _subset
 from monortm_amd import api, synth, tape3
-from monortm_amd.tape3 import LineRecords
 
 pytestmark = pytest.mark.gpu
-
-
-def _subset(rec: LineRecords, sel) -> LineRecords:
-    return LineRecords(**{k: getattr(rec, k)[sel] for k in ("vnu", "sp", "alfa", "epp", "mol", "hwhm", "tmpalf", "pshift", "iflg",
-                                                             "brd_flg", "brd_dat", "sdep")})
 
 
 def test_c4_shard_full_size(workdir):
