@@ -424,6 +424,61 @@ int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn
                                  monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_SFC,
                                  const double *wn_ends, void *stream);
 
+/* ---- The forward measurement operator: channel- and beam-averaged scans, y = F(x) without K (no reference counterpart; the radiance
+ * recurrence along every path is RTM's, src/RTMmono.f90:13-221).  DESIGN.md section 3.10.
+ *   Y[p][v][c] = sum_{j in view v} wpath[j] sum_{i: chan[i] = c} wchan[i] q[p][j][i]
+ * for a measurement operator of monortm_hip_obs_create, contracted inside the kernel that forms the monochromatic radiances
+ * (rtm_obs_kernel.hip): none of them reaches memory.  The forward half of the entries above - the same owner thread per element, the
+ * same fixed order of additions (paths ascending within a tile of 4, wavenumbers ascending within a block of 64, tiles ascending,
+ * blocks ascending within a tile), no atomics: repeated calls give the same bits, and a profile gives the same bits alone and inside
+ * a batch.  Empty views and channels without a sample are 0.
+ *   quantity 0: q = RAD;  1: q = TB, the mean of the monochromatic brightness temperatures;
+ *   quantity 2: the band brightness temperature - RAD is contracted (the power a radiometer integrates over its passband and beam)
+ *     and the finished element converted at the channel's nominal wavenumber,
+ *       Y = RADCN2 vcen[c] / log(RADCN1 vcen[c]^3 / Y_rad + 1).
+ *     The conversion takes the contracted radiance as the band's MEAN radiance: normalising the weights (sum of wpath x wchan = 1 per
+ *     measurement) is the caller's business, as everywhere for these operators.  An element without a sample stays 0; one whose
+ *     contracted radiance is <= 0 or not finite (weights of mixed sign) is NaN.
+ * vcen [nchan] doubles: read for quantity 2 only (may be NULL otherwise).  Host entries check it for the whole call - every value finite
+ * and > 0, MONORTM_EARG otherwise, nothing launched; device entries take a device pointer, a bad value surfaces through
+ * monortm_hip_check (MONORTM_EARG).  Y [nprof][nview][nchan] in the context's real type; tmpsfc is input only; npath and nwn must be
+ * the operator's; the other arguments and refusals as monortm_hip_rtm_scan.
+ *
+ * From a given O: real_kind 8 and 4.  Host buffers: sharded by profile like monortm_hip_rtm_scan, nlay, the factors, the handle and
+ * vcen of the whole call checked first; with real_kind 4 the sums are held (and the band temperature formed) in double and rounded
+ * once.  O is always uploaded: the one-call entry below is the route without a copy. */
+int monortm_hip_rtm_obs(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                        int quantity, const monortm_real *T, const monortm_real *TZ, const monortm_real *O, const monortm_real *path,
+                        const monortm_real *tmpsfc, int sfc_per_path, const monortm_real *emiss, const monortm_real *reflc, int obs,
+                        const double *vcen, monortm_real *Y);
+/* The same on device pointers, asynchronous on `stream`; one-device context.  Allocates and copies nothing.  A bad factor of an active
+ * layer or a bad vcen surfaces through monortm_hip_check (MONORTM_EARG).  With real_kind 4, Y itself holds the running sum: one float
+ * rounding per (tile of paths, block of wavenumbers) that contributes to an element, then (quantity 2) the conversion. */
+int monortm_hip_rtm_obs_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                            int quantity, const monortm_real *T, const monortm_real *TZ, const monortm_real *O,
+                            const monortm_real *path, const monortm_real *tmpsfc, int sfc_per_path, const monortm_real *emiss,
+                            const monortm_real *reflc, int obs, const double *vcen, monortm_real *Y, void *stream);
+
+/* MODM + the forward operator (no reference counterpart; MODM as monortm_hip_modm, the recurrence src/RTMmono.f90:13-221): ONE MODM
+ * pass, then ONE launch of the forward kernel.  O returns the vertical optical depths exactly as monortm_hip_modm does.  real_kind 8
+ * AND 4: nothing is perturbed, so none of the Jacobian entries' refusals applies.  Cross-section molecules: run monortm_hip_modm_xs
+ * and hand its O to monortm_hip_rtm_obs. */
+int monortm_hip_obs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                    const monortm_real *P, const monortm_real *T, const monortm_real *CLW, const monortm_real *WKL,
+                    const monortm_real *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd,
+                    const int *irt, const monortm_real *TZ, const monortm_real *tmpsfc, const monortm_real *emiss,
+                    const monortm_real *reflc, int quantity, int npath, const monortm_real *path, int sfc_per_path, int obs,
+                    const double *vcen, monortm_real *O, monortm_real *Y);
+/* The same on device pointers, asynchronous on `stream`; one-device context, nprof <= 65535.  wn_ends as for monortm_hip_modm_dev.
+ * Device-side failures (temperature range, bad factors, bad vcen) surface through monortm_hip_check.  After one call, a second of the
+ * same shapes allocates nothing (graph capture); the launch of the forward kernel itself never allocates. */
+int monortm_hip_obs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                        const monortm_real *P, const monortm_real *T, const monortm_real *CLW, const monortm_real *WKL,
+                        const monortm_real *WBRODL, const double *cntnm_fac /*host*/, double sclcpl, double sclhw, double y0res,
+                        int ibrd, const int *irt, const monortm_real *TZ, const monortm_real *tmpsfc, const monortm_real *emiss,
+                        const monortm_real *reflc, int quantity, int npath, const monortm_real *path, int sfc_per_path, int obs,
+                        const double *vcen, monortm_real *O, monortm_real *Y, const double *wn_ends, void *stream);
+
 /* Device-side failure flags raised by the kernels of earlier *_dev calls (temperature range, SD-Voigt
  * sign): synchronises `stream`, returns MONORTM_OK or the first error and clears the flags. */
 int monortm_hip_check(void *ctx, void *stream);

@@ -18,8 +18,8 @@ LIB = os.path.join(LIBDIR, "libmonortm_hip.so")
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FC = os.environ.get("MONORTM_FC", "/opt/rocm/bin/amdflang")
-HIP_SOURCES = ["api.hip", "lines_kernel.hip", "lines_ms_kernel.hip", "far_kernel.hip", "continuum_kernel.hip", "xsec_kernel.hip", "rtm_kernel.hip", "rtm_scan_kernel.hip", "jacobian_kernel.hip", "rtm_scan_jac_kernel.hip", "rtm_obs_jac_kernel.hip", "line_table.cpp"]
-HIP_DEPS = HIP_SOURCES + ["device_common.hpp", "lineshape.hpp", "cloud_tkc.hpp", "lines_device.hpp", "lines_asm.hpp", "lines_ms_asm.hpp", "line_table.hpp", "tables/monortm_tables.h",
+HIP_SOURCES = ["api.hip", "lines_kernel.hip", "lines_ms_kernel.hip", "far_kernel.hip", "continuum_kernel.hip", "xsec_kernel.hip", "rtm_kernel.hip", "rtm_scan_kernel.hip", "jacobian_kernel.hip", "rtm_scan_jac_kernel.hip", "rtm_obs_jac_kernel.hip", "rtm_obs_kernel.hip", "line_table.cpp"]
+HIP_DEPS = HIP_SOURCES + ["device_common.hpp", "lineshape.hpp", "cloud_tkc.hpp", "obs_exchange.hpp", "lines_device.hpp", "lines_asm.hpp", "lines_ms_asm.hpp", "line_table.hpp", "tables/monortm_tables.h",
                            "../../include/monortm_hip.h"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value", "-Wno-pass-failed",
              "-Wno-unused-const-variable"]
@@ -34,8 +34,15 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "
 # continuum_kernel.hip: finish_mw_kernel 0.106 -> 0.089 ms on configs[3] whole, 0.107 -> 0.090 on configs[4] whole, 0.0180 -> 0.0166 on the
 # 128-profile shard (a latency chain at eight waves per SIMD: fewer live constants, fewer scalar spills).  far_kernel.hip and
 # rtm_kernel.hip: no gain / 3 % worse - they keep the default.
+# rtm_obs_kernel.hip: the forward arithmetic of rtm_scan_kernel inside a loop over path tiles and wavenumber blocks.  With the default
+# the constants of its exponentials are hoisted out of both loops and stay live across them: 162 VGPRs, 122 - 163 SGPR spills, 3 waves per
+# SIMD (ONE 512-thread workgroup per CU) where the straight-line rtm_scan_kernel has 114 VGPRs and 4.  Without the hoisting: 108 VGPRs,
+# 70 - 86 SGPR spills, 4 waves per SIMD, no scratch either way, identical results (every test of tests/test_obs_forward.py, and Y
+# bit-equal to rtm_obs_jac_kernel's).  tools/obs_bench.py, the two builds in turn, twice: DeviceBatch.obs 1.396 -> 1.278 ms at 16 paths,
+# 2.557 -> 2.114 ms at 64 (the kernel's own share 0.365 -> 0.25 and 1.51 -> 1.07 ms; LABNOTES section 20).  rtm_obs_jac_kernel.hip keeps
+# the default: its resource table is pinned by DESIGN section 3.9.
 _NO_LICM = ["-mllvm", "-disable-machine-licm"]
-HIP_FILE_FLAGS = {"lines_ms_kernel.hip": _NO_LICM, "lines_kernel.hip": _NO_LICM, "continuum_kernel.hip": _NO_LICM}
+HIP_FILE_FLAGS = {"lines_ms_kernel.hip": _NO_LICM, "lines_kernel.hip": _NO_LICM, "continuum_kernel.hip": _NO_LICM, "rtm_obs_kernel.hip": _NO_LICM}
 
 
 def _check_flags(flags: list[str]) -> None:

@@ -92,6 +92,16 @@ SYMBOLS = {
     "monortm_hip_obs_jacobian_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                                C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
                                                C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 9),
+    "monortm_hip_rtm_obs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                      _vp, _vp, C.c_int, _vp, _vp]),
+    "monortm_hip_rtm_obs_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                          _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "monortm_hip_obs": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int,
+                                  C.c_int, _vp, _vp, _vp]),
+    "monortm_hip_obs_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int,
+                                      C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "monortm_hip_check": (C.c_int, [_vp, _vp]),
     "monortm_hip_profile": (C.c_int, [_vp, C.c_int]),
     "monortm_hip_kernel_time": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_longlong)]),
@@ -108,6 +118,8 @@ SCAN_JAC_RTM_FIELDS = ("rad", "tb", "k_o", "k_path", "k_t", "k_tz", "k_sfc")    
 SCAN_JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_path", "k_sfc")   # ... of monortm_hip_scan_jacobian
 OBS_JAC_RTM_FIELDS = ("y", "k_t", "k_tz", "k_sfc")                                           # output order of monortm_hip_rtm_obs_jac
 OBS_JAC_FIELDS = ("o", "y", "k_t", "k_tz", "k_w", "k_clw", "k_sfc")                           # ... of monortm_hip_obs_jacobian
+OBS_RTM_FIELDS = ("y",)                                                                      # ... of monortm_hip_rtm_obs
+OBS_FIELDS = ("o", "y")                                                                      # ... of monortm_hip_obs
 OBS_MAX_PATHS, OBS_MAX_WN, OBS_MAX_VIEWS, OBS_MAX_CHAN = 16384, 80000, 65535, 65536           # the bounds of monortm_hip_obs_create
 
 
@@ -200,11 +212,77 @@ class ObsOperator:
         return cls(vs, wp, ch, wc, nchan=len(channels)), perm
 
 
-def _quantity(q) -> int:
-    """'tb' -> 1, 'rad' -> 0; an int is passed through unchanged (the C ABI checks it)."""
+class _BadQuantity(KeyError, ValueError):
+    """An unknown quantity name: the KeyError it has always been, and a ValueError for callers that catch bad arguments."""
+
+
+def _quantity(q, band: bool = False) -> int:
+    """'tb' -> 1, 'rad' -> 0 and, for the forward measurement operator only (band=True), 'band_tb' -> 2; an int is passed through
+    unchanged (the C ABI checks it)."""
     if isinstance(q, str):
-        return {"tb": 1, "rad": 0}[q.lower()]
+        names = {"tb": 1, "rad": 0, "band_tb": 2} if band else {"tb": 1, "rad": 0}
+        if q.lower() not in names:
+            raise _BadQuantity(q)
+        return names[q.lower()]
     return int(q)
+
+
+# the radiation constants as the kernels hold them (K_RADCN1, K_RADCN2 of device_common.hpp; src/PhysConstants.f90)
+RADCN1 = 1.191042722E-12
+RADCN2 = 1.4387752
+
+
+def _band_args(vcen, rad):
+    v, r = np.asarray(vcen, np.float64), np.asarray(rad, np.float64)
+    if v.ndim != 1 or r.ndim < 1 or r.shape[-1] != len(v):
+        raise ValueError(f"vcen must be [nchan] and rad [..., nchan], got {v.shape} and {r.shape}")
+    if not np.all(np.isfinite(v) & (v > 0.)):
+        raise ValueError("vcen: every value finite and > 0")
+    return v, r
+
+
+def band_tb(vcen, rad) -> np.ndarray:
+    """The band brightness temperature of contracted radiances rad [..., nchan] at the channels' nominal wavenumbers vcen [nchan]
+    (quantity "band_tb" of MonoRTM.obs / rtm_obs, evaluated on the host in float64):
+        TB = RADCN2 vcen / log(RADCN1 vcen^3 / rad + 1).
+    An element that is exactly 0 (no sample: an empty view or channel) stays 0; one that is negative or not finite is NaN."""
+    v, r = _band_args(vcen, rad)
+    ok = np.isfinite(r) & (r > 0.)
+    out = np.where(r == 0., 0., np.nan)
+    c3 = np.broadcast_to(RADCN1 * (v * v * v), r.shape)
+    vv = np.broadcast_to(v, r.shape)
+    out[ok] = RADCN2 * vv[ok] / np.log(c3[ok] / r[ok] + 1.)
+    return out
+
+
+def band_tb_slope(vcen, rad) -> np.ndarray:
+    """dTB/dRAD of band_tb: RADCN2 v RADCN1 v^3 / (log(X)^2 X rad^2) with X = RADCN1 v^3 / rad + 1 (the factor of DESIGN.md section
+    3.6).  Band-TB Jacobians from the radiance Jacobians of obs_jacobian(quantity="rad"):
+        K_band = band_tb_slope(vcen, y_rad)[..., None, :] * K_rad.
+    Elements without a temperature (rad <= 0 or not finite) are NaN, those without a sample (rad == 0) are 0."""
+    v, r = _band_args(vcen, rad)
+    ok = np.isfinite(r) & (r > 0.)
+    out = np.where(r == 0., 0., np.nan)
+    c3 = np.broadcast_to(RADCN1 * (v * v * v), r.shape)[ok]
+    vv = np.broadcast_to(v, r.shape)[ok]
+    x = c3 / r[ok] + 1.
+    lx = np.log(x)
+    out[ok] = (RADCN2 * vv) * ((c3 / r[ok]) / x) / ((lx * lx) * r[ok])   # rad enters once per factor: rad^2 underflows for a cold band
+    return out
+
+
+def _vcen(vcen, quantity: int, nchan: int):
+    """The vcen argument of the forward entries: required, [nchan], finite and > 0 for quantity 2; ignored otherwise."""
+    if quantity != 2:
+        return None
+    if vcen is None:
+        raise ValueError("quantity 'band_tb' needs vcen [nchan], the channels' nominal wavenumbers")
+    v = np.ascontiguousarray(vcen, np.float64)
+    if v.shape != (nchan,):
+        raise ValueError(f"vcen must be [{nchan}], got {v.shape}")
+    if not np.all(np.isfinite(v) & (v > 0.)):
+        raise ValueError("vcen: every value finite and > 0")
+    return v
 
 
 # selectors 2 .. 7 of MonoRTM.counter(): launches of the continuum / cloud / total kernel by variant
@@ -643,6 +721,60 @@ class MonoRTM:
                                                     *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS]))
         return out
 
+    # ---- the forward measurement operator (monortm_hip_rtm_obs / monortm_hip_obs) ------------------------------
+    def rtm_obs(self, profiles: list[Profile], O: np.ndarray, path, obs: int, quantity="tb", emiss=None, reflc=None, vcen=None) -> dict:
+        """y = F(x) per measurement from one O [nprof, nlay_max, nwn]: the radiances of rtm_scan contracted with the operator `obs`
+        (a handle of obs_create) inside the kernel, in the fixed order of rtm_obs_jacobian's y.  quantity: "rad", "tb" (the mean of the
+        monochromatic brightness temperatures) or "band_tb" (the contracted radiance converted at the channels' nominal wavenumbers
+        vcen [nchan]: see band_tb; the weights must be normalised per measurement).  Works for both real kinds and for an O of
+        modm() with cross-section molecules.  Dict of y [nprof, nview, nchan]."""
+        q = _quantity(quantity, band=True)
+        nv, nc = self._obs_shape(obs)
+        vc = _vcen(vcen, q, nc)
+        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
+        dt = self.dtype
+        f = self._path(path, nprof, lm)
+        npath = f.shape[1]
+        em, rf = self._scan_sfc(em, rf, emiss, reflc, nprof, npath, nwn)
+        O = _np(O, dt)
+        if O.shape != (nprof, lm, nwn):
+            raise ValueError(f"O must be [{nprof}, {lm}, {nwn}], got {O.shape}")
+        out = dict(y=np.zeros((nprof, nv, nc), dt))
+        wn = _np(profiles[0].wn)
+        self._chk(self.lib.monortm_hip_rtm_obs(self.ctx, nprof, npath, nwn, _ptr(wn), _ptr(nlay), lm, _ptr(irt), q, _ptr(T), _ptr(TZ), _ptr(O),
+                                               _ptr(f), _ptr(ts), int(em.ndim == 3), _ptr(em), _ptr(rf), int(obs), _ptr(vc),
+                                               *[_ptr(out[k]) for k in OBS_RTM_FIELDS]))
+        return out
+
+    def obs(self, profiles: list[Profile], path, obs: int, quantity="tb", emiss=None, reflc=None, vcen=None) -> dict:
+        """MODM ONCE + the forward measurement operator (both real kinds): dict of o [nprof, nlay_max, nwn] (the vertical optical
+        depths, as modm() returns them) and y [nprof, nview, nchan]; the arguments of rtm_obs."""
+        q = _quantity(quantity, band=True)
+        nv, nc = self._obs_shape(obs)
+        vc = _vcen(vcen, q, nc)
+        p0 = profiles[0]
+        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
+        nmol, dt = p0.nmol, self.dtype
+        f = self._path(path, nprof, lm)
+        npath = f.shape[1]
+        em, rf = self._scan_sfc(em, rf, emiss, reflc, nprof, npath, nwn)
+
+        def pack(get, width=None):
+            out = np.zeros((nprof, lm) if width is None else (nprof, lm, width), dt)
+            for i, p in enumerate(profiles):
+                out[i, : p.nlay] = get(p)
+            return out
+
+        P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
+        WKL = pack(lambda p: p.wkl, nmol)
+        out = dict(o=np.zeros((nprof, lm, nwn), dt), y=np.zeros((nprof, nv, nc), dt))
+        wn, fac = _np(p0.wn), _np(p0.cntnm)
+        self._chk(self.lib.monortm_hip_obs(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T), _ptr(CLW),
+                                           _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, _ptr(irt), _ptr(TZ),
+                                           _ptr(ts), _ptr(em), _ptr(rf), q, npath, _ptr(f), int(em.ndim == 3), int(obs), _ptr(vc),
+                                           *[_ptr(out[k]) for k in OBS_FIELDS]))
+        return out
+
     # ---- the C-ABI gather of a profile-sharded job (RCCL; what a C / Fortran caller uses instead of torch.distributed) ------
     @staticmethod
     def comm_unique_id() -> bytes:
@@ -916,6 +1048,56 @@ class DeviceBatch:
                                                  *[d(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS],
                                                  _ptr(self.wn_ends), _vp(s.cuda_stream)))
         return out
+
+    # ---- the forward measurement operator on the resident batch (monortm_hip_modm_dev + monortm_hip_rtm_obs_dev) ------------------------
+    def obs(self, path, obs: int, quantity="tb", vcen=None, stream=None):
+        """y = F(x) per measurement on the current (or the given) stream, asynchronously: the batch's MODM step (into its resident O,
+        as step() and scan() run it), then the forward kernel on that O.  Returns y [nprof, nview, nchan], a torch tensor; obs is a
+        handle of rt.obs_create, quantity and vcen as MonoRTM.obs.  The output, the device copy of the factors and of vcen are
+        allocated at the first call for (obs, npath, quantity), overwritten by every later one and dropped at the first call after
+        rt.obs_destroy(obs), so that a graph capture of the call (after one warm call, with the factors in a tensor on the batch's
+        device) replays into the same tensor.  path as DeviceBatch.scan; TMPSFC is the profiles' own (input only).  Bad factors and a
+        bad vcen surface through check()."""
+        t = self.torch
+        real = t.float32 if self.rt.real_kind == 4 else t.float64  # dtype of the REAL arrays
+        q = _quantity(quantity, band=True)
+        f = t.as_tensor(path)
+        if f.dim() == 2:
+            f = f.unsqueeze(0).expand(self.nprof, -1, -1)
+        if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
+            raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
+        npath = int(f.shape[1])
+        key = (int(obs), npath, q)
+        cache = self.__dict__.setdefault("_obs_fwd", {})
+        live = self.rt.__dict__.get("_obs", {})
+        for k in [k for k in cache if k[0] not in live]:   # operators destroyed since: handles are never reused, let their tensors go
+            del cache[k]
+        nv, nc = self.rt._obs_shape(obs)
+        if key not in cache:
+            cache[key] = (t.zeros(self.nprof, nv, nc, dtype=real, device=self.dev), t.zeros(self.nprof, npath, self.lm, dtype=real, device=self.dev),
+                          t.ones(nc, dtype=t.float64, device=self.dev) if q == 2 else None)
+        y, fd, vd = cache[key]
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        with t.cuda.stream(s):
+            fd.copy_(f, non_blocking=True)
+            if q == 2:
+                if vcen is None:
+                    raise ValueError("quantity 'band_tb' needs vcen [nchan], the channels' nominal wavenumbers")
+                v = t.as_tensor(vcen)
+                if tuple(v.shape) != (nc,):
+                    raise ValueError(f"vcen must be [{nc}], got {tuple(v.shape)}")
+                vd.copy_(v, non_blocking=True)
+        sp = _vp(s.cuda_stream)
+        p0, lib, rt = self.p0, self.rt.lib, self.rt
+        d = lambda x: _vp(x.data_ptr())  # noqa: E731
+        rt._chk(lib.monortm_hip_modm_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol,
+                                         d(self.P), d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl,
+                                         p0.sclhw, p0.y0res, p0.ibrd, 0, d(self.O), d(self.OBM), d(self.OC), d(self.OCLW), _ptr(self.wn_ends),
+                                         sp))
+        rt._chk(lib.monortm_hip_rtm_obs_dev(rt.ctx, self.nprof, npath, self.nwn, d(self.wn), d(self.nlay), self.lm, d(self.irt), q,
+                                            d(self.T), d(self.TZ), d(self.O), d(fd), d(self.tmpsfc0), 0, d(self.emiss), d(self.reflc),
+                                            int(obs), d(vd) if q == 2 else None, d(y), sp))
+        return y
 
     # ---- HIP graph: the three launches of a step recorded once, replayed with a single call ------------------
     def capture(self):

@@ -357,7 +357,7 @@ namespace {
 int decode_flag(Ctx *c, int flag, hipStream_t s) {
     if (!flag) return MONORTM_OK;
     HIPCHK(c, hipMemsetAsync(c->errflag, 0, sizeof(int), s));
-    if (flag & ERRBIT_ARG) { c->err = "device arguments: nlay[p] outside 1..nlay_max, wavenumbers not ascending or not the grid dvset promises, or a negative / non-finite path factor (monortm_hip_rtm_scan_dev, monortm_hip_rtm_scan_jac_dev, monortm_hip_scan_jacobian_dev)"; return MONORTM_EARG; }
+    if (flag & ERRBIT_ARG) { c->err = "device arguments: nlay[p] outside 1..nlay_max, wavenumbers not ascending or not the grid dvset promises, or a negative / non-finite path factor (monortm_hip_rtm_scan_dev, monortm_hip_rtm_scan_jac_dev, monortm_hip_scan_jacobian_dev), or a vcen that is not finite and > 0 (monortm_hip_rtm_obs_dev, monortm_hip_obs_dev)"; return MONORTM_EARG; }
     if (flag & ERRBIT_TEMP) { c->err = "TIPS: layer temperature outside 70-3000 K / partition sum <= 0 (reference STOP, tips_2003.f90:277)"; return MONORTM_ETEMP; }
     c->err = "SDVOIGT: REAL(v) < 0 (reference STOP, modm.f90:1062)";
     return MONORTM_ESDV;
@@ -2353,6 +2353,178 @@ int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, do
                                             dv[i_W], dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em],
                                             dv[i_rf], quantity, njac, jac_mol, npath, dv[i_f], sfc_per_path, g < 0 ? obs : ob->shard[g], dv[o_O],
                                             dv[o_y], dv[o_kt], dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ks], ends, s->hs);
+    });
+}
+
+// ---- the forward measurement operator: channel- and beam-averaged scans ------------------------------
+}  // extern "C"
+
+namespace {
+int obs_check_quantity(Ctx *c, int quantity) {
+    if (quantity < 0 || quantity > 2) { c->err = "quantity must be 0 (RAD), 1 (TB) or 2 (band TB)"; return MONORTM_EARG; }
+    return MONORTM_OK;
+}
+// the channels' nominal wavenumbers of a host call (quantity 2 only): all of them, before anything is staged
+int obs_check_vcen(Ctx *c, int quantity, const double *vcen, int nchan) {
+    if (quantity != 2) return MONORTM_OK;
+    if (!vcen) { c->err = "quantity 2 (band TB) needs vcen [nchan]"; return MONORTM_EARG; }
+    for (int i = 0; i < nchan; i++)
+        if (!(vcen[i] > 0. && std::isfinite(vcen[i]))) { c->err = "vcen[" + std::to_string(i) + "] is not a finite wavenumber > 0"; return MONORTM_EARG; }
+    return MONORTM_OK;
+}
+
+// monortm_hip_rtm_obs_dev with the element size of Y as an argument: the host entry of a real_kind = 4 context has the kernel accumulate
+// (and convert to the band temperature) in double and rounds once, when it unpacks
+int rtm_obs_dev_impl(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
+                     const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path, const void *emiss,
+                     const void *reflc, int obs, const double *vcen, void *Y, int out_kind, void *stream) {
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !Y) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (int rcq = obs_check_quantity(c, quantity)) return rcq;
+    if (quantity == 2 && !vcen) { c->err = "quantity 2 (band TB) needs vcen [nchan]"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
+    if (int rcd = check_device(c)) return rcd;
+    RtmObsArgs a{};
+    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = c->real_kind;
+    a.sfc_per_path = sfc_per_path;
+    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    a.nview = ob->nview; a.nchan = ob->nchan;
+    a.view_start = ob->view_start; a.wpath = ob->wpath; a.mstart = ob->mstart; a.mlane = ob->mlane; a.mw = ob->mw;
+    a.vcen = quantity == 2 ? vcen : nullptr;
+    a.Y = Y;
+    a.errflag = c->errflag;
+    launch_rtm_obs(a, out_kind, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+// monortm_hip_obs_dev likewise: ONE MODM pass into the caller's O (the MODM outputs the operator does not use go to the context's
+// workspace, grown on demand and kept), then ONE launch of the forward kernel
+int obs_dev_impl(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P, const void *T,
+                 const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd,
+                 const int *irt, const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int npath,
+                 const void *path, int sfc_per_path, int obs, const double *vcen, void *O, void *Y, int out_kind, const double *wn_ends,
+                 void *stream) {
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !Y) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (int rcq = obs_check_quantity(c, quantity)) return rcq;
+    if (quantity == 2 && !vcen) { c->err = "quantity 2 (band TB) needs vcen [nchan]"; return MONORTM_EARG; }
+    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
+    if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
+    if (int rcd = check_device(c)) return rcd;
+    const size_t st = (size_t)nprof * nlay_max * nwn * (size_t)c->real_kind;   // bytes of one [nprof][nlay_max][nwn] array
+    Arena ws;
+    const size_t w_OM = ws.add(st * nmol), w_OC = ws.add(st * MONORTM_NCONT), w_OL = ws.add(st);
+    if (ws.size > c->jac_ws_bytes) {   // (the Jacobian entries' workspace: whichever call needs more grows it)
+        if (c->jac_ws) HIPCHK(c, hipFree(c->jac_ws));
+        c->jac_ws = nullptr;
+        c->jac_ws_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->jac_ws, ws.size));
+        c->jac_ws_bytes = ws.size;
+    }
+    char *wb = static_cast<char *>(c->jac_ws);
+    if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
+                                         ibrd, 0, nullptr, nullptr, O, wb + w_OM, wb + w_OC, wb + w_OL, wn_ends, stream))
+        return rc;
+    return rtm_obs_dev_impl(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, obs, vcen,
+                            Y, out_kind, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int monortm_hip_rtm_obs_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                            int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path,
+                            const void *emiss, const void *reflc, int obs, const double *vcen, void *Y, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    return rtm_obs_dev_impl(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, obs, vcen,
+                            Y, c->real_kind, stream);
+}
+
+int monortm_hip_obs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
+                        const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl,
+                        double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc, const void *emiss,
+                        const void *reflc, int quantity, int npath, const void *path, int sfc_per_path, int obs, const double *vcen, void *O,
+                        void *Y, const double *wn_ends, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    return obs_dev_impl(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt, TZ,
+                        tmpsfc, emiss, reflc, quantity, npath, path, sfc_per_path, obs, vcen, O, Y, c->real_kind, wn_ends, stream);
+}
+
+int monortm_hip_rtm_obs(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
+                        const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path, const void *emiss,
+                        const void *reflc, int obs, const double *vcen, void *Y) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    DeviceGuard guard;
+    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !Y) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (int rc = obs_check_quantity(c, quantity)) return rc;
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
+    if (int rc = obs_check_vcen(c, quantity, vcen, ob->nchan)) return rc;
+    // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
+    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vs = (size_t)nwn * (sfc_per_path ? npath : 1) * d;
+    HostCall hc(4);   // (the scan slots: lastO, which points into the MODM slots, stays valid)
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
+              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, l * nwn), i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs),
+              i_rf = hc.in(reflc, vs), i_vc = hc.in_shared(quantity == 2 ? vcen : nullptr, ob->nchan * sizeof(double));
+    // the kernel accumulates into a double Y (out_kind 8) whatever the context's REAL kind: rounded once, when it is unpacked
+    const int o_y = hc.out_widened(Y, (size_t)ob->nview * ob->nchan);
+    return hc.run(c, nprof, [&](Ctx *s, int g, int n, char *const *dv) {   // (every shard holds the operator under a handle of its own)
+        return rtm_obs_dev_impl(s, n, npath, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], quantity, dv[i_T], dv[i_TZ],
+                                dv[i_O], dv[i_f], dv[i_ts], sfc_per_path, dv[i_em], dv[i_rf], g < 0 ? obs : ob->shard[g], (double *)dv[i_vc],
+                                dv[o_y], 8, s->hs);
+    });
+}
+
+int monortm_hip_obs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
+                    const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
+                    double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc,
+                    int quantity, int npath, const void *path, int sfc_per_path, int obs, const double *vcen, void *O, void *Y) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !Y) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    DeviceGuard guard;
+    // the whole call is checked before the first device is touched: a refusal launches nothing anywhere
+    if (int rc = obs_check_quantity(c, quantity)) return rc;
+    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
+    if (int rc = obs_check_vcen(c, quantity, vcen, ob->nchan)) return rc;
+    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
+    for (int i = 1; i < nwn; i++)
+        if (!(wn[i] >= wn[i - 1])) { c->err = "wavenumbers must be ascending (the reference takes v1 = wn(1), v2 = wn(nwn), modm.f90:180-181)"; return MONORTM_EARG; }
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vs = (size_t)nwn * (sfc_per_path ? npath : 1) * d;
+    HostCall hc(8);   // (the Jacobian slots: a call between a MODM and an RTM call leaves lastO alone)
+    hc.flag = true;
+    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
+              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l), i_TZ = hc.in(TZ, l + d),
+              i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs), i_rf = hc.in(reflc, vs),
+              i_vc = hc.in_shared(quantity == 2 ? vcen : nullptr, ob->nchan * sizeof(double));
+    const int o_O = hc.out(O, l * nwn), o_y = hc.out_widened(Y, (size_t)ob->nview * ob->nchan);
+    return hc.run(c, nprof, [&](Ctx *s, int g, int n, char *const *dv) {   // (every shard holds the operator under a handle of its own)
+        const double ends[2] = {wn[0], wn[nwn - 1]};
+        return obs_dev_impl(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C], dv[i_W], dv[i_B],
+                            cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em], dv[i_rf], quantity, npath,
+                            dv[i_f], sfc_per_path, g < 0 ? obs : ob->shard[g], (double *)dv[i_vc], dv[o_O], dv[o_y], 8, ends, s->hs);
     });
 }
 

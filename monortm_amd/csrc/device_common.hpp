@@ -258,6 +258,20 @@ struct RtmObsJacArgs {
     double dt, dlnw;
     int *errflag;
 };
+// The forward measurement operator (rtm_obs_kernel.hip): the inputs of RtmScanArgs (tmpsfc: input only) and the
+// device tables of a measurement operator as in RtmObsJacArgs; quantity 0 / 1: q = RAD / TB, 2: the band brightness temperature - RAD
+// is contracted and the finished element converted at the channel's nominal wavenumber vcen [nchan] (read for quantity 2 only; a value
+// that is not finite and > 0 raises ERRBIT_ARG).  Output Y [nprof][nview][nchan].
+struct RtmObsArgs {
+    int nprof, npath, nwn, nlay_max, quantity, real_kind, sfc_per_path, nview, nchan;
+    const double *wn;
+    const void *T, *TZ, *O, *path, *tmpsfc, *emiss, *reflc;
+    const int *nlay, *irt;
+    const int *view_start, *mstart, *mlane;
+    const double *wpath, *mw, *vcen;
+    void *Y;
+    int *errflag;
+};
 // the MODM inputs of the base (state 0) and the perturbed states, [nstate][nprof][nlay_max](x nmol), real_kind 8
 struct JacPerturbArgs {
     int nstate, nprof, nlay_max, nmol;
@@ -454,5 +468,7 @@ void launch_rtm_scan_jac(const RtmScanJacArgs &a, bool full, hipStream_t s);
 // rtm_obs_jac_kernel.hip (full = FULL instantiation, real_kind 8; out_kind: element size of the outputs - 8 with a.real_kind = 4 is the
 // host entry's double accumulation)
 void launch_rtm_obs_jac(const RtmObsJacArgs &a, bool full, int out_kind, hipStream_t s);
+// rtm_obs_kernel.hip (out_kind as for launch_rtm_obs_jac)
+void launch_rtm_obs(const RtmObsArgs &a, int out_kind, hipStream_t s);
 
 }  // namespace monortm_dev

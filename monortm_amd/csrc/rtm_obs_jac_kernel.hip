@@ -2,59 +2,10 @@
 // gfx950: K per MEASUREMENT (view, channel), y = sum_{j in view} wpath_j sum_{i: chan_i = c} wchan_i q_ji, contracted inside the kernel
 // that forms the monochromatic per-path terms - none of them reaches memory.  See DESIGN.md section 3.9.
 #include "cloud_tkc.hpp"
+#include "obs_exchange.hpp"   // OBS_SLAB, wave_fence, add_rounded, to_channels: shared with rtm_obs_kernel.hip
 
 namespace {
 using namespace monortm_dev;
-
-constexpr int OBS_SLAB = 4;   // rows of a wave's LDS slab: fields that change lanes for channels in one exchange
-
-// A wave is one layer group: what its lanes leave in the wave's own slab is read by other lanes of the SAME wave only.  The LDS serves a
-// wave's accesses in program order, so a fence of wavefront scope (which keeps the compiler from moving the accesses) is all it takes.
-__device__ __forceinline__ void wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// a + b with b kept as it was rounded: tau = (double)O * factor is rounded ONCE, and the running optical depth above a layer must add that
-// tau - left to the compiler, the product is contracted into the sum here (fma(O, factor, ODTu)) and not in rtm_scan_jac_kernel, and the
-// transmittances of the two kernels part by an ulp; in the lowest layers of an opaque channel, where dq/dtau is the residue of a
-// cancellation, that ulp is the whole term
-__device__ __forceinline__ double add_rounded(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-
-// Lanes -> channels.  Every lane leaves its NF values (sums over the tile's paths, one wavenumber each) in the wave's slab; the owner
-// lane of channel c (c mod 64) adds the members of c in this wavenumber block, in ascending wavenumber, times wchan, and adds the sum
-// to dst[f][c] - a plain read-modify-write by the one thread that owns the element for the whole launch.  ms: the block's row of the
-// membership table (ms[c] .. ms[c + 1]: the members of c), mb = ms[0]; sMl / sMw: lane and weight of the block's members (LDS).
-// Called by whole waves (all 64 lanes, wave-uniform control flow).
-template <typename A, int NF>
-__device__ __forceinline__ void to_channels(double *slab, const double (&v)[NF], int nchan, const int *ms, int mb, const int *sMl,
-                                            const double *sMw, A *const (&dst)[NF], int lane) {
-    static_assert(NF <= OBS_SLAB, "slab rows");
-#pragma unroll
-    for (int f = 0; f < NF; f++) slab[f * 64 + lane] = v[f];
-    wave_fence();
-    for (int c = lane; c < nchan; c += 64) {
-        const int m0 = ms[c] - mb, m1 = ms[c + 1] - mb;
-        if (m1 > m0) {
-            double s[NF];
-#pragma unroll
-            for (int f = 0; f < NF; f++) s[f] = 0.;
-            for (int m = m0; m < m1; m++) {
-                const int ml = sMl[m];
-                const double w = sMw[m];
-#pragma unroll
-                for (int f = 0; f < NF; f++) s[f] = fma(w, slab[f * 64 + ml], s[f]);
-            }
-#pragma unroll
-            for (int f = 0; f < NF; f++) dst[f][c] = (A)((double)dst[f][c] + s[f]);
-        }
-    }
-    wave_fence();
-}
 
 // One workgroup = one (profile, view): 64 wavenumbers x G layer groups (a wave each).  It walks the view's paths in tiles of NP and, per
 // tile, the wavenumber blocks of 64, serially; per (tile, block) the two passes of rtm_scan_jac_kernel, its operations in its order
