@@ -328,10 +328,13 @@ __device__ __forceinline__ void planck_d(double c3, double v, double fbeta, doub
     *B = b;
     *dB = b * ((e + 1.) * r) * (v * fbeta * fbeta * (1. / K_RADCN2));
 }
-// ---- the arithmetic rtm_kernel, rtm_scan_kernel and rtm_jac_kernel's forward pass share --------------------------------------------------------------------------
+// ---- the arithmetic every radiance kernel shares -------------------------------------------------------------------------------------
+// rtm_layer_terms: rtm_kernel (rtm_kernel.hip), rtm_jac_kernel's pass 1 (jacobian_kernel.hip) and tile_forward_sweep (rtm_tile.hpp), which
+// is the forward sweep of rtm_scan_kernel, rtm_obs_kernel, rtm_scan_jac_kernel and rtm_obs_jac_kernel.  bb_fn and rtm_combine: rtm_kernel,
+// rtm_scan_kernel, rtm_obs_kernel.
 // A scan path with factor 1 is monortm_hip_rtm's result bit for bit (tests/test_rtm_extremes.py).  Left to the compiler, which
 // products fuse into which sums depends on the surrounding code (scalars in one kernel, per-path arrays in the other) - RAD came out
-// one ulp apart.  So both kernels call these, every product-sum is spelled out as an fma or a separately rounded product, and
+// one ulp apart.  So the kernels call these, every product-sum is spelled out as an fma or a separately rounded product, and
 // contraction is off inside them.
 // Planck function with the library exp, as RTM's surface and cosmic terms (RTMmono.f90:223-237)
 __device__ __forceinline__ double bb_fn(double v, double fbeta) {

@@ -3,6 +3,7 @@
 //   rtm_jac_kernel:     the exact adjoint of RAD_UP_DN + RTM (reference src/RTMmono.f90:13-221), chained with the central
 //                       differences of the perturbed states' optical depths (FULL)
 #include "cloud_tkc.hpp"
+#include "rtm_tile.hpp"   // jac_path_weights, jac_layer_terms, jac_dn_lev_above: shared with rtm_scan_jac_kernel and rtm_obs_jac_kernel
 
 namespace {
 using namespace monortm_dev;
@@ -45,6 +46,8 @@ __global__ __launch_bounds__(256) void jac_perturb_kernel(JacPerturbArgs a) {
 //     dTRTOT/dtau_k = -TRTOT, combined through the irt forms of RAD (RTMmono.f90:138-147) and dTB/dRAD,
 //   and the Planck terms: dB(T_k) into K_T, dB(TZ_j) of both sweeps into K_TZ.  Level j is written by the group that owns layer
 //   j - 1 (level 0 by group 0); the downward term of the layer above a group's top is formed once more for it.
+// The arithmetic of both - RAD's irt forms with dq/dRAD and the weights, and the per-layer body - is rtm_tile.hpp's, one definition
+// for this kernel and the scan kernels' NP paths; this file keeps the exchange through LDS, the FULL chain and the stores.
 // FULL (monortm_hip_jacobian): the central differences of the perturbed states' O (states 1, 2: T +- h; 3 + 2i, 4 + 2i: ln WKL of
 // jac_mol[i] +- eps) times dq/dO_k into K_T and K_W, dq/dO_k ODCLW_TKC(wn, T_k, 1) into K_CLW.
 // R: element type of the REAL arrays; the arithmetic is double.
@@ -64,10 +67,7 @@ __global__ __launch_bounds__(64 * G) void rtm_jac_kernel(RtmJacArgs a) {
     const R *O = rp<R>(a.O) + pw + iw;
     const R *T = rp<R>(a.T) + (size_t)prof * nlm, *TZ = rp<R>(a.TZ) + (size_t)prof * (nlm + 1);
     double *sBl = sBeta, *sBz = sBeta + nlm;
-    for (int l = g * 64 + lane; l < 2 * nlay + 1; l += 64 * G) {
-        if (l < nlay) sBl[l] = K_RADCN2 / (double)T[l];
-        else sBz[l - nlay] = K_RADCN2 / (double)TZ[l - nlay];
-    }
+    tile_load_beta<G>(T, TZ, nlay, sBl, sBz);
     const int chunk = (nlay + G - 1) / G;
     const int l0 = min(nlay, g * chunk), l1 = min(nlay, l0 + chunk);  // 0-based layer range [l0, l1)
 
@@ -117,41 +117,20 @@ __global__ __launch_bounds__(64 * G) void rtm_jac_kernel(RtmJacArgs a) {
     const double ex_s = exp(VV * (K_RADCN2 / tmpsfc)), ex_c = exp(VV * (K_RADCN2 / TSKY));
     const double SURFRAD = c3 / (ex_s - 1.), COSMOS = c3 / (ex_c - 1.);
     const double ESFC = (double)rp<R>(a.emiss)[o], RSFC = (double)rp<R>(a.reflc)[o];
-    double RAD = 0., cU = 0., cD = 0., cT = 0.;   // dRAD/dRUP, dRAD/dRDN, dRAD/dTRTOT
-    if (irt == 1) {
-        RAD = fma(TRTOT, fma(RSFC, fma(TRTOT, COSMOS, RDN), ESFC * SURFRAD), RUP);   // (as rtm_combine rounds it, device_common.hpp)
-        cU = 1.; cD = TRTOT * RSFC; cT = ESFC * SURFRAD + RSFC * RDN + 2. * RSFC * TRTOT * COSMOS;
-    }
-    if (irt == 2) {
-        RAD = fma(TRTOT, fma(TRTOT, COSMOS, RDN), RUP);
-        cU = 1.; cD = TRTOT; cT = RDN + 2. * TRTOT * COSMOS;
-    }
-    if (irt == 3) {
-        RAD = fma(TRTOT, COSMOS, RDN);
-        cU = 0.; cD = 1.; cT = COSMOS;
-    }
-    const double X = c3 / RAD + 1., lx = log(X);
-    double dq = 1.;   // dq/dRAD
-    // dTB/dRAD = RADCN2 v (c3 / RAD) / (ln^2 X X RAD); RAD enters once per factor: RAD^2 underflows for RAD < 1.5e-154 (a cold opaque
-    // column in the ultraviolet), where the derivative is finite
-    if (a.quantity == 1) dq = (K_RADCN2 * VV) * ((c3 / RAD) / X) / ((lx * lx) * RAD);
-    if (g == 0 && valid) {
+    if (!valid) return;   // (no barrier below; leaving here and not behind the stores keeps <double, 8, false> at 96 VGPRs, 5 waves per SIMD)
+    // RAD through its irt forms, dq/dRAD, the weights of pass 2 and the surface terms (rtm_tile.hpp)
+    double RAD, lx, dq, gU, gD, gT;
+    jac_path_weights(irt, TRTOT, RUP, RDN, ESFC, RSFC, SURFRAD, COSMOS, c3, VV, a.quantity, RAD, lx, dq, gU, gD, gT);
+    if (g == 0) {
         wp<R>(a.RAD)[o] = (R)RAD;
         wp<R>(a.TB)[o] = (R)(K_RADCN2 * VV / lx);
         R *ks = wp<R>(a.K_SFC) + (size_t)prof * 3 * nwn + iw;
-        double kts = 0., kem = 0., krf = 0.;
-        if (irt == 1) {
-            const double xs = VV * (K_RADCN2 / tmpsfc);
-            const double dBs = SURFRAD * (ex_s / (ex_s - 1.)) * (xs / tmpsfc);
-            kts = dq * TRTOT * ESFC * dBs;
-            kem = dq * TRTOT * SURFRAD;
-            krf = dq * TRTOT * (RDN + TRTOT * COSMOS);
-        }
-        ks[0] = (R)kts;
-        ks[nwn] = (R)kem;
-        ks[2 * (size_t)nwn] = (R)krf;
+        double ksfc[3];
+        jac_path_sfc(irt, dq, TRTOT, RDN, ESFC, SURFRAD, COSMOS, VV, ex_s, tmpsfc, ksfc);
+        ks[0] = (R)ksfc[0];
+        ks[nwn] = (R)ksfc[1];
+        ks[2 * (size_t)nwn] = (R)ksfc[2];
     }
-    if (!valid) return;   // (no barrier below)
 
     // ---- pass 2: per-layer derivatives, layers l1-1 .. l0 (0-based), top-down
     R *KO = a.K_O ? wp<R>(a.K_O) + pw + iw : nullptr;
@@ -159,7 +138,6 @@ __global__ __launch_bounds__(64 * G) void rtm_jac_kernel(RtmJacArgs a) {
     R *KTZ = wp<R>(a.K_TZ) + (size_t)prof * (nlm + 1) * nwn + iw;
     R *KW = FULL ? wp<R>(a.K_W) + pw * a.njac + iw : nullptr;
     R *KC = FULL ? wp<R>(a.K_CLW) + pw + iw : nullptr;
-    const double gU = dq * cU, gD = dq * cD, gT = dq * cT * TRTOT;
     if (l1 > l0) {
         double ODTd = ODTOT - above, ODTu = above;
         double upIncl = upLow + RUPg;   // sum of up_l, l <= current layer
@@ -169,34 +147,15 @@ __global__ __launch_bounds__(64 * G) void rtm_jac_kernel(RtmJacArgs a) {
         double Bzu, dBzu;
         planck_d(c3, VV, sBz[l1], &Bzu, &dBzu);
         double dn_lev = 0.;
-        if (l1 < nlay) {
-            const double tau = (double)O[(size_t)l1 * nwn];
-            const double pade = 0.193 * tau + 0.013 * (tau * tau);
-            dn_lev = gD * exp_cw(-(ODTOT - above)) * (1. - exp_cw(-tau)) * pade * rcp2(1. + pade) * dBzu;
-        }
+        if (l1 < nlay) dn_lev = jac_dn_lev_above((double)O[(size_t)l1 * nwn], gD, ODTd, dBzu);
         for (int k = l1 - 1; k >= l0; k--) {
             const double tau = (double)O[(size_t)k * nwn];
             double B, dB, Bzl, dBzl;
             planck_d(c3, VV, sBl[k], &B, &dB);
             planck_d(c3, VV, sBz[k], &Bzl, &dBzl);
-            const double t = exp_cw(-tau);
-            const double pade = 0.193 * tau + 0.013 * (tau * tau), pp = 0.193 + 0.026 * tau;
-            const double rp1 = rcp2(1. + pade), emis = 1. - t;
-            ODTd = ODTd - tau;
-            const double TRd = exp_cw(-ODTd), TRu = up ? exp_cw(-ODTu) : 0.;
-            ODTu = ODTu + tau;
-            const double bdn = B + pade * Bzl, bup = B + pade * Bzu;
-            const double dn = ((TRd * emis) * bdn) * rp1, upk = up ? ((TRu * emis) * bup) * rp1 : 0.;
-            upIncl = upIncl - upk;   // now sum_{l<k} up_l
-            const double dfdn = t * bdn * rp1 + emis * pp * (Bzl - B) * (rp1 * rp1);
-            const double dfup = t * bup * rp1 + emis * pp * (Bzu - B) * (rp1 * rp1);
-            const double dRUP = TRu * dfup - upIncl, dRDN = TRd * dfdn - dnAbove;
-            dnAbove = dnAbove + dn;
-            const double ko = gU * dRUP + gD * dRDN - gT;
-            double kt = (gU * TRu + gD * TRd) * emis * rp1 * dB;
-            const double wz = emis * pade * rp1;
-            KTZ[(size_t)(k + 1) * nwn] = (R)(gU * TRu * wz * dBzu + dn_lev);
-            dn_lev = gD * TRd * wz * dBzl;
+            double ko, kt, ktz;
+            jac_layer_terms(tau, B, dB, Bzl, dBzl, Bzu, dBzu, up, gU, gD, gT, ODTd, ODTu, upIncl, dnAbove, dn_lev, ko, kt, ktz);   // (rtm_tile.hpp)
+            KTZ[(size_t)(k + 1) * nwn] = (R)ktz;
             Bzu = Bzl;
             dBzu = dBzl;
             if (KO) KO[(size_t)k * nwn] = (R)ko;

@@ -16,15 +16,6 @@ __device__ __forceinline__ void wave_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// a + b with b kept as it was rounded: tau = (double)O * factor is rounded ONCE, and the running optical depth above a layer must add that
-// tau - left to the compiler, the product is contracted into the sum here (fma(O, factor, ODTu)) and not in rtm_scan_jac_kernel, and the
-// transmittances of the two kernels part by an ulp; in the lowest layers of an opaque channel, where dq/dtau is the residue of a
-// cancellation, that ulp is the whole term
-__device__ __forceinline__ double add_rounded(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-
 // Lanes -> channels.  Every lane leaves its NF values (sums over the tile's paths, one wavenumber each) in the wave's slab; the owner
 // lane of channel c (c mod 64) adds the members of c in this wavenumber block, in ascending wavenumber, times wchan, and adds the sum
 // to dst[f][c] - a plain read-modify-write by the one thread that owns the element for the whole launch.  ms: the block's row of the

@@ -2,14 +2,16 @@
 // gfx950: K per MEASUREMENT (view, channel), y = sum_{j in view} wpath_j sum_{i: chan_i = c} wchan_i q_ji, contracted inside the kernel
 // that forms the monochromatic per-path terms - none of them reaches memory.  See DESIGN.md section 3.9.
 #include "cloud_tkc.hpp"
-#include "obs_exchange.hpp"   // OBS_SLAB, wave_fence, add_rounded, to_channels: shared with rtm_obs_kernel.hip
+#include "obs_exchange.hpp"   // OBS_SLAB, wave_fence, to_channels: shared with rtm_obs_kernel.hip
+#include "rtm_tile.hpp"       // the tile sweep and the adjoint's per-path and per-(layer, path) arithmetic: shared with the scan kernels
 
 namespace {
 using namespace monortm_dev;
 
 // One workgroup = one (profile, view): 64 wavenumbers x G layer groups (a wave each).  It walks the view's paths in tiles of NP and, per
-// tile, the wavenumber blocks of 64, serially; per (tile, block) the two passes of rtm_scan_jac_kernel, its operations in its order
-// (rtm_layer_terms, planck_d, odclw_tkc, exp_cw, rcp2, tau = (double)O * factor rounded ONCE, the difference quotients of Opert).
+// tile, the wavenumber blocks of 64, serially; per (tile, block) the two passes of rtm_scan_jac_kernel - the very functions of
+// rtm_tile.hpp it calls (the preloads, the optical depths per path, the forward sweep, jac_path_weights, jac_layer_terms) - and around
+// them its operations in its order (planck_d, odclw_tkc, tau = (double)O * factor rounded ONCE, the difference quotients of Opert).
 // Where that kernel stores a term of path j, this one adds wpath_j x term to a register sum over the tile's paths (j ascending), hands
 // the sum to the channel's owner lane (to_channels: wavenumbers ascending) and adds it to the output (tiles ascending, blocks ascending
 // within a tile).  Every output element has ONE owner thread for the whole launch - the group that walks layer k (level k + 1; level 0,
@@ -65,10 +67,7 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
             KS[2 * (size_t)nchan + c] = (A)0;
         }
     }
-    for (int l = g * 64 + lane; l < 2 * nlay + 1; l += 64 * G) {
-        if (l < nlay) sBl[l] = K_RADCN2 / (double)T[l];
-        else sBz[l - nlay] = K_RADCN2 / (double)TZ[l - nlay];
-    }
+    tile_load_beta<G>(T, TZ, nlay, sBl, sBz);
     const int js = a.view_start[view], je = a.view_start[view + 1];
     const int nblk = (nwn + 63) / 64;
     const bool up = irt != 3;
@@ -79,13 +78,7 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
     for (int j0 = js; j0 < je; j0 += NP) {   // tiles of the view's paths; every bound below is workgroup-uniform
         const int npl = min(NP, je - j0);
         __syncthreads();   // (every wave is done with the factors of the tile before)
-        const R *F = rp<R>(a.path) + ((size_t)prof * a.npath + j0) * lm;
-        for (int j = 0; j < npl; j++)
-            for (int l = g * 64 + lane; l < nlay; l += 64 * G) {
-                const double f = (double)F[(size_t)j * lm + l];
-                if (!(f >= 0. && f < __builtin_inf())) atomicOr(a.errflag, ERRBIT_ARG);
-                sF[j * lm + l] = f;
-            }
+        tile_load_factors<G>(rp<R>(a.path) + ((size_t)prof * a.npath + j0) * lm, npl, nlay, lm, sF, a.errflag);
         if (g == 0 && lane < NP) sW[lane] = lane < npl ? a.wpath[j0 + lane] : 0.;
 
         for (int b = 0; b < nblk; b++) {
@@ -103,60 +96,13 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
             const double VV = a.wn[iw];
             const R *O = rp<R>(a.O) + pw + iw;
 
-            double part[NP];
-#pragma unroll
-            for (int j = 0; j < NP; j++) part[j] = 0.;
-            for (int l = l0; l < l1; l++) {
-                const double o = (double)O[(size_t)l * nwn];
-#pragma unroll
-                for (int j = 0; j < NP; j++)
-                    if (j < npl) part[j] = part[j] + __dmul_rn(o, sF[j * lm + l]);
-            }
             double above[NP], ODTOT[NP];
-#pragma unroll
-            for (int j = 0; j < NP; j++) {
-                above[j] = 0.;
-                ODTOT[j] = 0.;
-                if (j < npl) {
-                    sUp[g][lane] = part[j];
-                    __syncthreads();
-                    double below = 0., tot = 0.;
-                    for (int gg = 0; gg < G; gg++) {
-                        if (gg < g) below = below + sUp[gg][lane];
-                        tot = tot + sUp[gg][lane];
-                    }
-                    ODTOT[j] = tot;
-                    above[j] = tot - below - part[j];
-                    __syncthreads();
-                }
-            }
+            tile_optical_depths(O, nwn, l0, l1, npl, lm, sF, sUp, above, ODTOT);
             const double c3 = K_RADCN1 * (VV * VV * VV);
 
-            // ---- pass 1: the forward sums of rtm_kernel (RTMmono.f90:193-217), layers l1 .. l0+1 (1-based)
-            double RUPg[NP], RDNg[NP];
-            {
-                double ODTd[NP], ODTu[NP];
-#pragma unroll
-                for (int j = 0; j < NP; j++) {
-                    RUPg[j] = 0.;
-                    RDNg[j] = 0.;
-                    ODTd[j] = ODTOT[j] - above[j];
-                    ODTu[j] = above[j];
-                }
-                double bb_top = (up && l1 > l0) ? planck(c3, VV, sBz[l1]) : 0.;
-                for (int l = l1; l >= l0 + 1; l--) {
-                    const double o = (double)O[(size_t)(l - 1) * nwn];
-                    const double bb = planck(c3, VV, sBl[l - 1]), bbz = planck(c3, VV, sBz[l - 1]);
-#pragma unroll
-                    for (int j = 0; j < NP; j++)
-                        if (j < npl) {
-                            double unused = 0.;  // (CALCTMR's sum: not needed here)
-                            const double ODVI = __dmul_rn(o, sF[j * lm + l - 1]);
-                            rtm_layer_terms(ODVI, bb, bbz, bb_top, up, ODTd[j], ODTu[j], RUPg[j], RDNg[j], unused);  // rtm_kernel's rounding (device_common.hpp)
-                        }
-                    bb_top = bbz;
-                }
-            }
+            // ---- pass 1: the group's forward sums (rtm_tile.hpp)
+            double RUPg[NP], RDNg[NP], no_tmr[1];
+            tile_forward_sweep<false>(O, nwn, l0, l1, npl, lm, sBl, sBz, sF, c3, VV, up, above, ODTOT, RUPg, RDNg, no_tmr);
             // the surface and the cosmic background: the same for every path of the tile
             const double ex_s = exp(VV * (K_RADCN2 / tmpsfc)), ex_c = exp(VV * (K_RADCN2 / TSKY));
             const double SURFRAD = c3 / (ex_s - 1.), COSMOS = c3 / (ex_c - 1.);
@@ -188,35 +134,16 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
                     const double TRTOT = exp(-ODTOT[j]);
                     const size_t os = a.sfc_per_path ? ((size_t)prof * a.npath + j0 + j) * nwn + iw : (size_t)prof * nwn + iw;
                     const double ESFC = (double)rp<R>(a.emiss)[os], RSFC = (double)rp<R>(a.reflc)[os];
-                    double RAD = 0., cU = 0., cD = 0., cT = 0.;   // dRAD/dRUP, dRAD/dRDN, dRAD/dTRTOT
-                    if (irt == 1) {
-                        RAD = fma(TRTOT, fma(RSFC, fma(TRTOT, COSMOS, RDN), ESFC * SURFRAD), RUP);   // (as rtm_combine rounds it, device_common.hpp)
-                        cU = 1.; cD = TRTOT * RSFC; cT = ESFC * SURFRAD + RSFC * RDN + 2. * RSFC * TRTOT * COSMOS;
-                    }
-                    if (irt == 2) {
-                        RAD = fma(TRTOT, fma(TRTOT, COSMOS, RDN), RUP);
-                        cU = 1.; cD = TRTOT; cT = RDN + 2. * TRTOT * COSMOS;
-                    }
-                    if (irt == 3) {
-                        RAD = fma(TRTOT, COSMOS, RDN);
-                        cU = 0.; cD = 1.; cT = COSMOS;
-                    }
-                    const double X = c3 / RAD + 1., lx = log(X);
-                    double dq = 1.;   // dq/dRAD
-                    // dTB/dRAD with RAD entering once per factor, as rtm_jac_kernel forms it (RAD^2 underflows for a cold opaque column)
-                    if (a.quantity == 1) dq = (K_RADCN2 * VV) * ((c3 / RAD) / X) / ((lx * lx) * RAD);
+                    double RAD, lx, dq;
+                    jac_path_weights(irt, TRTOT, RUP, RDN, ESFC, RSFC, SURFRAD, COSMOS, c3, VV, a.quantity, RAD, lx, dq, gU[j], gD[j], gT[j]);
                     const double wj = sW[j];
                     sq[0] = fma(wj, a.quantity == 1 ? K_RADCN2 * VV / lx : RAD, sq[0]);
-                    if (irt == 1) {
-                        const double xs = VV * (K_RADCN2 / tmpsfc);
-                        const double dBs = SURFRAD * (ex_s / (ex_s - 1.)) * (xs / tmpsfc);
-                        sq[1] = fma(wj, dq * TRTOT * ESFC * dBs, sq[1]);
-                        sq[2] = fma(wj, dq * TRTOT * SURFRAD, sq[2]);
-                        sq[3] = fma(wj, dq * TRTOT * (RDN + TRTOT * COSMOS), sq[3]);
+                    if (irt == 1) {   // (0 otherwise)
+                        double ksfc[3];
+                        jac_path_sfc(irt, dq, TRTOT, RDN, ESFC, SURFRAD, COSMOS, VV, ex_s, tmpsfc, ksfc);
+#pragma unroll
+                        for (int i = 0; i < 3; i++) sq[1 + i] = fma(wj, ksfc[i], sq[1 + i]);
                     }
-                    gU[j] = dq * cU;
-                    gD[j] = dq * cD;
-                    gT[j] = dq * cT * TRTOT;
                     upIncl0[j] = upLow + RUPg[j];   // sum of up_l, l <= the group's top layer
                     dnHigh0[j] = dnHigh;            // sum of dn_l, l > the group's top layer
                 }
@@ -245,11 +172,7 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
                     const double o1 = (double)O[(size_t)l1 * nwn];
 #pragma unroll
                     for (int j = 0; j < NP; j++)
-                        if (j < npl) {
-                            const double tau = __dmul_rn(o1, sF[j * lm + l1]);
-                            const double pade = 0.193 * tau + 0.013 * (tau * tau);
-                            dn_lev[j] = gD[j] * exp_cw(-(ODTOT[j] - above[j])) * (1. - exp_cw(-tau)) * pade * rcp2(1. + pade) * dBzu;
-                        }
+                        if (j < npl) dn_lev[j] = jac_dn_lev_above(__dmul_rn(o1, sF[j * lm + l1]), gD[j], ODTd[j], dBzu);
                 }
                 for (int k = l1 - 1; k >= l0; k--) {
                     const double o = (double)O[(size_t)k * nwn];
@@ -270,26 +193,11 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
                         kof[j] = 0.;
                         if (j < npl) {
                             const double f = sF[j * lm + k];
-                            const double tau = __dmul_rn(o, f);
-                            const double t = exp_cw(-tau);
-                            const double pade = 0.193 * tau + 0.013 * (tau * tau), pp = 0.193 + 0.026 * tau;
-                            const double rp1 = rcp2(1. + pade), emis = 1. - t;
-                            ODTd[j] = ODTd[j] - tau;
-                            const double TRd = exp_cw(-ODTd[j]), TRu = up ? exp_cw(-ODTu[j]) : 0.;
-                            ODTu[j] = add_rounded(ODTu[j], tau);
-                            const double bdn = B + pade * Bzl, bup = B + pade * Bzu;
-                            const double dn = ((TRd * emis) * bdn) * rp1, upk = up ? ((TRu * emis) * bup) * rp1 : 0.;
-                            upIncl[j] = upIncl[j] - upk;   // now sum_{l<k} up_l
-                            const double dfdn = t * bdn * rp1 + emis * pp * (Bzl - B) * (rp1 * rp1);
-                            const double dfup = t * bup * rp1 + emis * pp * (Bzu - B) * (rp1 * rp1);
-                            const double dRUP = TRu * dfup - upIncl[j], dRDN = TRd * dfdn - dnAbove[j];
-                            dnAbove[j] = dnAbove[j] + dn;
-                            const double ko = gU[j] * dRUP + gD[j] * dRDN - gT[j];
-                            double kt = (gU[j] * TRu + gD[j] * TRd) * emis * rp1 * dB;
-                            const double wz = emis * pade * rp1;
+                            double ko, kt, ktz;
+                            jac_layer_terms(__dmul_rn(o, f), B, dB, Bzl, dBzl, Bzu, dBzu, up, gU[j], gD[j], gT[j], ODTd[j], ODTu[j], upIncl[j],
+                                            dnAbove[j], dn_lev[j], ko, kt, ktz);   // (rtm_tile.hpp)
                             const double wj = sW[j];
-                            sk[1] = fma(wj, gU[j] * TRu * wz * dBzu + dn_lev[j], sk[1]);
-                            dn_lev[j] = gD[j] * TRd * wz * dBzl;
+                            sk[1] = fma(wj, ktz, sk[1]);
                             kof[j] = __dmul_rn(f, ko);
                             if constexpr (FULL) {
                                 kt += kof[j] * dOdT;

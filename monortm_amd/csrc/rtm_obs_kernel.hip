@@ -3,6 +3,7 @@
 // monochromatic radiances along the paths - none of them reaches memory.  The forward half of rtm_obs_jac_kernel.hip: its layout, its
 // owner threads, its order of additions, without the adjoint.  See DESIGN.md section 3.10.
 #include "obs_exchange.hpp"
+#include "rtm_tile.hpp"
 
 namespace {
 using namespace monortm_dev;
@@ -16,8 +17,8 @@ __device__ __forceinline__ double band_tb(double vc, double rad) {
 
 // One workgroup = one (profile, view): 64 wavenumbers x G layer groups (a wave each).  It walks the view's paths in tiles of NP and, per
 // tile, the wavenumber blocks of 64, serially (blocks no channel has a member in are skipped); per (tile, block) the forward sums of
-// rtm_scan_kernel, its operations in its order (tau = (double)O * factor rounded ONCE, planck of the layer and its lower level once per
-// layer for the tile, rtm_layer_terms, the group sums through LDS one path at a time in the reference's visiting order, rtm_combine).
+// rtm_scan_kernel - the very functions of rtm_tile.hpp it calls (the preloads, the optical depths per path, the forward sweep) - then
+// the group sums through LDS one path at a time in the reference's visiting order and rtm_combine.
 // Where that kernel stores q of path j, group 0 adds wpath_j x q to a register sum over the tile's paths (j ascending), hands the sum to
 // the channel's owner lane (to_channels: wavenumbers ascending) and the owner adds it to Y (tiles ascending, blocks ascending within a
 // tile).  Every element of Y has ONE owner thread for the whole launch - group 0, lane = channel mod 64 - which zero-fills it first: no
@@ -44,10 +45,7 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_kernel(RtmObsArgs a) {
     A *Y = wp<A>(a.Y) + ((size_t)prof * a.nview + view) * nchan;
     if (g == 0)
         for (int c = lane; c < nchan; c += 64) Y[c] = (A)0;
-    for (int l = g * 64 + lane; l < 2 * nlay + 1; l += 64 * G) {
-        if (l < nlay) sBl[l] = K_RADCN2 / (double)T[l];
-        else sBz[l - nlay] = K_RADCN2 / (double)TZ[l - nlay];
-    }
+    tile_load_beta<G>(T, TZ, nlay, sBl, sBz);
     const int js = a.view_start[view], je = a.view_start[view + 1];
     const int nblk = (nwn + 63) / 64;
     const bool up = irt != 3;
@@ -58,13 +56,7 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_kernel(RtmObsArgs a) {
     for (int j0 = js; j0 < je; j0 += NP) {   // tiles of the view's paths; every bound below is workgroup-uniform
         const int npl = min(NP, je - j0);
         __syncthreads();   // (every wave is done with the factors of the tile before)
-        const R *F = rp<R>(a.path) + ((size_t)prof * a.npath + j0) * lm;
-        for (int j = 0; j < npl; j++)
-            for (int l = g * 64 + lane; l < nlay; l += 64 * G) {
-                const double f = (double)F[(size_t)j * lm + l];
-                if (!(f >= 0. && f < __builtin_inf())) atomicOr(a.errflag, ERRBIT_ARG);
-                sF[j * lm + l] = f;
-            }
+        tile_load_factors<G>(rp<R>(a.path) + ((size_t)prof * a.npath + j0) * lm, npl, nlay, lm, sF, a.errflag);
         if (g == 0 && lane < NP) sW[lane] = lane < npl ? a.wpath[j0 + lane] : 0.;
 
         for (int b = 0; b < nblk; b++) {
@@ -82,60 +74,11 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_kernel(RtmObsArgs a) {
             const double VV = a.wn[iw];
             const R *O = rp<R>(a.O) + pw + iw;
 
-            double part[NP];
-#pragma unroll
-            for (int j = 0; j < NP; j++) part[j] = 0.;
-            for (int l = l0; l < l1; l++) {
-                const double o = (double)O[(size_t)l * nwn];
-#pragma unroll
-                for (int j = 0; j < NP; j++)
-                    if (j < npl) part[j] = part[j] + __dmul_rn(o, sF[j * lm + l]);
-            }
             double above[NP], ODTOT[NP];
-#pragma unroll
-            for (int j = 0; j < NP; j++) {
-                above[j] = 0.;
-                ODTOT[j] = 0.;
-                if (j < npl) {
-                    sUp[g][lane] = part[j];
-                    __syncthreads();
-                    double below = 0., tot = 0.;
-                    for (int gg = 0; gg < G; gg++) {
-                        if (gg < g) below = below + sUp[gg][lane];
-                        tot = tot + sUp[gg][lane];
-                    }
-                    ODTOT[j] = tot;
-                    above[j] = tot - below - part[j];
-                    __syncthreads();
-                }
-            }
+            tile_optical_depths(O, nwn, l0, l1, npl, lm, sF, sUp, above, ODTOT);
             const double c3 = K_RADCN1 * (VV * VV * VV);
-
-            // the forward sums of rtm_kernel (RTMmono.f90:193-217), layers l1 .. l0+1 (1-based)
-            double RUP[NP], RDN[NP];
-            {
-                double ODTd[NP], ODTu[NP];
-#pragma unroll
-                for (int j = 0; j < NP; j++) {
-                    RUP[j] = 0.;
-                    RDN[j] = 0.;
-                    ODTd[j] = ODTOT[j] - above[j];
-                    ODTu[j] = above[j];
-                }
-                double bb_top = (up && l1 > l0) ? planck(c3, VV, sBz[l1]) : 0.;
-                for (int l = l1; l >= l0 + 1; l--) {
-                    const double o = (double)O[(size_t)(l - 1) * nwn];
-                    const double bb = planck(c3, VV, sBl[l - 1]), bbz = planck(c3, VV, sBz[l - 1]);
-#pragma unroll
-                    for (int j = 0; j < NP; j++)
-                        if (j < npl) {
-                            double unused = 0.;  // (CALCTMR's sum: not needed here)
-                            const double ODVI = __dmul_rn(o, sF[j * lm + l - 1]);
-                            rtm_layer_terms(ODVI, bb, bbz, bb_top, up, ODTd[j], ODTu[j], RUP[j], RDN[j], unused);  // rtm_kernel's rounding (device_common.hpp)
-                        }
-                    bb_top = bbz;
-                }
-            }
+            double RUP[NP], RDN[NP], no_tmr[1];
+            tile_forward_sweep<false>(O, nwn, l0, l1, npl, lm, sBl, sBz, sF, c3, VV, up, above, ODTOT, RUP, RDN, no_tmr);
             // the group sums in the reference's visiting order, one path at a time: only group 0 goes on with them
 #pragma unroll
             for (int j = 0; j < NP; j++)

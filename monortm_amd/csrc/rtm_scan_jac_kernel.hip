@@ -2,6 +2,7 @@
 // monortm_hip_scan_jacobian) for gfx950: the exact adjoint of RAD_UP_DN + RTM (reference src/RTMmono.f90:13-221) per path, from ONE
 // set of optical depths and ONE set of perturbed MODM states.  See DESIGN.md section 3.8.
 #include "cloud_tkc.hpp"
+#include "rtm_tile.hpp"
 
 namespace {
 using namespace monortm_dev;
@@ -10,7 +11,9 @@ using namespace monortm_dev;
 // paths of which the last may hold fewer - npl, a workgroup-uniform count, so the barriers below stay in uniform control flow; hc / kT
 // of the layers and levels and the tile's factors in LDS; tau = (double)O * factor rounded ONCE) with the two passes of rtm_jac_kernel
 // per path, its operations in its order: on optical depths a caller scaled beforehand the two kernels differ by instruction
-// contraction only.
+// contraction only.  The preloads, the optical depths per path and the forward sweep are rtm_tile.hpp's, shared with rtm_scan_kernel
+// and the obs kernels; a path's pass-1 epilogue (jac_path_weights) and the per-(layer, path) body of pass 2 (jac_layer_terms,
+// jac_dn_lev_above) are rtm_tile.hpp's as well, shared with rtm_jac_kernel and rtm_obs_jac_kernel.
 //   pass 1: the group sums of the optical depth, the upward and the downward terms (rtm_layer_terms), exchanged through LDS one path
 //           at a time; RAD, TB, K_SFC and the weights gU = dq/dRUP, gD = dq/dRDN, gT = TRTOT dq/dTRTOT of every path;
 //   pass 2: every group walks its layers again, top-down.  Per layer, ONCE for the tile: (double)O, B and dB/dT of the layer and of its
@@ -37,75 +40,20 @@ __global__ __launch_bounds__(64 * G) void rtm_scan_jac_kernel(RtmScanJacArgs a) 
     const R *T = rp<R>(a.T) + (size_t)prof * lm, *TZ = rp<R>(a.TZ) + (size_t)prof * (lm + 1);
     const R *F = rp<R>(a.path) + ((size_t)prof * a.npath + j0) * lm;
     double *sBl = sBeta, *sBz = sBeta + lm, *sF = sBeta + 2 * lm + 1;
-    for (int l = g * 64 + lane; l < 2 * nlay + 1; l += 64 * G) {
-        if (l < nlay) sBl[l] = K_RADCN2 / (double)T[l];
-        else sBz[l - nlay] = K_RADCN2 / (double)TZ[l - nlay];
-    }
-    for (int j = 0; j < npl; j++)
-        for (int l = g * 64 + lane; l < nlay; l += 64 * G) {
-            const double f = (double)F[(size_t)j * lm + l];
-            if (!(f >= 0. && f < __builtin_inf())) atomicOr(a.errflag, ERRBIT_ARG);
-            sF[j * lm + l] = f;
-        }
+    tile_load_beta<G>(T, TZ, nlay, sBl, sBz);
+    tile_load_factors<G>(F, npl, nlay, lm, sF, a.errflag);
     __syncthreads();
     const int chunk = (nlay + G - 1) / G;
     const int l0 = min(nlay, g * chunk), l1 = min(nlay, l0 + chunk);  // 0-based layer range [l0, l1)
 
-    double part[NP];
-#pragma unroll
-    for (int j = 0; j < NP; j++) part[j] = 0.;
-    for (int l = l0; l < l1; l++) {
-        const double o = (double)O[(size_t)l * nwn];
-#pragma unroll
-        for (int j = 0; j < NP; j++)
-            if (j < npl) part[j] = part[j] + __dmul_rn(o, sF[j * lm + l]);
-    }
     double above[NP], ODTOT[NP];
-#pragma unroll
-    for (int j = 0; j < NP; j++) {
-        above[j] = 0.;
-        ODTOT[j] = 0.;
-        if (j < npl) {
-            sUp[g][lane] = part[j];
-            __syncthreads();
-            double below = 0., tot = 0.;
-            for (int gg = 0; gg < G; gg++) {
-                if (gg < g) below = below + sUp[gg][lane];
-                tot = tot + sUp[gg][lane];
-            }
-            ODTOT[j] = tot;
-            above[j] = tot - below - part[j];
-            __syncthreads();
-        }
-    }
+    tile_optical_depths(O, nwn, l0, l1, npl, lm, sF, sUp, above, ODTOT);
     const double c3 = K_RADCN1 * (VV * VV * VV);
     const bool up = irt != 3;
 
-    // ---- pass 1: the forward sums of rtm_kernel (RTMmono.f90:193-217), layers l1 .. l0+1 (1-based)
-    double RUPg[NP], RDNg[NP];
-    {
-        double ODTd[NP], ODTu[NP];
-#pragma unroll
-        for (int j = 0; j < NP; j++) {
-            RUPg[j] = 0.;
-            RDNg[j] = 0.;
-            ODTd[j] = ODTOT[j] - above[j];
-            ODTu[j] = above[j];
-        }
-        double bb_top = (up && l1 > l0) ? planck(c3, VV, sBz[l1]) : 0.;
-        for (int l = l1; l >= l0 + 1; l--) {
-            const double o = (double)O[(size_t)(l - 1) * nwn];
-            const double bb = planck(c3, VV, sBl[l - 1]), bbz = planck(c3, VV, sBz[l - 1]);
-#pragma unroll
-            for (int j = 0; j < NP; j++)
-                if (j < npl) {
-                    double unused = 0.;  // (CALCTMR's sum: not needed here)
-                    const double ODVI = __dmul_rn(o, sF[j * lm + l - 1]);
-                    rtm_layer_terms(ODVI, bb, bbz, bb_top, up, ODTd[j], ODTu[j], RUPg[j], RDNg[j], unused);  // rtm_kernel's rounding (device_common.hpp)
-                }
-            bb_top = bbz;
-        }
-    }
+    // ---- pass 1: the group's forward sums (rtm_tile.hpp)
+    double RUPg[NP], RDNg[NP], no_tmr[1];
+    tile_forward_sweep<false>(O, nwn, l0, l1, npl, lm, sBl, sBz, sF, c3, VV, up, above, ODTOT, RUPg, RDNg, no_tmr);
     // the surface and the cosmic background: the same for every path of the tile
     const double TSKY = 2.75;
     const double tsfc_in = (double)rp<R>(a.tmpsfc)[prof];
@@ -141,42 +89,18 @@ __global__ __launch_bounds__(64 * G) void rtm_scan_jac_kernel(RtmScanJacArgs a) 
             const size_t o = pj * nwn + iw;
             const size_t os = a.sfc_per_path ? o : (size_t)prof * nwn + iw;
             const double ESFC = (double)rp<R>(a.emiss)[os], RSFC = (double)rp<R>(a.reflc)[os];
-            double RAD = 0., cU = 0., cD = 0., cT = 0.;   // dRAD/dRUP, dRAD/dRDN, dRAD/dTRTOT
-            if (irt == 1) {
-                RAD = fma(TRTOT, fma(RSFC, fma(TRTOT, COSMOS, RDN), ESFC * SURFRAD), RUP);   // (as rtm_combine rounds it, device_common.hpp)
-                cU = 1.; cD = TRTOT * RSFC; cT = ESFC * SURFRAD + RSFC * RDN + 2. * RSFC * TRTOT * COSMOS;
-            }
-            if (irt == 2) {
-                RAD = fma(TRTOT, fma(TRTOT, COSMOS, RDN), RUP);
-                cU = 1.; cD = TRTOT; cT = RDN + 2. * TRTOT * COSMOS;
-            }
-            if (irt == 3) {
-                RAD = fma(TRTOT, COSMOS, RDN);
-                cU = 0.; cD = 1.; cT = COSMOS;
-            }
-            const double X = c3 / RAD + 1., lx = log(X);
-            double dq = 1.;   // dq/dRAD
-            // dTB/dRAD with RAD entering once per factor, as rtm_jac_kernel forms it (RAD^2 underflows for a cold opaque column)
-            if (a.quantity == 1) dq = (K_RADCN2 * VV) * ((c3 / RAD) / X) / ((lx * lx) * RAD);
+            double RAD, lx, dq;
+            jac_path_weights(irt, TRTOT, RUP, RDN, ESFC, RSFC, SURFRAD, COSMOS, c3, VV, a.quantity, RAD, lx, dq, gU[j], gD[j], gT[j]);
             if (g == 0 && valid) {
                 wp<R>(a.RAD)[o] = (R)RAD;
                 wp<R>(a.TB)[o] = (R)(K_RADCN2 * VV / lx);
                 R *ks = wp<R>(a.K_SFC) + pj * 3 * nwn + iw;
-                double kts = 0., kem = 0., krf = 0.;
-                if (irt == 1) {
-                    const double xs = VV * (K_RADCN2 / tmpsfc);
-                    const double dBs = SURFRAD * (ex_s / (ex_s - 1.)) * (xs / tmpsfc);
-                    kts = dq * TRTOT * ESFC * dBs;
-                    kem = dq * TRTOT * SURFRAD;
-                    krf = dq * TRTOT * (RDN + TRTOT * COSMOS);
-                }
-                ks[0] = (R)kts;
-                ks[nwn] = (R)kem;
-                ks[2 * (size_t)nwn] = (R)krf;
+                double ksfc[3];
+                jac_path_sfc(irt, dq, TRTOT, RDN, ESFC, SURFRAD, COSMOS, VV, ex_s, tmpsfc, ksfc);
+                ks[0] = (R)ksfc[0];
+                ks[nwn] = (R)ksfc[1];
+                ks[2 * (size_t)nwn] = (R)ksfc[2];
             }
-            gU[j] = dq * cU;
-            gD[j] = dq * cD;
-            gT[j] = dq * cT * TRTOT;
             upIncl0[j] = upLow + RUPg[j];   // sum of up_l, l <= the group's top layer
             dnHigh0[j] = dnHigh;            // sum of dn_l, l > the group's top layer
         }
@@ -210,11 +134,7 @@ __global__ __launch_bounds__(64 * G) void rtm_scan_jac_kernel(RtmScanJacArgs a) 
             const double o1 = (double)O[(size_t)l1 * nwn];
 #pragma unroll
             for (int j = 0; j < NP; j++)
-                if (j < npl) {
-                    const double tau = __dmul_rn(o1, sF[j * lm + l1]);
-                    const double pade = 0.193 * tau + 0.013 * (tau * tau);
-                    dn_lev[j] = gD[j] * exp_cw(-(ODTOT[j] - above[j])) * (1. - exp_cw(-tau)) * pade * rcp2(1. + pade) * dBzu;
-                }
+                if (j < npl) dn_lev[j] = jac_dn_lev_above(__dmul_rn(o1, sF[j * lm + l1]), gD[j], ODTd[j], dBzu);
         }
         for (int k = l1 - 1; k >= l0; k--) {
             const double o = (double)O[(size_t)k * nwn];
@@ -234,26 +154,11 @@ __global__ __launch_bounds__(64 * G) void rtm_scan_jac_kernel(RtmScanJacArgs a) 
                 kof[j] = 0.;
                 if (j < npl) {
                     const double f = sF[j * lm + k];
-                    const double tau = __dmul_rn(o, f);
-                    const double t = exp_cw(-tau);
-                    const double pade = 0.193 * tau + 0.013 * (tau * tau), pp = 0.193 + 0.026 * tau;
-                    const double rp1 = rcp2(1. + pade), emis = 1. - t;
-                    ODTd[j] = ODTd[j] - tau;
-                    const double TRd = exp_cw(-ODTd[j]), TRu = up ? exp_cw(-ODTu[j]) : 0.;
-                    ODTu[j] = ODTu[j] + tau;
-                    const double bdn = B + pade * Bzl, bup = B + pade * Bzu;
-                    const double dn = ((TRd * emis) * bdn) * rp1, upk = up ? ((TRu * emis) * bup) * rp1 : 0.;
-                    upIncl[j] = upIncl[j] - upk;   // now sum_{l<k} up_l
-                    const double dfdn = t * bdn * rp1 + emis * pp * (Bzl - B) * (rp1 * rp1);
-                    const double dfup = t * bup * rp1 + emis * pp * (Bzu - B) * (rp1 * rp1);
-                    const double dRUP = TRu * dfup - upIncl[j], dRDN = TRd * dfdn - dnAbove[j];
-                    dnAbove[j] = dnAbove[j] + dn;
-                    const double ko = gU[j] * dRUP + gD[j] * dRDN - gT[j];
-                    double kt = (gU[j] * TRu + gD[j] * TRd) * emis * rp1 * dB;
-                    const double wz = emis * pade * rp1;
+                    double ko, kt, ktz;
+                    jac_layer_terms(__dmul_rn(o, f), B, dB, Bzl, dBzl, Bzu, dBzu, up, gU[j], gD[j], gT[j], ODTd[j], ODTu[j], upIncl[j],
+                                    dnAbove[j], dn_lev[j], ko, kt, ktz);   // (rtm_tile.hpp)
                     const size_t jk = (size_t)j * lw + (size_t)k * nwn;
-                    KTZ[(size_t)j * zw + (size_t)(k + 1) * nwn] = (R)(gU[j] * TRu * wz * dBzu + dn_lev[j]);
-                    dn_lev[j] = gD[j] * TRd * wz * dBzl;
+                    KTZ[(size_t)j * zw + (size_t)(k + 1) * nwn] = (R)ktz;
                     kof[j] = __dmul_rn(f, ko);
                     if (KO) KO[jk] = (R)kof[j];
                     if (KP) KP[jk] = (R)__dmul_rn(o, ko);

@@ -1,6 +1,6 @@
 // rtm_scan_kernel.hip - CALCTMR + RAD_UP_DN + RTM (reference src/RTMmono.f90) along several paths through one atmosphere, from ONE
 // set of optical depths, for gfx950.  See DESIGN.md section 3.7.
-#include "device_common.hpp"
+#include "rtm_tile.hpp"
 
 namespace {
 using namespace monortm_dev;
@@ -13,6 +13,8 @@ using namespace monortm_dev;
 //   caller's pre-scaled O holds in double, then exactly the terms of rtm_kernel.
 // hc / kT of the layers and levels and the tile's factors are formed once per workgroup (LDS); factors of layers >= nlay[p] are
 // never read.  The LDS pieces of the group sums hold one path at a time: 24 KB at G = 16 whatever NP is.
+// The preloads, the optical depths per path and the forward sweep are rtm_tile.hpp's (shared with rtm_obs_kernel and the two adjoint
+// kernels); this file keeps the group-0 sums with CALCTMR's, the rtm_combine epilogue and the stores.
 template <typename R, int G, int NP>
 __global__ __launch_bounds__(64 * G) void rtm_scan_kernel(RtmScanArgs a) {
     __shared__ double sUp[G][64], sDn[G][64], sEx[G][64];
@@ -29,73 +31,19 @@ __global__ __launch_bounds__(64 * G) void rtm_scan_kernel(RtmScanArgs a) {
     const R *T = rp<R>(a.T) + (size_t)prof * lm, *TZ = rp<R>(a.TZ) + (size_t)prof * (lm + 1);
     const R *F = rp<R>(a.path) + ((size_t)prof * a.npath + j0) * lm;
     double *sBl = sBeta, *sBz = sBeta + lm, *sF = sBeta + 2 * lm + 1;
-    for (int l = g * 64 + lane; l < 2 * nlay + 1; l += 64 * G) {
-        if (l < nlay) sBl[l] = K_RADCN2 / (double)T[l];
-        else sBz[l - nlay] = K_RADCN2 / (double)TZ[l - nlay];
-    }
-    for (int j = 0; j < npl; j++)
-        for (int l = g * 64 + lane; l < nlay; l += 64 * G) {
-            const double f = (double)F[(size_t)j * lm + l];
-            if (!(f >= 0. && f < __builtin_inf())) atomicOr(a.errflag, ERRBIT_ARG);
-            sF[j * lm + l] = f;
-        }
+    tile_load_beta<G>(T, TZ, nlay, sBl, sBz);
+    tile_load_factors<G>(F, npl, nlay, lm, sF, a.errflag);
     __syncthreads();
     const int chunk = (nlay + G - 1) / G;
     const int l0 = min(nlay, g * chunk), l1 = min(nlay, l0 + chunk);  // 0-based layer range [l0, l1)
 
-    double part[NP];
-#pragma unroll
-    for (int j = 0; j < NP; j++) part[j] = 0.;
-    for (int l = l0; l < l1; l++) {
-        const double o = (double)O[(size_t)l * nwn];
-#pragma unroll
-        for (int j = 0; j < NP; j++)
-            if (j < npl) part[j] = part[j] + __dmul_rn(o, sF[j * lm + l]);
-    }
     double above[NP], ODTOT[NP];
-#pragma unroll
-    for (int j = 0; j < NP; j++) {
-        above[j] = 0.;
-        ODTOT[j] = 0.;
-        if (j < npl) {
-            sUp[g][lane] = part[j];
-            __syncthreads();
-            double below = 0., tot = 0.;
-            for (int gg = 0; gg < G; gg++) {
-                if (gg < g) below = below + sUp[gg][lane];
-                tot = tot + sUp[gg][lane];
-            }
-            ODTOT[j] = tot;
-            above[j] = tot - below - part[j];
-            __syncthreads();
-        }
-    }
+    tile_optical_depths(O, nwn, l0, l1, npl, lm, sF, sUp, above, ODTOT);
     const double c3 = K_RADCN1 * (VV * VV * VV);
     const bool up = irt != 3;
-
-    double RUP[NP], RDN[NP], sumexp[NP], ODTd[NP], ODTu[NP];
-#pragma unroll
-    for (int j = 0; j < NP; j++) {
-        RUP[j] = 0.;
-        RDN[j] = 0.;
-        sumexp[j] = 0.;
-        ODTd[j] = ODTOT[j] - above[j];  // downward sweep: optical depth from the surface up to and including the layer, running difference
-        ODTu[j] = above[j];             // upward sweep: optical depth above the layer
-    }
-    {  // RTMmono.f90:193-217 and CALCTMR :302-315, layers l1 .. l0+1 (1-based)
-        double bb_top = (up && l1 > l0) ? planck(c3, VV, sBz[l1]) : 0.;  // B at the upper level of the group's top layer
-        for (int l = l1; l >= l0 + 1; l--) {
-            const double o = (double)O[(size_t)(l - 1) * nwn];
-            const double bb = planck(c3, VV, sBl[l - 1]), bbz = planck(c3, VV, sBz[l - 1]);
-#pragma unroll
-            for (int j = 0; j < NP; j++)
-                if (j < npl) {
-                    const double ODVI = __dmul_rn(o, sF[j * lm + l - 1]);
-                    rtm_layer_terms(ODVI, bb, bbz, bb_top, up, ODTd[j], ODTu[j], RUP[j], RDN[j], sumexp[j]);  // (device_common.hpp)
-                }
-            bb_top = bbz;
-        }
-    }
+    double RUP[NP], RDN[NP], sumexp[NP];
+    tile_forward_sweep<true>(O, nwn, l0, l1, npl, lm, sBl, sBz, sF, c3, VV, up, above, ODTOT, RUP, RDN, sumexp);
+    // the group sums in the reference's visiting order, one path at a time: only group 0 goes on with them
 #pragma unroll
     for (int j = 0; j < NP; j++)
         if (j < npl) {
