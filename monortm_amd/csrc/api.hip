@@ -14,6 +14,7 @@
 
 #include "device_common.hpp"
 #include "line_table.hpp"
+#include "modm_plan.hpp"
 #include "lineshape.hpp"
 #include "tables/monortm_tables.h"
 
@@ -35,15 +36,8 @@ struct Ctx {
     std::vector<Ctx *> shards;
     // measurement switches (monortm_hip_set_option; the environment variables MONORTM_NSLICE / _FAIR /
     // _TILE_WAVES / _FINISH_GENERIC give their defaults ONCE, when the context is created - nothing on the launch path calls getenv)
-    struct Opt {
-        int nslice = 0;           // 0 = chosen per call
-        int fair = -1;            // -1 = chosen per call, 0 / 1 wave priorities off / on
-        int tile_waves = 0;       // 0 = lines_config(); 1 / 2 / 4 waves per workgroup of two-wavenumber tiles
-        int far_levels = -1;      // -1 = chosen per call; 0 = lines_kernel forms the far field of dense grids itself; 1 .. 6 levels of far_kernel
-        int lines_ms = -1;        // -1 = chosen per call; 0 = never lines_ms_kernel; 1 = whenever its layout fits (tests, measurements)
+    struct Opt : ModmPlanOpt {   // (modm_plan.hpp: the switches that decide what a MODM evaluation launches)
         int ms_ablate = 0;        // timing experiments: lines_ms_kernel without its later stages (wrong results)
-        int ms_items = 0;         // 0 = chosen per call; 64 / 128 / 192 (state, line) items per chunk of lines_ms_kernel
-        int finish_generic = 0;   // 1 = finish_kernel also where finish_mw_kernel would serve (A/B measurements, tests of the two against each other)
         double jac_dt = MONORTM_JAC_DT, jac_dlnw = MONORTM_JAC_DLNW;   // half-steps of the Jacobian's central differences
     } opt;
     void *comm = nullptr;     // RCCL communicator of a multi-process job (monortm_hip_comm_init), one rank per context
@@ -62,7 +56,8 @@ struct Ctx {
     size_t phys_bytes = 0;
     void *far = nullptr;      // far_kernel's sums, interval geometry and candidate runs of dense grids, grown on demand
     size_t far_bytes = 0;
-    double lines_per_cm = -1.;          // lines of the table per cm-1 (sizes far_kernel's workgroups), formed at the first dense call
+    double lines_per_cm = 0.;           // lines of the table per cm-1 (the tile choice of dense grids, far_kernel's workgroups); 0: no lines
+    bool no_physics_pass = false;       // MONORTM_NO_PHYSICS_PASS (A/B switch for measurements), read once per process when the first context is created
     hipStream_t far_stream = nullptr;   // far_plan_kernel runs beside physics_kernel (fork / join with far_ev)
     hipEvent_t far_ev[2] = {nullptr, nullptr};
     // lines_ms_kernel (batches of states on sparse channel sets): slot of (molecule, isotopologue 1) among the isotopologues the
@@ -180,8 +175,6 @@ hipError_t move_arena(void *dst, const void *src, size_t bytes, hipMemcpyKind ki
 void comm_release(Ctx *c);  // (RCCL communicator of the context, defined with the gather entry points)
 
 // one measurement switch from its textual value; unknown names / values are refused (MONORTM_EARG)
-constexpr double MONORTM_FAR_KAPPA_HOST = 1.2;   // = MONORTM_FAR_KAPPA of lines_device.hpp (least distance of a far line in tile half-widths)
-
 int set_option(Ctx *c, const char *name, const char *value) {
     const std::string n = name ? name : "", v = value ? value : "";
     const bool autov = v.empty() || v == "auto";
@@ -248,6 +241,19 @@ void prof_end(Ctx *c, hipStream_t s, Ctx::Ev &ev) {
     c->events.push_back(ev);
 }
 
+// A workspace grown on demand: at least `need` elements of `elem` bytes behind *p, *have of them there now.  Growth frees the old block
+// first (the contents are not kept); on failure the workspace is empty and the error is returned - the caller fails or falls back.
+hipError_t grow(void **p, size_t *have, size_t need, size_t elem = 1) {
+    if (need <= *have) return hipSuccess;
+    hipError_t e = *p ? hipFree(*p) : hipSuccess;
+    *p = nullptr;
+    *have = 0;
+    if (e == hipSuccess) e = hipMalloc(p, need * elem);
+    if (e == hipSuccess) *have = need;
+    else *p = nullptr;
+    return e;
+}
+
 // the *_dev entry points launch on the calling thread's current device: it must be the context's
 int check_device(Ctx *c) {
     int d = -1;
@@ -266,6 +272,74 @@ int check_modm_args(Ctx *c, int nprof, int nwn, int nlay_max, int nmol, int ibrd
     if (ixsect != 0 && ixsect != 1) { c->err = "ixsect must be 0 or 1"; return MONORTM_EARG; }
     if (ibrd != 0 && !c->host.any_brd) { /* nothing to do: flags all zero, same as ibrd = 0 */ }
     (void)v2;
+    return MONORTM_OK;
+}
+
+// Dense grids, ahead of lines_kernel: physics_kernel's records and far_kernel's sums where the plan wants them and their workspaces
+// can be had (a.phys / a.farmom stay null otherwise: lines_kernel forms the records, or the far field, itself)
+int dense_passes(Ctx *c, const ModmPlan &pl, ModmArgs &a, hipStream_t s) {
+    const int nlines = (int)c->host.size();
+    // (a workspace a later call needs less than a quarter of - or not at all - goes back to the device: a single large dense call
+    // must not pin tens of GB away from the caller's framework for the life of the context)
+    if (c->phys && (!pl.want_phys || pl.phys_need < c->phys_bytes / 4) && c->phys_bytes > (64u << 20)) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(s, &cap);
+        if (cap == hipStreamCaptureStatusNone) {
+            HIPCHK(c, hipDeviceSynchronize());   // (nobody reads the records any more)
+            HIPCHK(c, hipFree(c->phys));
+            c->phys = nullptr;
+            c->phys_bytes = 0;
+            if (c->far) { HIPCHK(c, hipFree(c->far)); c->far = nullptr; c->far_bytes = 0; }
+        }
+    }
+    if (pl.want_phys) {
+        // no room for the records: lines_kernel forms them in place, as on sparse grids
+        if (grow(&c->phys, &c->phys_bytes, pl.phys_need) != hipSuccess) (void)hipGetLastError();
+        if (c->phys) {
+            a.phys = c->phys;
+            a.phys_lines = nlines;
+            if (pl.far_levels > 0) {
+                if (pl.far_bytes > c->far_bytes && pl.far_bytes <= c->far_cap) {   // (beyond the cap lines_kernel forms the far field itself)
+                    if (grow(&c->far, &c->far_bytes, pl.far_bytes) == hipSuccess) {
+                        // all-ones bytes = NaN sums, -1 indices: an entry that a kernel reads without another having written it
+                        // shows in the results at once instead of depending on what the allocation held (once per growth)
+                        HIPCHK(c, hipMemsetAsync(c->far, 0xFF, pl.far_bytes, s));
+                    } else (void)hipGetLastError();   // no room: lines_kernel forms the far field itself
+                }
+                if (c->far && pl.far_bytes <= c->far_bytes) {
+                    a.farmom = static_cast<double *>(c->far);
+                    a.fargeom = reinterpret_cast<int *>(static_cast<char *>(c->far) + pl.far_mom_bytes);
+                    a.farseg = reinterpret_cast<int *>(static_cast<char *>(c->far) + pl.far_mom_bytes + pl.far_geom_bytes);
+                    a.far_levels = pl.far_levels;
+                    a.far_ni = pl.far_ni;
+                    a.far_tw = pl.TW;
+                    a.far_ntile = (int)pl.ntiles;
+                }
+            }
+            // far_plan_kernel (a chain of dependent table reads, ~65 us whatever the grid) needs nothing physics_kernel writes: it
+            // runs beside it on a stream of the context, forked from and joined to the caller's stream with two events (the pattern a
+            // stream capture follows as well)
+            const bool far_on = a.farmom != nullptr;
+            if (far_on && !c->far_stream) {
+                if (hipStreamCreateWithFlags(&c->far_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->far_ev[0], hipEventDisableTiming) != hipSuccess ||
+                    hipEventCreateWithFlags(&c->far_ev[1], hipEventDisableTiming) != hipSuccess) {
+                    c->err = "stream / events of the far-field plan could not be created";
+                    return MONORTM_EHIP;
+                }
+            }
+            if (far_on) {
+                HIPCHK(c, hipEventRecord(c->far_ev[0], s));
+                HIPCHK(c, hipStreamWaitEvent(c->far_stream, c->far_ev[0], 0));
+                launch_far_plan(a, c->lines, c->tables, c->far_stream);
+                HIPCHK(c, hipEventRecord(c->far_ev[1], c->far_stream));
+            }
+            launch_physics(a, c->lines, c->tables, nlines, pl.use_brd, s);
+            if (far_on) {
+                HIPCHK(c, hipStreamWaitEvent(s, c->far_ev[1], 0));
+                launch_far(a, c->lines, c->tables, pl.far_rho_tile, c->lines_per_cm > 0. ? c->lines_per_cm : 1., c->far_launches, s);
+            }
+        }
+    }
     return MONORTM_OK;
 }
 
@@ -787,6 +861,17 @@ int monortm_hip_init(const char *tape3_path, double v1, double v2, int icp, int 
     for (size_t i = 0; i < h.meta.size(); i++)
         if ((h.meta[i] >> 10) & 3) { L.lc_mask |= (1ull << (h.meta[i] & 63)); ncoupled++; }
     c->lc_frac = h.meta.empty() ? 0. : (double)ncoupled / (double)h.meta.size();
+    {
+        double vlo = 0., vhi = 0.;
+        if (!h.vnu.empty()) {
+            const auto mm = std::minmax_element(h.vnu.begin(), h.vnu.end());
+            vlo = *mm.first;
+            vhi = *mm.second;
+        }
+        c->lines_per_cm = (double)h.size() / std::max(vhi - vlo, 1.0);
+    }
+    static const bool no_physics_pass = getenv("MONORTM_NO_PHYSICS_PASS") != nullptr;
+    c->no_physics_pass = no_physics_pass;
     {   // the isotopologues the table holds per molecule (at least the first: a line without a known one reads its Doppler factor)
         int iso_max[MXMOL + 1] = {0};
         for (size_t i = 0; i < h.meta.size(); i++) {
@@ -1265,300 +1350,33 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
         a.XAMNT = XAMNT; a.ODXSEC = ODXSEC; a.nxs = c->xs.nxs;
     }
 
-    const double DVABS = 1.0;
-    const double V1ABS = (int)(vends[0]) - 3. * DVABS;
-    const double V2ABS = (int)(vends[1] + 3. * DVABS + 0.5);
-    const int NPTABS = (int)((V2ABS - V1ABS) / DVABS + 1.5);
-    if (NPTABS > 5050) { c->err = "wavenumber span exceeds the 5050-point continuum grid (N_ABSRB, lblparams.f90:35)"; return MONORTM_EARG; }
+    // what the call launches: decided from the shape, the table's and the device's constants alone (modm_plan.hpp)
+    ModmPlanIn in{};
+    in.nprof = nprof; in.nwn = nwn; in.nlay_max = nlay_max; in.nmol = nmol; in.real_kind = c->real_kind; in.ibrd = ibrd; in.ixsect = ixsect;
+    in.v1 = vends[0]; in.v2 = vends[1];
+    in.nlines = (long long)c->host.size(); in.lines_per_cm = c->lines_per_cm; in.lc_frac = c->lc_frac; in.any_brd = c->host.any_brd;
+    in.ms_nslot = c->ms_slot_host[nmol];   // slots of the molecules of this call: slot_base[nmol] pairs
+    in.cus = c->cus; in.phys_cap = c->phys_cap; in.far_cap = c->far_cap;
+    in.opt = c->opt;
+    in.no_physics_pass = c->no_physics_pass;
+    ModmPlan pl;
+    const char *why = nullptr;
+    if ((rc = modm_plan(in, &pl, &why))) { c->err = why; return rc; }
 
-    // few workgroups (single profiles): slice the line list over several blocks per (profile, layer, tile)
-    int nw, wpl;  // waves per workgroup, wavenumbers per lane
-    lines_config(nwn, c->real_kind, (long long)nprof * nlay_max, vends[1] - vends[0], &nw, &wpl);
-    // dense grids whose far field comes from far_kernel (the physics pass below: >= 4 tiles, records fit): tiles of two waves, 256
-    // wavenumbers.  The lines a tile evaluates directly are those within 1.2 of ITS half-widths, so halving the tile halves that
-    // work, and the level of intervals it adds to far_kernel costs less (configs[2]: lines_kernel 2.92 -> 1.84 ms, far_kernel
-    // 0.71 -> 1.06 ms).  Without far_kernel the four-wave tile with its own far field stays the better one.
-    static const bool phys_off_cfg = getenv("MONORTM_NO_PHYSICS_PASS") != nullptr;
-    // levels of far_kernel for tiles of tw wavenumbers - tiles, pairs, fours ... up to a half-width of ~3 cm-1 (configs[2], tiles of
-    // 0.64: three levels 1.01 ms, four 1.06, two 1.63) - and the bytes of its workspace (sums, interval geometry, candidate runs)
-    auto far_levels_for = [&](int tw) {
-        if (nwn < 2) return 0;
-        const int nt = (nwn + tw - 1) / tw;
-        const double rho_tile = 0.5 * tw * (vends[1] - vends[0]) / (double)(nwn - 1);
-        // no interval for which a line can be far: a far line lies >= kappa half-widths from the tile's centre AND holds the whole
-        // tile inside its 25 cm-1 window, i.e. kappa rho <= 25 - rho (wide sparse channel sets: the plan, the levels and the
-        // workspace would be paid for nothing - ADVICE r5).  far_kernel counts the workgroups of a molecule on an XCD in 16 bits
-        // (FarPlace::cnt): a grid of more tiles than that keeps the far field inside lines_kernel
-        if (MONORTM_FAR_KAPPA_HOST * rho_tile >= 25.0 - rho_tile || nt > 65535) return 0;
-        int levels = 1;
-        while (levels < FAR_MAXLEV && rho_tile * (double)(1 << levels) <= 3.0 && far_level_count(nt, levels - 1) > 1) levels++;
-        if (c->opt.far_levels >= 0) levels = std::min(c->opt.far_levels, FAR_MAXLEV);
-        return levels;
-    };
-    auto far_bytes_for = [&](int tw, int levels, size_t *mom_b, size_t *geom_b) {
-        const int nt = (nwn + tw - 1) / tw;
-        const size_t ni = (size_t)far_level_offset(nt, levels), states = (size_t)nprof * nlay_max;
-        *mom_b = states * ni * nmol * FAR_MOM_STRIDE * sizeof(double);
-        *geom_b = states * ni * nmol * FAR_GEOM_INTS * sizeof(int);
-        return *mom_b + *geom_b + states * (size_t)nt * nmol * FAR_SEG_INTS * sizeof(int);
-    };
-    const size_t kFarCap = c->far_cap;   // (beyond it lines_kernel forms the far field itself)
-    bool far_tiles = false;   // tiles of 128 / 256 wavenumbers chosen because far_kernel serves the grid
-    if (nw == 4 && wpl == 2 && c->opt.far_levels != 0 && !phys_off_cfg && (size_t)nprof * nlay_max * c->host.size() * 48 <= c->phys_cap) {
-        if (c->lines_per_cm < 0.) {   // (once per context: the table does not change)
-            double vlo = 0., vhi = 0.;
-            if (!c->host.vnu.empty()) {
-                const auto mm = std::minmax_element(c->host.vnu.begin(), c->host.vnu.end());
-                vlo = *mm.first;
-                vhi = *mm.second;
-            }
-            c->lines_per_cm = (double)c->host.size() / std::max(vhi - vlo, 1.0);
-        }
-        // the smallest tile - one wave (128 wavenumbers), two, four - that still has ~1000 lines within 1.2 of its half-widths (the
-        // ones it evaluates directly: below that the prologue of a tile outweighs them) and at least four tiles on the grid.
-        // configs[2] (1800 lines per cm-1, 0.005 cm-1 steps), line-sum segment: 512 wavenumbers 3.75 ms, 256: 3.02, 128: 2.69
-        const double dvm = (vends[1] - vends[0]) / (double)std::max(nwn - 1, 1);
-        for (int cand = 1; cand <= 2; cand *= 2) {
-            const int tw = 128 * cand;
-            size_t mb, gb;
-            const int lv = far_levels_for(tw);
-            if (nwn >= 4 * tw && c->lines_per_cm * 2.4 * (0.5 * tw * dvm) >= 1000. && lv > 0 && far_bytes_for(tw, lv, &mb, &gb) <= kFarCap) { nw = cand; far_tiles = true; break; }
-        }
-    }
-    if (c->opt.tile_waves && wpl >= 2) { nw = c->opt.tile_waves; wpl = 2; }  // measurements only: waves per workgroup of the two-wavenumber tiles
-    const int NTw = 64 * nw, TW = NTw * wpl;  // lines per chunk, wavenumbers per tile
-    const long long nblocks = (long long)((nwn + TW - 1) / TW) * nlay_max * nprof;
-    const long long nlines = (long long)c->host.size();
-    const long long cus = c->cus;  // (16 one-wave workgroups of lines_kernel are resident per compute unit: 128 VGPRs, 10 KB of LDS)
-    // batches of states on a sparse channel set, double precision: G states per wave, five wavenumbers per lane
-    // (lines_ms_kernel.hip) - when the batch makes whole rounds of such waves and the layout fits the LDS (decided before the line
-    // slices: this kernel walks the whole list of its states)
-    bool use_ms = false;
-    int ms_nprof = nprof;   // profiles [0, ms_nprof) go through lines_ms_kernel (all of them unless the batch is split, below)
-    MsArgs ms{};
-    if (c->real_kind == 8 && nw == 1 && wpl == 1 && nlines > 0 && c->opt.lines_ms != 0 && c->opt.nslice == 0) {
-        const int LPS = (nwn + MS_WPS - 1) / MS_WPS;
-        int G = std::min(std::min(12, 64 / LPS), nprof);
-        // slots of the molecules of this call: slot_base[nmol] pairs
-        ms.nslot = c->ms_slot_host[nmol];
-        // lines per chunk: a prepare pass holds spp = 64 / CL whole states (a lane then keeps its line through the passes of a chunk),
-        // so CL is one of the values that leave few lanes idle, the largest whose ceil(G / spp) passes stay within the budget - three
-        // passes of 64 (state, line) items, two, or one - and that leaves <= 10 KB of LDS a wave (16 waves per compute unit)
-        static const int cl_set[] = {64, 32, 21, 16, 12, 10, 9, 8};
-        for (int items = c->opt.ms_items ? c->opt.ms_items : 192; items >= 64 && !use_ms && G >= 1 && ms.nslot > 0; items -= 64) {
-            int CL = 0;
-            for (int cand : cl_set)
-                if (CL == 0 && (G + 64 / cand - 1) / (64 / cand) <= items / 64) CL = cand;
-            if (CL == 0) break;
-            ms.G = G; ms.LPS = LPS; ms.CL = CL; ms.spp = 64 / CL; ms.nsteps = (G + ms.spp - 1) / ms.spp;
-            // records per state in LDS: the chunk + 2 read ahead, padded so that the states' arrays start 24 banks apart (a lane reads
-            // 16 bytes of ITS state's record: eight states then touch eight disjoint groups of four banks)
-            ms.sa_stride = CL + 2;
-            while (ms.sa_stride % 8 != 3) ms.sa_stride++;
-            ms.npg = (nprof + G - 1) / G;
-            ms.inv_cl = (65536 + CL - 1) / CL;
-            ms.inv_lps = (65536 + LPS - 1) / LPS;
-            bool exact = ms.nsteps <= MS_MAXSTEPS;
-            for (int ln = 0; ln < 64 && exact; ln++) exact = (int)(((unsigned)ln * (unsigned)ms.inv_lps) >> 16) == ln / LPS;
-            for (int ln = 0; ln < 64 && exact; ln++) exact = (int)(((unsigned)ln * (unsigned)ms.inv_cl) >> 16) == ln / CL;
-            if (exact && lines_ms_lds(ms, nmol) <= 10240 - 160) use_ms = true;
-        }
-        const long long groups = (long long)ms.npg * nlay_max;
-        if (use_ms && c->opt.lines_ms < 0) {
-            // auto: a wave of lines_ms_kernel carries G states, so a batch is a few ROUNDS of such waves over the 16 wave slots of
-            // every compute unit, and a round that is only part full costs half a round + half its share (measured on configs[3]'s
-            // shape, 50 channels, final kernels: 128 / 256 / 320 / 384 / 512 / 640 / 768 / 1024 profiles = 0.34 / 0.67 / 0.84 / 1.0 / 1.34 /
-            // 1.68 / 2.0 / 2.67 rounds take 0.69 / 0.83 / 0.98 / 1.0 / 1.63 / 1.74 / 1.96 / 2.64 times the 0.35 ms of a full round;
-            // lines_kernel takes 1.26 of that per round of states whatever the batch: tools/rounds_sweep.sh).
-            // From two rounds on the part-full round hides behind the others (2.0 -> 1.96, 2.67 -> 2.65).  Lists with many coupled lines
-            // (their shapes go one wavenumber at a time here, Voigt pairs through a queue per wave): bench's c2lc shape at 384 profiles
-            // 0.524 against 0.551 ms - a margin of 5 % instead of 20 %, so only whole rounds and large batches take this kernel.
-            const double r = (double)groups / (double)(16 * cus), fr = r - std::floor(r);
-            const double cost_ms = (r >= 2.0) ? r : std::floor(r) + (fr > 0.02 ? 0.5 + 0.5 * fr : 0.0);
-            // What lines_kernel costs per round of lines_ms_kernel's states: 1.26 at six states a wave (50 channels).  A wave's evaluate stage
-            // and prologue cost the same for four states as for nine, its prepare stage goes with the states: per state 0.055 + 0.60 / G of
-            // a six-state wave's time (stage times of DESIGN 3.1m), lines_kernel the same per state whatever the channel count
-            // (tools/rounds_sweep.sh with MONORTM_BENCH_CHANNELS: 64 channels = four states a wave 1.01, 40 = eight 1.42, 32 = nine 1.33).
-            // Species broadening (IBRD = 1: both kernels walk the seven-species blocks in every pass - 0.472 against 0.534 ms at 384
-            // profiles of bench's c4brd shape) and coupled lists (above) narrow the margin.
-            double gain = std::min(1.35, 1.26 * 0.155 / (0.055 + 0.60 / (double)G));
-            if (c->lc_frac > 0.02) gain *= 1.04 / 1.26;
-            else if (ibrd != 0 && c->host.any_brd) gain *= 1.13 / 1.26;
-            // between one and two rounds: the whole rounds through lines_ms_kernel, the rest of the profiles through lines_kernel (two
-            // launches on the stream; 512 profiles of configs[3]'s shape: 384 + 128 = 0.37 + 0.16 ms against 0.60 either way)
-            const long long npg_round = (16 * cus) / std::max(nlay_max, 1);   // groups of G profiles that fill the wave slots once
-            const long long n_whole = (long long)G * npg_round * (long long)std::floor(r);
-            const double cost_split = (r >= 1.0 && r < 2.0 && n_whole >= G && n_whole < nprof)
-                                          ? std::floor(r) + gain * (double)(((nprof - n_whole + G - 1) / G) * nlay_max) / (double)(16 * cus) : 1e30;
-            if (G * nwn * 10 < 64 * MS_WPS * 7) use_ms = false;
-            else if (cost_split < 0.97 * std::min(cost_ms, gain * r)) ms_nprof = (int)n_whole;
-            else if (cost_ms >= gain * r) use_ms = false;
-        }
-        if (use_ms && ms_nprof < nprof) ms.npg = (ms_nprof + G - 1) / G;
-    }
-    int nslice = 1;
-    if (nblocks < 4 * cus && nlines >= 2 * NTw) {
-        // at least ~40 lines per slice: below that the prologue of a workgroup outweighs its share of the lines
-        nslice = (int)std::min<long long>(16, std::min<long long>((8 * cus + nblocks - 1) / nblocks, nlines / 40));
-        if (nslice < 1) nslice = 1;
-    } else {
-        // long line lists: a block walks hundreds of chunks, and with only a few rounds of blocks over the chip
-        // (resident: 16 one-wave or 4 four-wave blocks per CU) the last round runs half empty.  Slices of >= 32 chunks
-        // until there are >= 8 rounds.
-        // (a grid served by far_kernel walks a quarter of its window at most: four rounds - configs[2], one-wave tiles: three
-        // slices 2.33 ms for the line-sum segment, five 2.34, seven 2.36, two 2.40, one 2.64)
-        const long long resident = cus * (16 / nw), chunks = nlines / NTw;
-        const long long want = ((far_tiles ? 4 : 8) * resident + nblocks - 1) / nblocks;
-        nslice = (int)std::max<long long>(1, std::min<long long>(16, std::min<long long>(want, chunks / 32)));
-        // a grid that fills at most five eighths of the wave slots: two slices use the rest (c4 shape, 32 profiles: 0.096 ->
-        // 0.089 ms per step).  A full round is better off unsliced since the waves order themselves by progress (a.fair below):
-        // 64 profiles 0.155 -> 0.127 ms, c5 0.188 -> 0.151 ms per step
-        if (nslice == 1 && nblocks * nw <= 10 * cus && nlines >= 3 * NTw) nslice = 2;
-    }
-    if (c->opt.nslice) nslice = c->opt.nslice;  // measurements only
-    if (use_ms) nslice = 1;   // (lines_ms_kernel walks the whole list of its states)
-    if (nslice > 1) {
-        const size_t need = (size_t)nslice * nprof * nlay_max * nmol * nwn;
-        if (need > c->partial_elems) {
-            if (c->partial) HIPCHK(c, hipFree(c->partial));
-            c->partial = nullptr;
-            c->partial_elems = 0;
-            HIPCHK(c, hipMalloc(&c->partial, need * (size_t)c->real_kind));
-            c->partial_elems = need;
-        }
-    }
-    a.nslice = nslice;
+    HIPCHK(c, grow(&c->partial, &c->partial_elems, pl.partial_elems, (size_t)c->real_kind));   // (0 elements: one slice)
+    a.nslice = pl.nslice;
     a.partial = c->partial;
-    // progress-ordered wave priorities (lines_kernel.hip): grids of at most a few rounds over the 4096 wave slots that 128 VGPRs
-    // leave on 256 CUs.  Re-measured in round 4 with the shorter kernels: one-wave double-precision tiles gain at every size
-    // (4 / 8 / 16 rounds: -3 % / -0.6 % / -0.5 %), the four-wavenumber float tile loses at 8 rounds (configs[4] whole: 1.127
-    // against 1.099 ms), multi-wave tiles lose 1 % at 8, the one-wave two-wavenumber tile gains 2 % at 8 (round 3's configs[4]
-    // workload: 0.823 against 0.841 ms) - so: always for the first, up to 8 rounds for the last, up to 4 for the others
-    // (round 5, after the tested sub-runs are skipped per (wave, k): the four-wavenumber float tile gains at 8 rounds as well -
-    // configs[4] whole 0.992 -> 0.948 ms - so every one-wave tile up to 8 rounds)
-    a.fair = ((nw == 1 && wpl == 1 && c->real_kind == 8) || nblocks * nslice * nw <= ((nw == 1) ? 8 : 4) * 16 * cus) ? 1 : 0;
-    if (c->opt.fair >= 0) a.fair = c->opt.fair;  // measurements only
-    // microwave to far infrared (last wavenumber below 820 cm-1: no O3 / O2 / Rayleigh term anywhere): the fused finish kernel
-    // (option "finish" = generic: an A/B switch for measurements and tests)
-    const bool mw = vends[1] < 820.0 && NPTABS <= 1000 && !c->opt.finish_generic;
-#ifdef LINES_TIMING
-    if (mw) {
-#else
-    if (mw && nslice == 1) {
-#endif
-        const size_t need = (size_t)nprof * nlay_max * nwn;
-        if (need > c->osum_elems) {
-            if (c->osum) HIPCHK(c, hipFree(c->osum));
-            c->osum = nullptr;
-            c->osum_elems = 0;
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->osum), need * sizeof(double)));
-            c->osum_elems = need;
-        }
+    a.fair = pl.fair;
+    if (pl.need_osum) {
+        HIPCHK(c, grow(reinterpret_cast<void **>(&c->osum), &c->osum_elems, pl.osum_elems, sizeof(double)));
         a.osum = c->osum;
     }
     Ctx::Ev ev{};
-    const bool use_brd = ibrd != 0 && c->host.any_brd;
-    size_t dyn = sizeof(double) * (size_t)(19 * nmol) + sizeof(int) * (size_t)(2 * nmol + 2 + 2 * FAR_SEGS * nmol);
-#ifdef MONORTM_EXTRA_LDS   // occupancy experiment (tools/build_variant.sh): fewer resident workgroups per CU
-    dyn += MONORTM_EXTRA_LDS;
-#endif
-    if (nprof > 65535) { c->err = "more than 65535 profiles in one call: split the batch"; return MONORTM_EARG; }
-    dim3 grid(((nwn + TW - 1) / TW) * nslice, nprof, nlay_max);  // (tile x slice, profile, layer): see lines_kernel
-    // dense grids (a line sits in the window of many tiles): its tile-independent part once per (profile, layer) - 48 B of room (32 written for an uncoupled line) per
-    // (layer, line), up to an eighth of the device memory; lines_kernel then reads the record instead of forming it in every tile
-    const long long ntiles = (nwn + TW - 1) / TW;
-    static const bool phys_off = getenv("MONORTM_NO_PHYSICS_PASS") != nullptr;  // A/B switch for measurements
-    const size_t phys_need = (size_t)nprof * nlay_max * (size_t)nlines * 48;
     prof_begin(c, s, 0, ev);
-    // (a workspace a later call needs less than a quarter of - or not at all - goes back to the device: a single large dense call
-    // must not pin tens of GB away from the caller's framework for the life of the context)
-    const bool want_phys = ntiles >= 4 && nlines > 0 && phys_need <= c->phys_cap && !phys_off;
-    if (c->phys && (!want_phys || phys_need < c->phys_bytes / 4) && c->phys_bytes > (64u << 20)) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s, &cap);
-        if (cap == hipStreamCaptureStatusNone) {
-            HIPCHK(c, hipDeviceSynchronize());   // (nobody reads the records any more)
-            HIPCHK(c, hipFree(c->phys));
-            c->phys = nullptr;
-            c->phys_bytes = 0;
-            if (c->far) { HIPCHK(c, hipFree(c->far)); c->far = nullptr; c->far_bytes = 0; }
-        }
-    }
-    if (want_phys) {
-        if (phys_need > c->phys_bytes) {
-            if (c->phys) HIPCHK(c, hipFree(c->phys));
-            c->phys = nullptr;
-            c->phys_bytes = 0;
-            if (hipMalloc(&c->phys, phys_need) == hipSuccess) c->phys_bytes = phys_need;
-            else {  // no room for the records: lines_kernel forms them in place, as on sparse grids
-                c->phys = nullptr;
-                (void)hipGetLastError();
-            }
-        }
-        if (c->phys) {
-            a.phys = c->phys;
-            a.phys_lines = (int)nlines;
-            // multi-wave tiles (the ones that have a far field): the far lines of every tile through far_kernel
-            const int levels = (wpl == 2) ? far_levels_for(TW) : 0;
-            if (levels > 0) {
-                size_t mom_b, geom_b;
-                const size_t need = far_bytes_for(TW, levels, &mom_b, &geom_b), ni = (size_t)far_level_offset((int)ntiles, levels);
-                if (need > c->far_bytes && need <= kFarCap) {
-                    if (c->far) HIPCHK(c, hipFree(c->far));
-                    c->far = nullptr;
-                    c->far_bytes = 0;
-                    if (hipMalloc(&c->far, need) == hipSuccess) {
-                        c->far_bytes = need;
-                        // all-ones bytes = NaN sums, -1 indices: an entry that a kernel reads without another having written it
-                        // shows in the results at once instead of depending on what the allocation held (once per growth)
-                        HIPCHK(c, hipMemsetAsync(c->far, 0xFF, need, s));
-                    } else (void)hipGetLastError();   // no room: lines_kernel forms the far field itself
-                }
-                if (c->far && need <= c->far_bytes) {
-                    a.farmom = static_cast<double *>(c->far);
-                    a.fargeom = reinterpret_cast<int *>(static_cast<char *>(c->far) + mom_b);
-                    a.farseg = reinterpret_cast<int *>(static_cast<char *>(c->far) + mom_b + geom_b);
-                    a.far_levels = levels;
-                    a.far_ni = (int)ni;
-                    a.far_tw = TW;
-                    a.far_ntile = (int)ntiles;
-                }
-            }
-            // far_plan_kernel (a chain of dependent table reads, ~65 us whatever the grid) needs nothing physics_kernel writes: it
-            // runs beside it on a stream of the context, forked from and joined to the caller's stream with two events (the pattern a
-            // stream capture follows as well)
-            const bool far_on = a.farmom != nullptr;
-            if (far_on && !c->far_stream) {
-                if (hipStreamCreateWithFlags(&c->far_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->far_ev[0], hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&c->far_ev[1], hipEventDisableTiming) != hipSuccess) {
-                    c->err = "stream / events of the far-field plan could not be created";
-                    return MONORTM_EHIP;
-                }
-            }
-            if (far_on) {
-                HIPCHK(c, hipEventRecord(c->far_ev[0], s));
-                HIPCHK(c, hipStreamWaitEvent(c->far_stream, c->far_ev[0], 0));
-                launch_far_plan(a, c->lines, c->tables, c->far_stream);
-                HIPCHK(c, hipEventRecord(c->far_ev[1], c->far_stream));
-            }
-            launch_physics(a, c->lines, c->tables, (int)nlines, use_brd, s);
-            if (far_on) {
-                HIPCHK(c, hipStreamWaitEvent(s, c->far_ev[1], 0));
-                launch_far(a, c->lines, c->tables, 0.5 * TW * (vends[1] - vends[0]) / (double)std::max(nwn - 1, 1),
-                           c->lines_per_cm > 0. ? c->lines_per_cm : 1., c->far_launches, s);
-            }
-        }
-    }
-    if (use_ms) {
-        const long long groups = (long long)ms.npg * nlay_max;
-        const size_t need = lines_ms_scratch(ms, groups);
-        if (need > c->ms_scratch_bytes) {
-            if (c->ms_scratch) HIPCHK(c, hipFree(c->ms_scratch));
-            c->ms_scratch = nullptr;
-            c->ms_scratch_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->ms_scratch, need));
-            c->ms_scratch_bytes = need;
-        }
+    if ((rc = dense_passes(c, pl, a, s))) return rc;
+    MsArgs ms = pl.ms;
+    if (pl.use_ms) {
+        HIPCHK(c, grow(&c->ms_scratch, &c->ms_scratch_bytes, lines_ms_scratch(ms, (long long)ms.npg * nlay_max)));
         const size_t nl4 = (std::max<size_t>(c->host.size(), 1) + 3) / 4 * 4;
         if (!c->ms_reach) {   // two bytes + one float per table line (the table does not change)
             void *p = nullptr;
@@ -1572,56 +1390,40 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
         ms.slot_base = c->ms_slot_base;
         ms.ablate = c->opt.ms_ablate;
     }
-    if (use_ms && ms_nprof < nprof) {
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+    if (pl.use_ms && pl.ms_nprof < nprof) {
         // a split batch (double precision, one tile, one slice, no dense-grid workspaces): the same arguments with nprof = the whole
         // rounds for lines_ms_kernel, and shifted by those profiles for lines_kernel
         ModmArgs am = a, aw = a;
-        am.nprof = ms_nprof;
-        const size_t st = (size_t)ms_nprof * nlay_max;   // states ahead of the second part
+        am.nprof = pl.ms_nprof;
+        const size_t st = (size_t)pl.ms_nprof * nlay_max;   // states ahead of the second part
         auto shift = [](const void *p, size_t elems) { return p ? static_cast<const void *>(static_cast<const double *>(p) + elems) : nullptr; };
-        aw.nprof = nprof - ms_nprof;
+        aw.nprof = nprof - pl.ms_nprof;
         aw.P = shift(a.P, st); aw.T = shift(a.T, st); aw.CLW = shift(a.CLW, st); aw.WBRODL = shift(a.WBRODL, st);
         aw.WKL = shift(a.WKL, st * nmol);
-        aw.nlay = a.nlay + ms_nprof;
+        aw.nlay = a.nlay + pl.ms_nprof;
         aw.O = const_cast<void *>(shift(a.O, st * nwn)); aw.O_CLW = const_cast<void *>(shift(a.O_CLW, st * nwn));
         aw.O_BY_MOL = const_cast<void *>(shift(a.O_BY_MOL, st * nmol * nwn));
         aw.OC = const_cast<void *>(shift(a.OC, st * MONORTM_NCONT * nwn));
         aw.osum = a.osum ? a.osum + st * nwn : nullptr;
-        launch_lines_ms(am, c->lines, c->tables, ms, use_brd, s);
-        launch_lines(aw, c->lines, c->tables, nw, wpl, use_brd, dim3(grid.x, (unsigned)aw.nprof, grid.z), dyn, s);
-    } else if (use_ms) launch_lines_ms(a, c->lines, c->tables, ms, use_brd, s);
-    else launch_lines(a, c->lines, c->tables, nw, wpl, use_brd, grid, dyn, s);
+        launch_lines_ms(am, c->lines, c->tables, ms, pl.use_brd, s);
+        launch_lines(aw, c->lines, c->tables, pl.nw, pl.wpl, pl.use_brd, dim3(grid.x, (unsigned)aw.nprof, grid.z), pl.dyn_lds, s);
+    } else if (pl.use_ms) launch_lines_ms(a, c->lines, c->tables, ms, pl.use_brd, s);
+    else launch_lines(a, c->lines, c->tables, pl.nw, pl.wpl, pl.use_brd, grid, pl.dyn_lds, s);
     prof_end(c, s, ev);
     HIPCHK(c, hipGetLastError());
-    // finest coarse grid: 1 cm-1 (O2 A band) above 1340 cm-1, 2 cm-1 (CO2) below
-    const bool high = vends[1] > 1340.0;
-    const int csize = (high ? NPTABS : NPTABS / 2) + 24;
-    // few workgroups (single profiles) below 1340 cm-1: the four waves of a workgroup run the passes side by side, each
-    // with its own grids; a grid that fills the chip is served better by one pass after the other
-    const bool par = !high && (long long)nlay_max * nprof < 16 * cus;
-    const int fin_threads = par ? 256 : ((NPTABS <= 256 && nwn <= 128) ? 64 : 256);  // microwave-sized grids: one wave
-    // one-wave workgroups on a grid of >= 4096 of them: four layers per wave, a 16-lane team each (continuum_kernel.hip)
-    const bool quad = !high && !par && fin_threads == 64 && NPTABS <= 64;
-    const int lds_sets = (par || quad) ? 4 : 1;
-    const size_t lds = sizeof(double) * (size_t)(NPTABS + 4 + csize) * lds_sets;
     prof_begin(c, s, 1, ev);
     if (ixsect == 1) launch_xsec(a, c->xs, s);   // MONORTM_XSEC_SUB comes first (modm.f90:197); the finish kernel adds its sum into O
-    a.slices_reduced = 0;
-    if (nslice > 1 && (long long)nmol * nwn > 4096) {  // wide grids: the slice sums at full memory bandwidth
-        launch_reduce_slices(a, s);
-        a.slices_reduced = 1;
-    }
-    if (mw) {
-        const hipError_t e = launch_finish_mw(a, c->tables, vends[0], vends[1], V1ABS, V2ABS, NPTABS, c->mw_cache, s);
+    a.slices_reduced = pl.slices_reduced;
+    if (pl.slices_reduced) launch_reduce_slices(a, s);
+    if (pl.mw) {
+        const hipError_t e = launch_finish_mw(a, c->tables, vends[0], vends[1], pl.V1ABS, pl.V2ABS, pl.NPTABS, c->mw_cache, s);
         if (e != hipSuccess) {
             c->err = std::string("launch_finish_mw: ") + (c->mw_cache.why ? c->mw_cache.why : hipGetErrorString(e));
             return c->mw_cache.why ? MONORTM_EUNSUPPORTED : MONORTM_EHIP;
         }
-        c->finish_launches[0]++;
-    } else {
-        HIPCHK(c, launch_finish(a, c->tables, V1ABS, V2ABS, NPTABS, csize, high, par, fin_threads, lds, lds_sets, s));
-        c->finish_launches[high ? 1 : (par ? 2 : (quad ? 3 : (fin_threads == 64 ? 4 : 5)))]++;
-    }
+    } else HIPCHK(c, launch_finish(a, c->tables, pl.V1ABS, pl.V2ABS, pl.NPTABS, pl.csize, pl.high, pl.par, pl.fin_threads, pl.fin_lds, pl.lds_sets, s));
+    c->finish_launches[pl.finish_variant]++;
     prof_end(c, s, ev);
     HIPCHK(c, hipGetLastError());
     return MONORTM_OK;

@@ -67,6 +67,9 @@ constexpr int NSCOR = MXMOL * 9;
 #define MONORTM_FAR_P 56
 #endif
 constexpr int FAR_P = MONORTM_FAR_P;   // Chebyshev sums of a far field (lines_device.hpp: "Far field of a tile")
+#ifndef MONORTM_FAR_KAPPA
+#define MONORTM_FAR_KAPPA 1.2          // least distance of a far line in tile half-widths (lines_device.hpp: FAR_KAPPA; modm_plan.hpp: which grids have far lines)
+#endif
 // ---- the far field of dense grids formed OUTSIDE lines_kernel (far_kernel.hip, round 5) -------------------------------------------
 // Intervals of wavenumbers in up to FAR_MAXLEV levels: level 0 = the tiles of lines_kernel (tw wavenumbers each), level l = groups
 // of 2^l consecutive tiles.  gi = far_level_offset(l) + j numbers them; the parent of (l, j) is (l + 1, j / 2).
@@ -394,6 +397,7 @@ __host__ __device__ inline R *wp(void *p) { return static_cast<R *>(p); }
 // ---- lines_ms_kernel (round 6): G states per one-wave workgroup, MS_WPS wavenumbers per lane (lines_ms_kernel.hip) -------------------
 #define MS_WPS 5
 #define MS_MAXSTEPS 4
+constexpr int MS_HOTA_BYTES = 32;   // sizeof(HotA) (lineshape.hpp; asserted in lines_ms_kernel.hip): the host sizes the wave's LDS with it (modm_plan.hpp)
 struct MsArgs {
     int G, LPS, CL, nsteps;   // states per wave, lanes per state, lines per chunk, prepare passes (ceil(G / spp))
     int spp;                  // states per prepare pass (64 / CL): lane = sub CL + l serves line l of state t spp + sub in pass t
@@ -408,14 +412,12 @@ struct MsArgs {
     float *near0;             // [lines of the table] distance of the table centre to the nearest channel, rounded down (ms_reach_kernel)
     int ablate;               // MONORTM_EXPERIMENT builds only (option ms_ablate; wrong results): 1 = prologue only, 2 = no evaluate stage, 3-5 parts of it
 };
-size_t lines_ms_lds(const MsArgs &ms, int nmol);
 size_t lines_ms_scratch(const MsArgs &ms, long long nwg);
 void launch_lines_ms(const ModmArgs &a, const DevLines &L, const DevTables &tb, const MsArgs &ms, bool ibrd, hipStream_t s);
 
 // ---- launchers: one translation unit per kernel family -------------------------------------------------------
-// lines_kernel.hip: block = nw waves, lane = wpl wavenumbers (tile = wpl * nw * 64), as chosen by lines_config();
+// lines_kernel.hip: block = nw waves, lane = wpl wavenumbers (tile = wpl * nw * 64), as chosen by lines_config() (modm_plan.hpp);
 // ibrd selects the species-broadening instantiation
-void lines_config(int nwn, int real_kind, long long states, double span, int *nw, int *wpl);  // span = wn[nwn-1] - wn[0]
 void launch_physics(const ModmArgs &a, const DevLines &L, const DevTables &tb, int nlines, bool ibrd, hipStream_t s);
 // far_kernel.hip: far_plan_kernel (which lines are far for which interval; independent of physics_kernel), then far_kernel per level,
 // top level first (reads the plan and physics_kernel's records)

@@ -1101,9 +1101,7 @@ __device__ __forceinline__ void eval_dispatch(const unsigned long long *mAL, con
 // at kappa = 1.6, 9e-14 at 1.3 (relative to the term, h from 1e-5 to 0.2; tests/test_hip_parity.py::test_far_field_dense_grid).
 // ------------------------------------------------------------------------------------------------
 // (FAR_P = MONORTM_FAR_P, 56 sums: device_common.hpp - the host sizes far_kernel's buffers with it)
-#ifndef MONORTM_FAR_KAPPA
-#define MONORTM_FAR_KAPPA 1.2
-#endif
+// (MONORTM_FAR_KAPPA, 1.2: device_common.hpp - the host decides with it which grids have far lines at all)
 constexpr double FAR_KAPPA = MONORTM_FAR_KAPPA;
 // terms until |w|^n < 1e-15 at the least distance kappa: 34.5 / ln(kappa + sqrt(kappa^2 - 1)) + 3 - 59 at 1.2 (round 5, first session: 60 sums; now 56, 1.86^-56 = 7e-16: a
 // multiple of four, the butterfly forms four at a time; measured on c3: kappa / sums 1.6 / 36: 5.54 ms, 1.45 / 44: 5.48, 1.3 / 52:

@@ -22,6 +22,7 @@
 #define MONORTM_EXP_SGPR_CONSTANTS 1   // (exp_prep of lines_device.hpp: see there)
 #include "lines_device.hpp"
 #include "lines_ms_asm.hpp"
+#include "modm_plan.hpp"
 
 namespace {
 using namespace monortm_dev;
@@ -773,10 +774,7 @@ __global__ __launch_bounds__(64, 4) void lines_ms_kernel(ModmArgs a, DevLines L,
 }  // namespace
 
 namespace monortm_dev {
-size_t lines_ms_lds(const MsArgs &ms, int nmol) {
-    return sizeof(HotA) * (size_t)(ms.G * ms.sa_stride) + sizeof(double) * (size_t)(64 + ms.G * 20 + ms.G * nmol + 2 * ms.G * ms.nslot) +
-           sizeof(unsigned long long) * (size_t)(4 + MS_MAXSTEPS + 2 * MS_WPS + 1) + sizeof(int) * (size_t)(3 * nmol + 2 + 64) + (size_t)ms.nsteps * 64 + 16;
-}
+static_assert(sizeof(HotA) == MS_HOTA_BYTES, "lines_ms_lds (modm_plan.hpp) sizes the records of a chunk with MS_HOTA_BYTES");
 size_t lines_ms_scratch(const MsArgs &ms, long long nwg) { return (size_t)nwg * ms_scratch_per_wg(ms.G, ms.CL); }
 void launch_lines_ms(const ModmArgs &a, const DevLines &L, const DevTables &tb, const MsArgs &ms, bool ibrd, hipStream_t s) {
     const int nlines = L.mol_start[MXMOL + 1];

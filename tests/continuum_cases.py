@@ -7,7 +7,7 @@ pure-Python input builders monortm_amd.synth / monortm_amd.tape3 are all it take
 Line file: the 1672 bytes that a TAPE3 holds ahead of its first line block (as test_edge_empty_line_list_and_wide_grid cuts them).
 Without lines O_BY_MOL is zero, and O, OC and O_CLW are the work of the finish kernel alone.
 
-Launch variants (api.hip, restated in variant()): `mw` finish_mw_kernel, `high` finish_kernel<HIGH>, `par` <PAR>, `q4` <Q4>, `plain64` /
+Launch variants (modm_plan.hpp, restated in variant()): `mw` finish_mw_kernel, `high` finish_kernel<HIGH>, `par` <PAR>, `q4` <Q4>, `plain64` /
 `plain256` finish_kernel with 64 / 256 threads.  A case names the variant every one of its runs must reach; the GPU test asserts it
 with monortm_hip_counter.
 
@@ -61,7 +61,7 @@ def nptabs(v1: float, v2: float) -> int:
 
 
 def variant(wn: np.ndarray, nprof: int, nlay_max: int, cus: int, generic: bool = False) -> str:
-    """The launch variant a call takes: the rule of api.hip, restated from its description, so that the case table can be checked
+    """The launch variant a call takes: the rule of modm_plan.hpp, restated from its description, so that the case table can be checked
     on a machine without a GPU for any count of compute units."""
     npt, nwn, last = nptabs(wn[0], wn[-1]), len(wn), float(wn[-1])
     if last < 820.0 and npt <= 1000 and not generic:

@@ -7,11 +7,11 @@ lists are dense and hold one molecule (or one dense molecule and a few lines of 
 dominates: the launcher then takes the other variants by itself - no test sets MONORTM_FAR_WAVES.
 
 Every case declares the NWF of each of its launches (`expect`).  plan() restates, in integer and double arithmetic, what the host does
-with a case - the blocks of the line file it keeps, lines_config, the tile choice and the level count of api.hip, the steps -> NWF rule
+with a case - the blocks of the line file it keeps, lines_config, the tile choice and the level count of modm_plan.hpp, the steps -> NWF rule
 of launch_far - and geometry() what far_plan_kernel finds for one (interval, molecule, layer state): the Voigt guard, the seven FarGeom
 indices, inheritance, the runs of far_kernel and the runs left to the tile.  census() walks the steps of far_kernel with them (which
 lines a step holds, one or two resonances, its order from far_order restated in float32, the sign of A in far_slot_of).
-tests/test_far_cpu.py asserts that the declared variants follow from the mirror with a margin and that the cases reach the branches
+tests/test_modm_plan_cpu.py holds plan() to modm_plan.hpp itself (host code, no GPU); tests/test_far_cpu.py asserts that the declared variants follow from the mirror with a margin and that the cases reach the branches
 they were built for; tests/test_far_kernel.py reads the variants back from the launch counters and compares with the oracle.
 
 Lists: molecule subsets of synth.synthetic_lines(80000, seed, vhi = just above the last wavenumber + 25), thinned to a line count.
@@ -40,7 +40,7 @@ FAR_MOM_STRIDE, FAR_GEOM_INTS, FAR_SEG_INTS = FAR_P + 2, 8, 10
 THRESHOLDS = (16.0, 32.0, 128.0)                             # launch_far: steps <= 16 -> 1, <= 32 -> 2, <= 128 -> 4, else 8
 MARGIN = 0.10                                                # every level's steps stay this far (relative) from every threshold
 NWF = (1, 2, 4, 8)
-FAR_CAP, PHYS_CAP = 1 << 30, 2 << 30                         # api.hip: the least workspace caps of a context
+FAR_CAP, PHYS_CAP = 1 << 30, 2 << 30                         # api.hip (Ctx): the least workspace caps of a context
 K_BOLTZ, K_AVOGAD, K_CLIGHT, K_T0, K_P0 = 1.3806503e-16, 6.02214199e23, 2.99792458e10, 296.0, 1013.25
 # lightest isotopologue (the widest Doppler line) of the molecules that hold lines here, g / mol (TIPS / molec_mass of the reference);
 # the guard's two sides are asserted 5 % apart wherever the mirror decides with them

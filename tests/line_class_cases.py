@@ -502,7 +502,7 @@ def walk(eff, family: str):
 
 
 def ms_layout(nwn, nprof, nslot, ms_items=192):
-    """api.hip's choice for lines_ms_kernel, (G, CL): the restatement of tests/test_ms_prepare_passes.py."""
+    """modm_plan.hpp's choice for lines_ms_kernel, (G, CL): the restatement of tests/test_ms_prepare_passes.py."""
     from test_ms_prepare_passes import _layout
 
     got = _layout(nwn, nprof, ms_items, nslot)

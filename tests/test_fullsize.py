@@ -180,7 +180,7 @@ def test_c5_full_batch_single_precision(workdir):
     host = rt4.run(profs)   # the same batch (= the same kernel configuration) through host buffers
     for x, y in zip(host[200:256], d4[200:256]):
         assert np.array_equal(x.o, y.o) and np.array_equal(x.tb, y.tb) and np.array_equal(x.o_by_mol, y.o_by_mol)
-    # a batch below 8192 (profile, layer) states takes two tiles of two wavenumbers per lane instead of one of four (api.hip
+    # a batch below 8192 (profile, layer) states takes two tiles of two wavenumbers per lane instead of one of four (modm_plan.hpp
     # lines_config): the radiation term and the molecule sums are held in double there - the same results to float rounding
     part = rt4.run(profs[200:256])
     for x, y in zip(part, d4[200:256]):

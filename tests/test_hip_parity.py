@@ -592,8 +592,8 @@ np.savez(out, o=d.o, obm=d.o_by_mol, tb=d.tb, rad=d.rad)
 @pytest.mark.parametrize("ibrd,real_kind", [(0, 8), (1, 8), (0, 4)])
 def test_physics_pass_equals_in_place(ibrd, real_kind, workdir, gpu):
     """Grids of >= 4 tiles: physics_kernel forms the tile-independent part of every line once per (profile, layer) and
-    lines_kernel reads it back.  Bitwise the same as forming it inside every tile (MONORTM_NO_PHYSICS_PASS=1 is read at first
-    use, hence child processes), for coupled lines, species broadening and the single-precision build; and within 1e-10
+    lines_kernel reads it back.  Bitwise the same as forming it inside every tile (MONORTM_NO_PHYSICS_PASS=1 is read once per
+    process, hence child processes), for coupled lines, species broadening and the single-precision build; and within 1e-10
     of the oracle."""
     import os
     import subprocess

@@ -3,7 +3,7 @@ is (sub, l) = line l of the chunk for state t SPP + sub in pass t, and the line 
 that mapping can go wrong, the kernel forced with `lines_kernel = ms` and the chunk size set with `ms_items`; every profile against
 the oracle (north_star's 1e-6) and against lines_kernel (1e-11: the two differ by the rounding of the shared reciprocals).
 
-The layout the host chooses (api.hip; `_layout` below mirrors it): G = min(12, 64 // LPS, nprof) states a wave with
+The layout the host chooses (modm_plan.hpp; `_layout` below mirrors it, tests/test_modm_plan_cpu.py holds the two together): G = min(12, 64 // LPS, nprof) states a wave with
 LPS = ceil(nwn / 5); CL the largest of 64, 32, 21, 16, 12, 10, 9, 8 whose ceil(G / SPP) passes are within ms_items // 64; one pass
 less while the wave's LDS exceeds 10080 bytes.  For the cases here (both line lists: five (molecule, isotopologue) slots):
 
@@ -55,7 +55,7 @@ def gpu():
 
 
 def _layout(nwn, nprof, ms_items, nslot):
-    """api.hip's choice for lines_ms_kernel: (G, CL, passes, items budget taken, LDS bytes of the wave)."""
+    """modm_plan.hpp's choice for lines_ms_kernel: (G, CL, passes, items budget taken, LDS bytes of the wave)."""
     lps = (nwn + 4) // 5
     g = min(12, 64 // lps, nprof)
     for items in range(ms_items, 63, -64):

@@ -13,6 +13,7 @@ CF="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-pass-faile
 /opt/rocm/bin/hipcc $CF -mllvm -disable-machine-licm -DMONORTM_EXPERIMENT=1 "$@" -c $CSRC/lines_ms_kernel.hip -o $OUT/obj_$NAME/lines_ms_kernel.o &
 /opt/rocm/bin/hipcc $CF -DMONORTM_EXPERIMENT=1 "$@" -c $CSRC/api.hip -o $OUT/obj_$NAME/api.o &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/libmonortm_hip_$NAME.so $OUT/obj_$NAME/lines_ms_kernel.o $OUT/obj_$NAME/api.o \
-    $OBJ/lines_kernel.o $OBJ/far_kernel.o $OBJ/continuum_kernel.o $OBJ/xsec_kernel.o $OBJ/rtm_kernel.o $OBJ/rtm_scan_kernel.o $OBJ/jacobian_kernel.o $OBJ/rtm_scan_jac_kernel.o $OBJ/rtm_obs_jac_kernel.o $OBJ/line_table.o
+# every other object of the shipped build, whatever _build.py's HIP_SOURCES lists by now
+REST=$(ls $OBJ/*.o | grep -v -e /lines_ms_kernel.o -e /api.o)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/libmonortm_hip_$NAME.so $OUT/obj_$NAME/lines_ms_kernel.o $OUT/obj_$NAME/api.o $REST
 ls -la $OUT/libmonortm_hip_$NAME.so

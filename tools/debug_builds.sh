@@ -12,6 +12,12 @@ cd "$(dirname "$0")/../monortm_amd/csrc"
 OUT=../../build_dbg
 mkdir -p $OUT
 SRC="api.hip lines_kernel.hip lines_ms_kernel.hip far_kernel.hip continuum_kernel.hip xsec_kernel.hip rtm_kernel.hip rtm_scan_kernel.hip jacobian_kernel.hip rtm_scan_jac_kernel.hip rtm_obs_jac_kernel.hip line_table.cpp"
+# ... and every object of the shipped build (../lib/obj/, built by __graft_entry__.build()) whose source is not recompiled here
+for o in ../lib/obj/*.o; do
+    [ -e "$o" ] || { echo "no objects in monortm_amd/lib/obj: run __graft_entry__.build() first"; exit 1; }
+    b=$(basename $o .o)
+    case " $SRC " in *" $b.hip "*|*" $b.cpp "*) ;; *) SRC="$SRC $o" ;; esac
+done
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-value -Wno-pass-failed -Wno-unused-const-variable -DMONORTM_EXPERIMENT=1"
 /opt/rocm/bin/hipcc $FLAGS -DLINES_TIMING -o $OUT/libmonortm_hip_ltiming.so $SRC
 /opt/rocm/bin/hipcc $FLAGS -DLINES_CLASS_STATS -o $OUT/libmonortm_hip_classes.so $SRC
