@@ -117,7 +117,7 @@ __global__ __launch_bounds__(64 * G) void rtm_jac_kernel(RtmJacArgs a) {
     const double ex_s = exp(VV * (K_RADCN2 / tmpsfc)), ex_c = exp(VV * (K_RADCN2 / TSKY));
     const double SURFRAD = c3 / (ex_s - 1.), COSMOS = c3 / (ex_c - 1.);
     const double ESFC = (double)rp<R>(a.emiss)[o], RSFC = (double)rp<R>(a.reflc)[o];
-    if (!valid) return;   // (no barrier below; leaving here and not behind the stores keeps <double, 8, false> at 96 VGPRs, 5 waves per SIMD)
+    if (!valid) return;   // (no barrier below; leaving here and not behind the stores saves registers: DESIGN.md section 3.6)
     // RAD through its irt forms, dq/dRAD, the weights of pass 2 and the surface terms (rtm_tile.hpp)
     double RAD, lx, dq, gU, gD, gT;
     jac_path_weights(irt, TRTOT, RUP, RDN, ESFC, RSFC, SURFRAD, COSMOS, c3, VV, a.quantity, RAD, lx, dq, gU, gD, gT);
@@ -140,7 +140,21 @@ __global__ __launch_bounds__(64 * G) void rtm_jac_kernel(RtmJacArgs a) {
     R *KC = FULL ? wp<R>(a.K_CLW) + pw + iw : nullptr;
     if (l1 > l0) {
         double ODTd = ODTOT - above, ODTu = above;
-        double upIncl = upLow + RUPg;   // sum of up_l, l <= current layer
+        // the sum of up_l, l <= the group's top layer, from pass 2's own terms, error-free (jac_up_sum, rtm_tile.hpp)
+        double upIncl = 0., upLo = 0.;
+        if (up) {
+            double ODTu2 = above, B2, dB2, Bzu2, dBzu2;
+            planck_d(c3, VV, sBz[l1], &Bzu2, &dBzu2);
+            for (int k = l1 - 1; k >= l0; k--) {
+                planck_d(c3, VV, sBl[k], &B2, &dB2);
+                jac_up_sum((double)O[(size_t)k * nwn], B2, Bzu2, up, ODTu2, upIncl, upLo);
+                planck_d(c3, VV, sBz[k], &Bzu2, &dBzu2);
+            }
+            double s2, e2;
+            two_sum(upIncl, upLow, s2, e2);
+            upIncl = s2;
+            upLo = upLo + e2;
+        }
         double dnAbove = dnHigh;        // sum of dn_l, l > current layer
         // B and dB/dT at the upper level of the group's top layer, and the downward sweep's term of level l1 from the layer
         // above (its lower level); level nlay (top of the atmosphere) is the lower level of no layer
@@ -154,7 +168,7 @@ __global__ __launch_bounds__(64 * G) void rtm_jac_kernel(RtmJacArgs a) {
             planck_d(c3, VV, sBl[k], &B, &dB);
             planck_d(c3, VV, sBz[k], &Bzl, &dBzl);
             double ko, kt, ktz;
-            jac_layer_terms(tau, B, dB, Bzl, dBzl, Bzu, dBzu, up, gU, gD, gT, ODTd, ODTu, upIncl, dnAbove, dn_lev, ko, kt, ktz);   // (rtm_tile.hpp)
+            jac_layer_terms(tau, B, dB, Bzl, dBzl, Bzu, dBzu, up, gU, gD, gT, ODTd, ODTu, upIncl, upLo, dnAbove, dn_lev, ko, kt, ktz);   // (rtm_tile.hpp)
             KTZ[(size_t)(k + 1) * nwn] = (R)ktz;
             Bzu = Bzl;
             dBzu = dBzl;

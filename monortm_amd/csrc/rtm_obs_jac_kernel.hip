@@ -108,14 +108,14 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
             const double SURFRAD = c3 / (ex_s - 1.), COSMOS = c3 / (ex_c - 1.);
             // totals in the reference's visiting order (every group needs them) and the sums of the other groups, one path at a time;
             // then q, K_SFC and the weights of the path
-            double gU[NP], gD[NP], gT[NP], upIncl0[NP], dnHigh0[NP];
+            double gU[NP], gD[NP], gT[NP], upLow0[NP], dnHigh0[NP];
             double sq[4] = {0., 0., 0., 0.};   // sums over the tile's paths of wpath x (q, dq/dTMPSFC, dq/dEMISS, dq/dREFLC)
 #pragma unroll
             for (int j = 0; j < NP; j++) {
                 gU[j] = 0.;
                 gD[j] = 0.;
                 gT[j] = 0.;
-                upIncl0[j] = 0.;
+                upLow0[j] = 0.;
                 dnHigh0[j] = 0.;
                 if (j < npl) {
                     sUp[g][lane] = RUPg[j];
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
 #pragma unroll
                         for (int i = 0; i < 3; i++) sq[1 + i] = fma(wj, ksfc[i], sq[1 + i]);
                     }
-                    upIncl0[j] = upLow + RUPg[j];   // sum of up_l, l <= the group's top layer
+                    upLow0[j] = upLow;              // sum of up_l, l < the group's bottom layer
                     dnHigh0[j] = dnHigh;            // sum of dn_l, l > the group's top layer
                 }
             }
@@ -160,9 +160,39 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
                 for (int j = 0; j < NP; j++) {
                     ODTd[j] = ODTOT[j] - above[j];
                     ODTu[j] = above[j];
-                    upIncl[j] = upIncl0[j];
+                    upIncl[j] = 0.;
                     dnAbove[j] = dnHigh0[j];
                     dn_lev[j] = 0.;
+                }
+                // the sums of up_l, l <= the group's top layer, from pass 2's own terms, error-free (jac_up_sum, rtm_tile.hpp)
+                double upLo[NP];
+                {
+                    double ODTu2[NP];
+#pragma unroll
+                    for (int j = 0; j < NP; j++) {
+                        ODTu2[j] = above[j];
+                        upIncl[j] = 0.;
+                        upLo[j] = 0.;
+                    }
+                    if (up) {
+                        double B2, dB2, Bzu2, dBzu2;
+                        planck_d(c3, VV, sBz[l1], &Bzu2, &dBzu2);
+                        for (int k = l1 - 1; k >= l0; k--) {
+                            const double o2 = (double)O[(size_t)k * nwn];
+                            planck_d(c3, VV, sBl[k], &B2, &dB2);
+#pragma unroll
+                            for (int j = 0; j < NP; j++)
+                                if (j < npl) jac_up_sum(__dmul_rn(o2, sF[j * lm + k]), B2, Bzu2, up, ODTu2[j], upIncl[j], upLo[j]);
+                            planck_d(c3, VV, sBz[k], &Bzu2, &dBzu2);
+                        }
+#pragma unroll
+                        for (int j = 0; j < NP; j++) {
+                            double s2, e2;
+                            two_sum(upIncl[j], upLow0[j], s2, e2);
+                            upIncl[j] = s2;
+                            upLo[j] = upLo[j] + e2;
+                        }
+                    }
                 }
                 // B and dB/dT at the upper level of the group's top layer, and the downward sweep's term of level l1 from the layer above
                 // (its lower level); level nlay (top of the atmosphere) is the lower level of no layer
@@ -194,7 +224,7 @@ __global__ __launch_bounds__(64 * G) void rtm_obs_jac_kernel(RtmObsJacArgs a) {
                         if (j < npl) {
                             const double f = sF[j * lm + k];
                             double ko, kt, ktz;
-                            jac_layer_terms(__dmul_rn(o, f), B, dB, Bzl, dBzl, Bzu, dBzu, up, gU[j], gD[j], gT[j], ODTd[j], ODTu[j], upIncl[j],
+                            jac_layer_terms(__dmul_rn(o, f), B, dB, Bzl, dBzl, Bzu, dBzu, up, gU[j], gD[j], gT[j], ODTd[j], ODTu[j], upIncl[j], upLo[j],
                                             dnAbove[j], dn_lev[j], ko, kt, ktz);   // (rtm_tile.hpp)
                             const double wj = sW[j];
                             sk[1] = fma(wj, ktz, sk[1]);

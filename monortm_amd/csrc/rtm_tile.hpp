@@ -113,6 +113,45 @@ __device__ __forceinline__ double add_rounded(double a, double b) {
     return a + b;
 }
 
+// s + e = a + b exactly (Knuth): the sum as rounded and what the rounding dropped
+__device__ __forceinline__ void two_sum(double a, double b, double &s, double &e) {
+#pragma clang fp contract(off)
+    s = a + b;
+    const double bv = s - a;
+    e = (a - (s - bv)) + (b - bv);
+}
+
+// What pass 2 needs of one (layer, path) for the upward sweep: t = exp(-tau), the Pade weight and 1 / (1 + pade), emis = 1 - t, TRu =
+// exp(-ODTu) (ODTu: the optical depth above the layer), bup = B + pade Bzu and the layer's upward term upk.  ONE definition with
+// contraction off: jac_up_sum and jac_layer_terms must form upk to the same bit (see jac_up_sum).
+__device__ __forceinline__ void jac_up_parts(double tau, double B, double Bzu, bool up, double ODTu, double &t, double &pade, double &rp1,
+                                             double &emis, double &TRu, double &bup, double &upk) {
+#pragma clang fp contract(off)
+    t = exp_cw(-tau);
+    pade = 0.193 * tau + 0.013 * (tau * tau);
+    rp1 = rcp2(1. + pade);
+    emis = 1. - t;
+    TRu = up ? exp_cw(-ODTu) : 0.;
+    bup = B + pade * Bzu;
+    upk = up ? ((TRu * emis) * bup) * rp1 : 0.;
+}
+
+// Pass 2 walks a group's layers top-down and needs, per layer, the sum of the upward terms of the layers BELOW it.  Held as a running
+// difference from the rounded group sum of pass 1, that sum keeps ~10 eps x RUP where the truth is e^-tau of nothing (at and under an
+// opaque layer) - invisible in dq/dtau on the column's scale, but K_PATH = O x dq/dtau multiplies it by the opaque layer's O (1e6
+// against a column whose other layers have O = 1e-5: 2.4e-5 of the column's largest K_PATH; LABNOTES section 23).  So the group's sum
+// is formed once more from pass 2's OWN terms, error-free (H + L = the exact sum of the rounded terms up to eps^2), and
+// jac_layer_terms takes the same terms off again, error-free: what is left under an opaque layer is eps^2 x RUP.
+// One layer's step of that sum, layers top-down as in pass 2 (ODTu advances as there).
+__device__ __forceinline__ void jac_up_sum(double tau, double B, double Bzu, bool up, double &ODTu, double &H, double &L) {
+    double t, pade, rp1, emis, TRu, bup, upk, s, e;
+    jac_up_parts(tau, B, Bzu, up, ODTu, t, pade, rp1, emis, TRu, bup, upk);
+    ODTu = add_rounded(ODTu, tau);
+    two_sum(H, upk, s, e);
+    H = s;
+    L = L + e;
+}
+
 // One path's epilogue of pass 1: RAD through the irt forms (RTMmono.f90:138-147, as rtm_combine rounds it), lx = log(c3 / RAD + 1) (TB =
 // RADCN2 v / lx), dq = dq/dRAD and the weights gU = dq/dRUP, gD = dq/dRDN, gT = TRTOT dq/dTRTOT of pass 2.  Pure arithmetic of one
 // thread, as is jac_path_sfc below: no barrier, no store.
@@ -144,13 +183,15 @@ __device__ __forceinline__ void jac_path_weights(int irt, double TRTOT, double R
     gT = dq * cT * TRTOT;
 }
 // ... and its surface terms dq/dTMPSFC, dq/dEMISS, dq/dREFLC (0 unless irt = 1), for the threads that store or contract them.  ex_s =
-// exp(hc v / k tmpsfc), the exponential SURFRAD was formed with.
+// exp(hc v / k tmpsfc), the exponential SURFRAD was formed with; where it overflows, dq/dTMPSFC is 0.
 __device__ __forceinline__ void jac_path_sfc(int irt, double dq, double TRTOT, double RDN, double ESFC, double SURFRAD, double COSMOS,
                                              double VV, double ex_s, double tmpsfc, double (&ksfc)[3]) {
     ksfc[0] = ksfc[1] = ksfc[2] = 0.;
     if (irt == 1) {
         const double xs = VV * (K_RADCN2 / tmpsfc);
-        const double dBs = SURFRAD * (ex_s / (ex_s - 1.)) * (xs / tmpsfc);
+        // ex_s = inf (hc v / k tmpsfc > 709.78: a cold surface in the ultraviolet): SURFRAD = 0 and inf / inf is NaN where dB/dT has
+        // underflowed to 0, as in planck_d
+        const double dBs = (ex_s == __builtin_inf()) ? 0. : SURFRAD * (ex_s / (ex_s - 1.)) * (xs / tmpsfc);
         ksfc[0] = dq * TRTOT * ESFC * dBs;
         ksfc[1] = dq * TRTOT * SURFRAD;
         ksfc[2] = dq * TRTOT * (RDN + TRTOT * COSMOS);
@@ -160,30 +201,38 @@ __device__ __forceinline__ void jac_path_sfc(int irt, double dq, double TRTOT, d
 // The downward sweep's term of level l1 from the layer ABOVE a group's top layer (its lower level), which pass 2 starts from where
 // l1 < nlay: tau of that layer, ODTd = the optical depth up to and including the group's top layer, dBzu = dB/dT at level l1.
 __device__ __forceinline__ double jac_dn_lev_above(double tau, double gD, double ODTd, double dBzu) {
+#pragma clang fp contract(off)
     const double pade = 0.193 * tau + 0.013 * (tau * tau);
     return gD * exp_cw(-ODTd) * (1. - exp_cw(-tau)) * pade * rcp2(1. + pade) * dBzu;
 }
 
 // Pass 2 for one (layer k, path), layers taken top-down: tau the layer's optical depth along the path (rounded once), B / dB, Bzl /
 // dBzl, Bzu / dBzu the Planck function and dB/dT of the layer, its lower and its upper level.  Advances the running optical depths
-// (ODTd, ODTu), the sums of the other layers' terms (upIncl -> sum_{l<k} up_l, dnAbove -> sum_{l>=k} dn_l) and dn_lev (in: the
+// (ODTd, ODTu), the sums of the other layers' terms (upIncl + upLo -> sum_{l<k} up_l, error-free: in, the lower groups' sum plus
+// jac_up_sum's H and L over the group's layers down to this one; dnAbove -> sum_{l>=k} dn_l) and dn_lev (in: the
 // downward term of level k + 1 from the layer above, out: of level k from this layer).  Out: ko = dq/dtau_k, kt = the Planck term of
 // dq/dT_k, ktz = dq/dTZ_{k+1}.  Pure arithmetic of one thread: no barrier, no store.
 __device__ __forceinline__ void jac_layer_terms(double tau, double B, double dB, double Bzl, double dBzl, double Bzu, double dBzu, bool up,
                                                 double gU, double gD, double gT, double &ODTd, double &ODTu, double &upIncl,
-                                                double &dnAbove, double &dn_lev, double &ko, double &kt, double &ktz) {
-    const double t = exp_cw(-tau);
-    const double pade = 0.193 * tau + 0.013 * (tau * tau), pp = 0.193 + 0.026 * tau;
-    const double rp1 = rcp2(1. + pade), emis = 1. - t;
+                                                double &upLo, double &dnAbove, double &dn_lev, double &ko, double &kt, double &ktz) {
+    // every product and sum rounded as written: which of them the compiler would fuse depends on the code around the call, and the
+    // instantiations of one kernel (a profile alone: G = 2; inside a batch: G = 8 working with two groups) must agree to the bit
+#pragma clang fp contract(off)
+    double t, pade, rp1, emis, TRu, bup, upk, s, e;
+    jac_up_parts(tau, B, Bzu, up, ODTu, t, pade, rp1, emis, TRu, bup, upk);
+    const double pp = 0.193 + 0.026 * tau;
     ODTd = ODTd - tau;
-    const double TRd = exp_cw(-ODTd), TRu = up ? exp_cw(-ODTu) : 0.;
+    const double TRd = exp_cw(-ODTd);
     ODTu = add_rounded(ODTu, tau);
-    const double bdn = B + pade * Bzl, bup = B + pade * Bzu;
-    const double dn = ((TRd * emis) * bdn) * rp1, upk = up ? ((TRu * emis) * bup) * rp1 : 0.;
-    upIncl = upIncl - upk;   // now sum_{l<k} up_l
+    const double bdn = B + pade * Bzl;
+    const double dn = ((TRd * emis) * bdn) * rp1;
+    two_sum(upIncl, -upk, s, e);   // the very upk jac_up_sum added
+    upIncl = s;
+    upLo = upLo + e;
+    const double upBelow = upIncl + upLo;   // sum_{l<k} up_l
     const double dfdn = t * bdn * rp1 + emis * pp * (Bzl - B) * (rp1 * rp1);
     const double dfup = t * bup * rp1 + emis * pp * (Bzu - B) * (rp1 * rp1);
-    const double dRUP = TRu * dfup - upIncl, dRDN = TRd * dfdn - dnAbove;
+    const double dRUP = TRu * dfup - upBelow, dRDN = TRd * dfdn - dnAbove;
     dnAbove = dnAbove + dn;
     ko = gU * dRUP + gD * dRDN - gT;
     kt = (gU * TRu + gD * TRd) * emis * rp1 * dB;

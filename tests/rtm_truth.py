@@ -1,5 +1,6 @@
 """An extended-precision restatement of CALCTMR + RAD_UP_DN + RTM (reference src/RTMmono.f90:13-325), the input classes that stress
-the way the radiance kernels regroup that loop, and the error measure of tests/test_rtm_truth_cpu.py and tests/test_rtm_extremes.py.
+the way the radiance kernels regroup that loop, its derivatives in closed form (truth_adjoint), and the error measures of
+tests/test_rtm_truth_cpu.py, tests/test_rtm_extremes.py and tests/test_adjoint_extremes.py.
 
 A helper module like tests/common.py (no fixtures, no test).  Nothing here runs on a GPU or imports the product.
 
@@ -179,6 +180,13 @@ def cycled_classes(nprof: int, shift: int = 0):
     return [CLASSES[(p // 3 + shift) % len(CLASSES)] for p in range(nprof)]
 
 
+def make_batch(name: str, cls: str) -> Batch:
+    """The seeded batch BATCHES[name] of one class (or "cycled") that the tests against the truth share."""
+    seed = 7000 + 100 * list(BATCHES).index(name) + (CLASSES.index(cls) if cls != "cycled" else 50)
+    nlay = BATCHES[name]
+    return Batch(nlay, cycled_classes(len(nlay)) if cls == "cycled" else cls, seed)
+
+
 # ---- the error measure -----------------------------------------------------------------------------------------------------------
 def E(a, t, orc, real_kind: int = 8, denormal_slack: bool = False) -> float:
     """max |a - t| / |t| over the elements where t is finite and representable; inf when an element breaks one of the rules:
@@ -259,6 +267,71 @@ def truth_derivatives(b: Batch, a: dict, quantities=("rad", "tb")):
         em = np.asarray(a["em"], LD)
         rad["k_sfc"] = np.where(one, np.stack([t0["trtot"] * em * t0["dsurfrad"], t0["trtot"] * t0["surfrad"],
                                                t0["trtot"] * (t0["rdn"] + t0["trtot"] * t0["cosmos"])], axis=1), LD(0))
+        res = {}
+        for q in quantities:
+            dq = dtb[:, None, :] if q == "tb" else LD(1)
+            res[q] = {k: np.where(v_ != 0, dq * v_, LD(0)) for k, v_ in rad.items()}
+            res[q]["q"] = t0[q]
+    return res
+
+
+def truth_adjoint(wn, nlay, irt, T, TZ, O, tmpsfc, emiss, reflc, quantities=("rad", "tb")):
+    """The derivatives of the truth's RAD and TB in closed form, from the sums of truth() itself, in the dict layout of
+    truth_derivatives: {quantity: k_o, k_t [nprof, lm, nwn], k_tz [nprof, lm + 1, nwn], k_sfc [nprof, 3, nwn], q [nprof, nwn]}, longdouble.
+    With t = exp(-tau), e = -expm1(-tau), p = 0.193 tau + 0.013 tau^2 and f(tau; Bz) = e (B + p Bz) / (1 + p), a layer's term of a sweep:
+      RDN = sum_l exp(-below_l) f_l(Bz_l),  RUP = sum_l exp(-above_l) f_l(Bz_{l+1}),  TRTOT = exp(-sum tau), below / above direct sums;
+      df/dtau = t (B + p Bz) / (1 + p) + e (0.193 + 0.026 tau) (Bz - B) / (1 + p)^2;
+      dRDN/dtau_k = exp(-below_k) df_k/dtau - sum_{l>k} dn_l (tau_k lies below every higher layer), dRUP/dtau_k likewise with l < k;
+      dB/dT = B x / T / -expm1(-x), x = hc v / kT, which no exponential overflows; level j is the lower level of layer j (RDN) and the
+      upper level of layer j - 1 (RUP);
+      RAD's three irt forms (RTMmono.f90:138-147) give dRAD/dRUP, dRAD/dRDN, dRAD/dTRTOT; TB's derivatives are RAD's times dtb_drad.
+    Padded layers and levels are exactly 0; what lies beyond nlay[p] is never read.  tests/test_rtm_truth_cpu.py holds it to the
+    independent differences of truth_derivatives."""
+    nlay, irt = np.asarray(nlay), np.asarray(irt)
+    t0 = truth(wn, nlay, irt, T, TZ, O, tmpsfc, emiss, reflc)
+    O, T, TZ = np.asarray(O, LD), np.asarray(T, LD), np.asarray(TZ, LD)
+    nprof, lm, nwn = O.shape
+    lay = np.arange(lm)[None, :] < nlay[:, None]
+    lev = np.arange(lm + 1)[None, :] <= nlay[:, None]
+    O = np.where(lay[:, :, None], O, LD(0))
+    T, TZ = np.where(lay, T, LD(250))[:, :, None], np.where(lev, TZ, LD(250))[:, :, None]
+    v = np.asarray(wn, LD)[None, None, :]
+    c3 = RADCN1 * (v * v * v)
+    with np.errstate(all="ignore"):
+        xl, xz = v * (RADCN2 / T), v * (RADCN2 / TZ)
+        bb, bz = _planck(c3, v, T), _planck(c3, v, TZ)
+        dbb, dbz = bb * (xl / T) / -np.expm1(-xl), bz * (xz / TZ) / -np.expm1(-xz)
+        zero = np.zeros((nprof, 1, nwn), LD)
+        below = np.concatenate([zero, np.cumsum(O, axis=1)[:, :-1]], axis=1)
+        above = np.concatenate([np.cumsum(O[:, ::-1], axis=1)[:, ::-1][:, 1:], zero], axis=1)
+        tdn, tup = np.exp(-below), np.exp(-above)
+        t, e = np.exp(-O), -np.expm1(-O)
+        p, dp = LD(0.193) * O + LD(0.013) * (O * O), LD(0.193) + LD(0.026) * O
+        r = 1 / (1 + p)
+        bzl, bzu = bz[:, :-1], bz[:, 1:]
+        dn, up = tdn * e * (bb + p * bzl) * r, tup * e * (bb + p * bzu) * r
+        dfdn = t * (bb + p * bzl) * r + e * dp * (bzl - bb) * (r * r)
+        dfup = t * (bb + p * bzu) * r + e * dp * (bzu - bb) * (r * r)
+        dn_above = np.concatenate([np.cumsum(dn[:, ::-1], axis=1)[:, ::-1][:, 1:], zero], axis=1)   # sum of dn_l, l > k
+        up_below = np.concatenate([zero, np.cumsum(up, axis=1)[:, :-1]], axis=1)                     # sum of up_l, l < k
+        drdn, drup = tdn * dfdn - dn_above, tup * dfup - up_below
+        i = irt[:, None]
+        tr, rdn, cosmos, surfrad = t0["trtot"], t0["rdn"], t0["cosmos"], t0["surfrad"]
+        em, rf = np.asarray(emiss, LD), np.asarray(reflc, LD)
+        cu = np.where(i == 3, LD(0), LD(1))
+        cd = np.where(i == 1, tr * rf, np.where(i == 2, tr, LD(1)))
+        ct = np.where(i == 1, em * surfrad + rf * rdn + 2 * rf * tr * cosmos, np.where(i == 2, rdn + 2 * tr * cosmos, cosmos))
+        cu, cd, ct_tr = cu[:, None, :], cd[:, None, :], (ct * tr)[:, None, :]
+        wz = e * p * r
+        k_tz = np.zeros((nprof, lm + 1, nwn), LD)
+        k_tz[:, :-1] += cd * tdn * wz * dbz[:, :-1]
+        k_tz[:, 1:] += cu * tup * wz * dbz[:, 1:]
+        one = (irt == 1)[:, None, None]
+        rad = dict(k_o=np.where(lay[:, :, None], cu * drup + cd * drdn - ct_tr, LD(0)),
+                   k_t=np.where(lay[:, :, None], (cu * tup + cd * tdn) * e * r * dbb, LD(0)),
+                   k_tz=np.where(lev[:, :, None], k_tz, LD(0)),
+                   k_sfc=np.where(one, np.stack([tr * em * t0["dsurfrad"], tr * surfrad, tr * (rdn + tr * cosmos)], axis=1), LD(0)))
+        dtb = dtb_drad(t0["rad"], t0["c3"], v[0])
         res = {}
         for q in quantities:
             dq = dtb[:, None, :] if q == "tb" else LD(1)

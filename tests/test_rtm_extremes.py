@@ -13,6 +13,8 @@ same inputs in the same test):
 Every call is made twice, the padding beyond nlay[p] once zero and once NaN: the results must be identical.
 
 Launch instantiations (real_kind R): A64, L200 -> <R, 16>; B30, D48 -> <R, 8>; C12 -> <R, 2>; the Jacobians <double, 8> and <double, 2>.
+tests/test_adjoint_extremes.py holds the adjoints (rtm_jac_kernel in both real kinds and on A64, rtm_scan_jac_kernel, rtm_obs_jac_kernel)
+and rtm_obs_kernel to the same truth and its closed-form adjoint, with this module's batches, classes and raw_* helpers.
 Run with -s for every figure; MONORTM_TRUTH_RECORD names a file that collects the worst of each."""
 import ctypes as C
 
@@ -88,10 +90,7 @@ def same(x, y):
     return all(np.array_equal(x[k], y[k], equal_nan=True) for k in x)
 
 
-def make_batch(name, cls):
-    seed = 7000 + 100 * list(tr.BATCHES).index(name) + (tr.CLASSES.index(cls) if cls != "cycled" else 50)
-    nlay = tr.BATCHES[name]
-    return tr.Batch(nlay, tr.cycled_classes(len(nlay)) if cls == "cycled" else cls, seed)
+make_batch = tr.make_batch
 
 
 def check_against_truth(what, kind, b, got, truth, orc):

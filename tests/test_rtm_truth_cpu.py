@@ -3,7 +3,8 @@ reference loop, in double) against the extended-precision truth of tests/rtm_tru
 
 E_orc = E(oracle, truth) is the REFERENCE's own error on a class.  It must be small (<= 1e-7, a tenth of the project's 1e-6 criterion)
 wherever the GPU tests hold the kernels to the oracle at 1e-6; only `thinnest` and `degenerate` may lie outside - there the reference's
-1 - exp(-tau) cancels (tau = 1e-12 keeps 4 digits).  Run with -s for the table."""
+1 - exp(-tau) cancels (tau = 1e-12 keeps 4 digits).  And what tests/test_adjoint_extremes.py leans on: the truth's closed-form adjoint
+(truth_adjoint) against Richardson differences of the truth.  Run with -s for the tables."""
 import numpy as np
 import pytest
 
@@ -110,3 +111,41 @@ def test_closed_form_dtb_drad_matches_differences_of_tb():
             got = rt.dtb_drad(rad, c3, v)
             err = np.abs(got - want)[ok] / np.abs(want)[ok]
         assert ok.sum() > 0.3 * ok.size and err.max() <= 1e-10, (cls, float(err.max()))
+
+
+# ---- the analytic adjoint of the truth ---------------------------------------------------------------------------------------------
+# The worst k_error of truth_adjoint against truth_derivatives over k_o, k_t, k_tz, RAD and TB, B30 and C12, measured on the CPU
+# (LABNOTES section 23 has the table by field).  What is measured is the DIFFERENCES' error: 1e-10 is their truncation
+# (x / T)^5 h^4 on k_t / k_tz, 1e-9 the rounding eps RAD / h of k_o where an opaque layer leaves a column's largest dRAD/dtau at
+# 1e-3 RAD.  The two functions share truth() and dtb_drad and nothing else.
+ADJOINT_MEASURED = {"lognormal": 1.1e-10, "thin": 1.6e-10, "thinnest": 1.2e-10, "opaque_bottom": 1.3e-9, "opaque_top": 1.5e-9,
+                    "opaque_middle": 6.9e-11, "mixed": 1.6e-9, "underflow": 8.0e-10, "degenerate": 9.6e-11}
+
+
+@pytest.mark.parametrize("cls", rt.CLASSES)
+@pytest.mark.parametrize("name", ["B30", "C12"])
+def test_truth_adjoint_against_truth_differences(name, cls):
+    """truth_adjoint (closed form) against truth_derivatives (Richardson-extrapolated central differences of truth()), by k_error.
+    Bound outside CANCELLING: 10 x the class's measured worst, and never looser than 1e-8 - two decades inside the 1e-6 the kernels
+    are held to; `thinnest` and `degenerate` are printed and recorded.  K_SFC: the two share the closed form, so equal.  Padded
+    layers and levels are exactly 0 and NaN beyond nlay[p] changes no bit."""
+    b = rt.make_batch(name, cls)
+    a = b.rounded(np.float64, 0.0)
+    ref, got = rt.truth_derivatives(b, a), rt.truth_adjoint(*b.args(a))
+    got_n = rt.truth_adjoint(*b.args(b.rounded(np.float64, np.nan)))
+    bound = min(10 * ADJOINT_MEASURED[cls], 1e-8)
+    fails = []
+    for q in ("rad", "tb"):
+        for k in ("k_o", "k_t", "k_tz", "k_sfc", "q"):
+            assert got[q][k].dtype == np.longdouble and np.array_equal(got[q][k], got_n[q][k]), f"{q} {k}: padding beyond nlay[p] is read"
+        for k in ("k_o", "k_t", "k_tz"):
+            assert np.all(got[q][k][~(b.lev if k == "k_tz" else b.lay)] == 0), f"{q} {k}: padding is not zero"
+            e = rt.k_error(got[q][k], ref[q][k], ref[q]["q"])
+            print(f"truth_adjoint {name} {cls:14s} {q:3s} {k:4s} {e:.1e}")
+            rt.record(f"truth_adjoint/{k}/{cls}/{q}", e)
+            if cls not in rt.CANCELLING and not e <= bound:
+                fails.append(f"{q} {k} {e:.2e} > {bound:.1e}")
+        assert np.array_equal(got[q]["k_sfc"], ref[q]["k_sfc"]) and np.all(got[q]["k_sfc"][b.irt != 1] == 0)
+        assert np.array_equal(got[q]["q"], ref[q]["q"])
+    rt.dump_record()
+    assert not fails, f"{name} {cls}: " + ", ".join(fails)
