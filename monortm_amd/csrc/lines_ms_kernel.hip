@@ -23,12 +23,13 @@
 #include "lines_device.hpp"
 #include "lines_ms_asm.hpp"
 #include "modm_plan.hpp"
+#include "ms_reach.hpp"
 
 namespace {
 using namespace monortm_dev;
 
 constexpr int WPS = MS_WPS;   // wavenumbers per lane
-constexpr double MS_REACH_RHO = 2.0;   // densest state (RHORAT = density over that at 1013.25 hPa, 296 K) the slot masks allow for
+static_assert(MS_REACH_SLOTS == MS_WPS, "ms_reach.hpp forms one bit per wavenumber of a lane");
 
 __device__ __forceinline__ void ms_sync() {  // one wave: order the compiler, the LDS unit keeps program order
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -613,18 +614,9 @@ __global__ void ms_reach_kernel(const double *wn, int nwn, int LPS, DevLines L, 
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nlines) return;
     const uint32_t meta = L.meta[idx];
-    const double x = L.vnu[idx], pad = L.max_abs_shift * MS_REACH_RHO + 1e-6;
+    const double x = L.vnu[idx], pad = ms_reach_pad(L.max_abs_shift);
     const bool every = ((meta & 63u) == 7u && ((meta >> 10) & 3u)) || !(x == x);
-    unsigned r = 0u;
-    for (int k = 0; k < WPS; k++) {
-        const int c0 = LPS * k;
-        if (c0 >= nwn) break;
-        const double wlo = wn[c0], whi = wn[min(c0 + LPS, nwn) - 1];
-        if (every || (!(x - pad - 25. > whi) && !(wlo - 25. > x + pad))) r |= 1u << k;
-        // bits 8 .. 12: the NEGATIVE resonance reaches the slot (WN + Xnu <= 25 for its lowest channel, modm.f90:713 / :757)
-        if (every || !(wlo + (x - pad) > 25.)) r |= 256u << k;
-    }
-    reach[idx] = (unsigned short)r;
+    reach[idx] = (unsigned short)ms_reach_word(wn, nwn, LPS, x, every, pad);   // (ms_reach.hpp: the two slot tests)
     // ... and the distance of the table centre to the nearest channel, rounded down: line_records' Voigt test (some channel within
     // 100 Doppler widths of the SHIFTED centre, modm.f90:427) cannot pass where this distance less the shift exceeds the limit
     // (triangle inequality), so that the search over the channels is left to the few lines near a channel.  0 (= search) for a NaN centre.

@@ -121,7 +121,8 @@ def test_c4_full_batch_on_one_gpu(workdir):
     line is the most general over the states of its wave, four lines share a reciprocal), the last shard of 128 profiles on its
     own takes lines_kernel: the two agree to the rounding of the regrouped sums (1e-12 of a cell's optical depth); with
     lines_kernel forced for both (one state per wave: a profile's arithmetic does not depend on its neighbours) the shard
-    reproduces its slice of the big batch bit for bit.  Two profiles are checked against the oracle."""
+    reproduces its slice of the big batch bit for bit.  Seven profiles of the big batch itself and two single-profile batches are
+    checked against the oracle."""
     from oracle.pyoracle import Oracle
 
     rec = synth.synthetic_lines(500)
@@ -142,6 +143,16 @@ def test_c4_full_batch_on_one_gpu(workdir):
     assert tb.shape == (1024, 50) and np.all(np.isfinite(tb)) and tb.min() > 2.7 and tb.max() < 320.0
     big_o, big_obm, big_rad = b.O[896:].cpu().numpy(), b.OBM[896:].cpu().numpy(), b.RAD[896:].cpu().numpy()
     orc = Oracle(t3, wn[0], wn[-1])
+    # the big batch itself against the oracle (only these rows are fetched): the first and the last group of six, the round
+    # boundary of lines_ms_kernel's waves at profile 384 and the short last group (1020 .. 1023)
+    from monortm_amd.caseio import Dump
+
+    row = lambda x, i: x[i].cpu().numpy()  # noqa: E731
+    for i in (0, 5, 6, 383, 384, 1019, 1023):
+        n = profs[i].nlay
+        got = Dump(row(b.O, i)[:n], row(b.OBM, i)[:n], row(b.OC, i)[:n], row(b.OCLW, i)[:n], row(b.RUP, i), row(b.RDN, i), row(b.TRTOT, i), row(b.RAD, i),
+                   row(b.TB, i), row(b.TMR, i), float(b.tmpsfc[i]))
+        compare(got, orc.run(profs[i]), rtol=RTOL, what=f"c4 big batch profile {i}")
     for i in (0, 1023):
         one = api.DeviceBatch(rt, [profs[i]])
         one.step()

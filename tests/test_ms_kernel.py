@@ -188,6 +188,13 @@ def test_ms_is_chosen_by_rounds_of_waves(workdir, gpu):
         for k in ("wn", "ms", "auto"):
             rt = _rt(t3, wn, k)
             d = rt.run(profs[:n])
+            if n == 512 and k == "auto":   # the split launch against the oracle: both ends of each part
+                from oracle.pyoracle import Oracle
+
+                orc = Oracle(t3, wn[0], wn[-1])
+                for i in (0, 383, 384, 511):
+                    compare(d[i], orc.run(profs[i]), rtol=RTOL, what=f"split launch of 512 profiles, profile {i}")
+                orc.close()
             res[k] = (np.stack([x.o_by_mol for x in d]), np.stack([x.o for x in d]), np.stack([x.tb for x in d]))
             rt.close()
         assert not np.array_equal(res["ms"][0], res["wn"][0])
