@@ -243,7 +243,8 @@ int monortm_hip_rtm_scan_dev(void *ctx, int nprof, int npath, int nwn, const dou
  *                                    through MODM (lines, continuum, cloud);  monortm_hip_rtm_jac: the Planck term only
  *   K_TZ  [nprof][nlay_max + 1][nwn] dq/dTZ_j, level temperature (RTM only, analytic; TZ_0 enters only RDN of layer 1, TZ_nlay only
  *                                    RUP: 0 for irt = 3)
- *   K_W   [nprof][nlay_max][njac][nwn] dq/d ln WKL_k,jac_mol[i] = WKL dq/dWKL (0 where WKL = 0)
+ *   K_W   [nprof][nlay_max][njac][nwn] dq/d ln WKL_k,jac_mol[i] = WKL dq/dWKL (0 where WKL = 0); for the other Jacobian variables
+ *                                    (MONORTM_JVAR_*, below): what their table says
  *   K_CLW [nprof][nlay_max][nwn]     dq/dCLW_k; the cloud optical depth is linear in CLW (ODCLW_TKC, src/CloudOptProp.f90:18-20,49),
  *                                    dO_k/dCLW_k = ODCLW_TKC(wn, T_k, 1) in closed form (right at CLW = 0 too)
  *   K_O   [nprof][nlay_max][nwn]     dq/dO_k, the optical-depth Jacobian (to chain cross sections or species outside jac_mol)
@@ -259,6 +260,21 @@ int monortm_hip_rtm_scan_dev(void *ctx, int nprof, int npath, int nwn, const dou
  * across a switch reports the switch.  T +- h must stay within 70-3000 K (MONORTM_ETEMP otherwise).
  * Cross-section molecules (IXSECT = 1) are not part of monortm_hip_jacobian: chain K_O with their dO.
  *
+ * Jacobian variables: an entry of jac_mol[] is a 1-based molecule (1..nmol) or one of the codes below, in any
+ * mix; slot i of K_W belongs to jac_mol[i].  eps is the "jac_dlnw" half-step for every one of them.
+ *   per layer   MONORTM_JVAR_P, _WBROD: P_k, WBRODL_k x (1 +- eps); the slot holds dq/d ln P_k, dq/d ln WBRODL_k (0 where WBRODL = 0),
+ *               T, WKL and every other input fixed
+ *   scalar      MONORTM_JVAR_CNTNM0 + i (cntnm_fac[i], i = 0..6: XSELF, XFRGN, XCO2C, XO3CN, XO2CN, XN2CN, XRAYL), _SCLCPL, _SCLHW,
+ *               _Y0RES: the argument +- eps (additive); slot [k] holds the part of dq/dtheta that acts through layer k, and the SUM
+ *               of the slots over the layers is dq/dtheta.  MODM switches a continuum off at a factor <= 0, so where fac - eps <= 0
+ *               the difference is one-sided, (O(fac + 2 eps) - O(fac)) / (2 eps): exact as well, O being linear in the factor. */
+#define MONORTM_JVAR_P 1001
+#define MONORTM_JVAR_WBROD 1002
+#define MONORTM_JVAR_CNTNM0 1011 /* + i, i = 0..6 */
+#define MONORTM_JVAR_SCLCPL 1021
+#define MONORTM_JVAR_SCLHW 1022
+#define MONORTM_JVAR_Y0RES 1023
+/*
  * RTM adjoint only, given O (e.g. from monortm_hip_modm): RAD, TB, K_O, K_T (Planck terms only), K_TZ, K_SFC.  real_kind 8 and 4
  * (double arithmetic either way).  Host buffers; a multi-device context shards the profiles like monortm_hip_rtm. */
 int monortm_hip_rtm_jac(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
@@ -274,8 +290,8 @@ int monortm_hip_rtm_jac_dev(void *ctx, int nprof, int nwn, const double *wn, con
                             monortm_real *K_SFC, void *stream);
 
 /* MODM + RTM with Jacobians: the forward outputs of the base state (O, RAD, TB) and K_T (total), K_TZ, K_W, K_CLW, K_O (may be
- * NULL), K_SFC.  jac_mol[njac]: HOST array of 1-based molecules (<= nmol, no duplicates; njac = 0: no K_W, which may then be NULL)
- * in both variants.  real_kind 8 only (MONORTM_EUNSUPPORTED otherwise).  Host buffers: shards like monortm_hip_modm.
+ * NULL), K_SFC.  jac_mol[njac]: HOST array of 1-based molecules (<= nmol) and MONORTM_JVAR_* codes (no duplicates, njac <= 39;
+ * njac = 0: no K_W, which may then be NULL) in both variants.  real_kind 8 only (MONORTM_EUNSUPPORTED otherwise).  Host buffers: shards like monortm_hip_modm.
  * Errors: MONORTM_EARG for a NULL required array, a bad quantity, a bad jac_mol; MONORTM_ETEMP when T +- h leaves 70-3000 K. */
 int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
                          int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,

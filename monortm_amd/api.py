@@ -113,6 +113,25 @@ _LIB = None
 # "jac_dlnw" changes them per context)
 JAC_DT = 1e-2
 JAC_DLNW = 1e-4
+# Jacobian variables besides the 1-based molecules (MONORTM_JVAR_* of include/monortm_hip.h): ln P and
+# ln WBRODL per layer, and the scalar arguments of MODM - the seven continuum factors, SCLCPL, SCLHW, Y0RES
+JAC_VARS = {"p": 1001, "wbrod": 1002, "xself": 1011, "xfrgn": 1012, "xco2c": 1013, "xo3cn": 1014, "xo2cn": 1015, "xn2cn": 1016,
+            "xrayl": 1017, "sclcpl": 1021, "sclhw": 1022, "y0res": 1023}
+
+
+def jac_codes(seq) -> np.ndarray:
+    """The `mols=` argument of the Jacobian calls as the int32 codes of the C ABI: ints (1-based molecules, or codes) pass through,
+    names are looked up in JAC_VARS (case-insensitive); an unknown name raises ValueError."""
+    out = []
+    for v in ([seq] if isinstance(seq, (str, int, np.integer)) else seq):
+        if isinstance(v, str):
+            if v.lower() not in JAC_VARS:
+                raise ValueError(f"unknown Jacobian variable {v!r}: a 1-based molecule or one of {sorted(JAC_VARS)}")
+            v = JAC_VARS[v.lower()]
+        out.append(int(v))
+    return np.ascontiguousarray(np.array(out, np.int32).reshape(-1))
+
+
 JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_sfc")
 SCAN_JAC_RTM_FIELDS = ("rad", "tb", "k_o", "k_path", "k_t", "k_tz", "k_sfc")                 # output order of monortm_hip_rtm_scan_jac
 SCAN_JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_path", "k_sfc")   # ... of monortm_hip_scan_jacobian
@@ -561,7 +580,10 @@ class MonoRTM:
     def jacobian(self, profiles: list[Profile], mols=(1,), quantity="tb") -> dict:
         """MODM + RTM with Jacobians for a batch (real_kind 8): dict of o [nprof, nlay_max, nwn], rad, tb [nprof, nwn], k_t, k_clw, k_o
         [nprof, nlay_max, nwn], k_tz [nprof, nlay_max + 1, nwn], k_w [nprof, nlay_max, len(mols), nwn] (d/d ln WKL of mols, 1-based)
-        and k_sfc [nprof, 3, nwn].  Partial derivatives with respect to the MODM / RTM inputs (see include/monortm_hip.h)."""
+        and k_sfc [nprof, 3, nwn].  Partial derivatives with respect to the MODM / RTM inputs (see include/monortm_hip.h).
+        mols may mix molecules with the names (or codes) of JAC_VARS: "p", "wbrod" (d/d ln P_k, d/d ln WBRODL_k) and the scalars
+        "xself" .. "xrayl", "sclcpl", "sclhw", "y0res", whose k_w slot summed over the layers is dq/dtheta (DESIGN.md section 3.11);
+        vars holds the codes in slot order.  The same holds for scan_jacobian, obs_jacobian and the DeviceBatch calls."""
         p0 = profiles[0]
         nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
         nmol, dt = p0.nmol, self.dtype
@@ -574,7 +596,7 @@ class MonoRTM:
 
         P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
         WKL = pack(lambda p: p.wkl, nmol)
-        jm = np.ascontiguousarray(np.asarray(mols, np.int32).reshape(-1))
+        jm = jac_codes(mols)
         nj = len(jm)
         out = dict(o=np.zeros((nprof, lm, nwn), dt), rad=np.zeros((nprof, nwn), dt), tb=np.zeros((nprof, nwn), dt),
                    k_t=np.zeros((nprof, lm, nwn), dt), k_tz=np.zeros((nprof, lm + 1, nwn), dt), k_w=np.zeros((nprof, lm, nj, nwn), dt),
@@ -584,6 +606,7 @@ class MonoRTM:
                                                 _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, _ptr(irt), _ptr(TZ),
                                                 _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj, _ptr(jm) if nj else None,
                                                 *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS]))
+        out["vars"] = jm
         return out
 
     # ---- Jacobians of path scans (monortm_hip_rtm_scan_jac / monortm_hip_scan_jacobian) ----------------------
@@ -635,7 +658,7 @@ class MonoRTM:
 
         P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
         WKL = pack(lambda p: p.wkl, nmol)
-        jm = np.ascontiguousarray(np.asarray(mols, np.int32).reshape(-1))
+        jm = jac_codes(mols)
         nj = len(jm)
         z = lambda *s: np.zeros((nprof, npath) + s, dt)  # noqa: E731
         out = dict(o=np.zeros((nprof, lm, nwn), dt), rad=z(nwn), tb=z(nwn), k_t=z(lm, nwn), k_tz=z(lm + 1, nwn), k_w=z(lm, nj, nwn),
@@ -646,6 +669,7 @@ class MonoRTM:
                                                      _ptr(irt), _ptr(TZ), _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj,
                                                      _ptr(jm) if nj else None, npath, _ptr(f), int(em.ndim == 3),
                                                      *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS]))
+        out["vars"] = jm
         return out
 
     # ---- channel- and beam-averaged Jacobians (monortm_hip_obs_create / _rtm_obs_jac / _obs_jacobian) ------------
@@ -708,7 +732,7 @@ class MonoRTM:
 
         P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
         WKL = pack(lambda p: p.wkl, nmol)
-        jm = np.ascontiguousarray(np.asarray(mols, np.int32).reshape(-1))
+        jm = jac_codes(mols)
         nj = len(jm)
         nv, nc = self._obs_shape(obs)
         z = lambda *s: np.zeros((nprof, nv) + s + (nc,), dt)  # noqa: E731
@@ -719,6 +743,7 @@ class MonoRTM:
                                                     _ptr(irt), _ptr(TZ), _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj,
                                                     _ptr(jm) if nj else None, npath, _ptr(f), int(em.ndim == 3), int(obs),
                                                     *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS]))
+        out["vars"] = jm
         return out
 
     # ---- the forward measurement operator (monortm_hip_rtm_obs / monortm_hip_obs) ------------------------------
@@ -911,7 +936,7 @@ class DeviceBatch:
         shapes of MonoRTM.jacobian, allocated at the first call for (mols, quantity) and overwritten by every later one (so that a
         graph capture of the call replays into the same tensors).  TMPSFC is the profiles' own (input only)."""
         t = self.torch
-        key = (tuple(int(m) for m in mols), _quantity(quantity))
+        key = (tuple(int(m) for m in jac_codes(mols)), _quantity(quantity))
         cache = self.__dict__.setdefault("_jac", {})
         if key not in cache:
             f64 = t.float32 if self.rt.real_kind == 4 else t.float64
@@ -929,6 +954,7 @@ class DeviceBatch:
                                              p0.ibrd, d(self.irt), d(self.TZ), d(self.tmpsfc0), d(self.emiss), d(self.reflc), key[1], nj,
                                              _ptr(jm) if nj else None, *[d(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS],
                                              _ptr(self.wn_ends), _vp(s.cuda_stream)))
+        out["vars"] = t.from_numpy(jm.copy())   # (a host tensor: the codes in slot order)
         return out
 
     # ---- path scans on the resident batch (monortm_hip_modm_dev + monortm_hip_rtm_scan_dev) ---------------------------------------
@@ -983,7 +1009,7 @@ class DeviceBatch:
         if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
             raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
         npath = int(f.shape[1])
-        key = (npath, tuple(int(m) for m in mols), _quantity(quantity))
+        key = (npath, tuple(int(m) for m in jac_codes(mols)), _quantity(quantity))
         cache = self.__dict__.setdefault("_scan_jac", {})
         if key not in cache:
             n, lm, nw, nj = self.nprof, self.lm, self.nwn, len(key[1])
@@ -1004,6 +1030,7 @@ class DeviceBatch:
                                                   d(self.reflc), key[2], nj, _ptr(jm) if nj else None, npath, d(fd), 0,
                                                   *[d(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS],
                                                   _ptr(self.wn_ends), _vp(s.cuda_stream)))
+        out["vars"] = t.from_numpy(jm.copy())   # (a host tensor: the codes in slot order)
         return out
 
     # ---- channel- and beam-averaged Jacobians on the resident batch (monortm_hip_obs_jacobian_dev) --------------------------------------
@@ -1022,7 +1049,7 @@ class DeviceBatch:
         if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
             raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
         npath = int(f.shape[1])
-        key = (int(obs), npath, tuple(int(m) for m in mols), _quantity(quantity))
+        key = (int(obs), npath, tuple(int(m) for m in jac_codes(mols)), _quantity(quantity))
         cache = self.__dict__.setdefault("_obs_jac", {})
         live = self.rt.__dict__.get("_obs", {})
         for k in [k for k in cache if k[0] not in live]:   # operators destroyed since: handles are never reused, let their tensors go
@@ -1047,6 +1074,7 @@ class DeviceBatch:
                                                  d(self.reflc), key[3], nj, _ptr(jm) if nj else None, npath, d(fd), 0, int(obs),
                                                  *[d(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS],
                                                  _ptr(self.wn_ends), _vp(s.cuda_stream)))
+        out["vars"] = t.from_numpy(jm.copy())   # (a host tensor: the codes in slot order)
         return out
 
     # ---- the forward measurement operator on the resident batch (monortm_hip_modm_dev + monortm_hip_rtm_obs_dev) ------------------------

@@ -492,12 +492,20 @@ int jac_check_args(Ctx *c, int nprof, int nwn, const int *nlay, int nlay_max, in
         if (nlay[p] < 1 || nlay[p] > nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
     return MONORTM_OK;
 }
+// Jacobian variables: the scalar arguments of MODM among the MONORTM_JVAR_* codes, and the per-layer ones
+bool jac_var_scalar(int v) {
+    return (v >= MONORTM_JVAR_CNTNM0 && v < MONORTM_JVAR_CNTNM0 + 7) || v == MONORTM_JVAR_SCLCPL || v == MONORTM_JVAR_SCLHW || v == MONORTM_JVAR_Y0RES;
+}
+bool jac_var_layer(int v, int nmol) { return (v >= 1 && v <= nmol) || v == MONORTM_JVAR_P || v == MONORTM_JVAR_WBROD; }
 int jac_check_mol(Ctx *c, int nmol, int njac, const int *jac_mol, const void *K_W) {
-    if (njac < 0 || njac > nmol || (njac > 0 && (!jac_mol || !K_W))) { c->err = "njac outside 0..nmol, or jac_mol / K_W missing"; return MONORTM_EARG; }
+    if (njac < 0 || njac > MXMOL || (njac > 0 && (!jac_mol || !K_W))) { c->err = "njac outside 0..39, or jac_mol / K_W missing"; return MONORTM_EARG; }
     for (int i = 0; i < njac; i++) {
-        if (jac_mol[i] < 1 || jac_mol[i] > nmol) { c->err = "jac_mol[" + std::to_string(i) + "] outside 1..nmol"; return MONORTM_EARG; }
+        if (!jac_var_layer(jac_mol[i], nmol) && !jac_var_scalar(jac_mol[i])) {
+            c->err = "jac_mol[" + std::to_string(i) + "] neither a molecule 1..nmol nor a MONORTM_JVAR_* code";
+            return MONORTM_EARG;
+        }
         for (int j = 0; j < i; j++)
-            if (jac_mol[j] == jac_mol[i]) { c->err = "jac_mol lists molecule " + std::to_string(jac_mol[i]) + " twice"; return MONORTM_EARG; }
+            if (jac_mol[j] == jac_mol[i]) { c->err = "jac_mol lists variable " + std::to_string(jac_mol[i]) + " twice"; return MONORTM_EARG; }
     }
     return MONORTM_OK;
 }
@@ -536,13 +544,19 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
         HIPCHK(c, hipMemcpyAsync(&vends[1], wn + nwn - 1, sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
     }
-    const int nstate = 3 + 2 * njac;
+    // Per-layer variables (molecules, P, WBRODL) are states of the perturbed arrays, in slot order; the two states of a scalar variable
+    // are MODM launches of the caller's own arrays with that argument changed.  State k of O, k = 3 + 2i / 4 + 2i
+    // for jac_mol[i] of either kind; the perturbed arrays hold the nps states of the base, T +- h and the per-layer variables only.
+    int lvar[MXMOL], nlv = 0;
+    for (int i = 0; i < njac; i++)
+        if (!jac_var_scalar(jac_mol[i])) lvar[nlv++] = jac_mol[i];
+    const int nstate = 3 + 2 * njac, nps = 3 + 2 * nlv;
     const size_t npl = (size_t)nprof * nlay_max, st = npl * nwn;
-    const bool ext = (long long)nstate * nprof <= 64 && (size_t)nstate * npl * c->host.size() * 48 <= (64u << 20);
-    const size_t nj = ext ? nstate : 1;   // states whose unused MODM outputs are held at once
+    const bool ext = (long long)nps * nprof <= 64 && (size_t)nps * npl * c->host.size() * 48 <= (64u << 20);
+    const size_t nj = ext ? nps : 1;   // states whose unused MODM outputs are held at once
     Arena ws;
-    const size_t w_P = ws.add(nstate * npl * 8), w_T = ws.add(nstate * npl * 8), w_C = ws.add(nstate * npl * 8), w_B = ws.add(nstate * npl * 8),
-                 w_W = ws.add(nstate * npl * nmol * 8), w_nl = ws.add(nstate * (size_t)nprof * sizeof(int)), w_O = ws.add(nstate * st * 8),
+    const size_t w_P = ws.add(nps * npl * 8), w_T = ws.add(nps * npl * 8), w_C = ws.add(nps * npl * 8), w_B = ws.add(nps * npl * 8),
+                 w_W = ws.add(nps * npl * nmol * 8), w_nl = ws.add(nps * (size_t)nprof * sizeof(int)), w_O = ws.add(nstate * st * 8),
                  w_OM = ws.add(nj * st * nmol * 8), w_OC = ws.add(nj * st * MONORTM_NCONT * 8), w_OL = ws.add(nj * st * 8);
     if (ws.size > c->jac_ws_bytes) {
         if (c->jac_ws) HIPCHK(c, hipFree(c->jac_ws));
@@ -556,32 +570,70 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
     *xO_out = xO;
     *st_out = st;
     JacPerturbArgs pa{};
-    pa.nstate = nstate; pa.nprof = nprof; pa.nlay_max = nlay_max; pa.nmol = nmol; pa.dt = c->opt.jac_dt; pa.dlnw = c->opt.jac_dlnw;
-    for (int i = 0; i < njac; i++) pa.jac_mol[i] = jac_mol[i];
+    pa.nstate = nps; pa.nprof = nprof; pa.nlay_max = nlay_max; pa.nmol = nmol; pa.dt = c->opt.jac_dt; pa.dlnw = c->opt.jac_dlnw;
+    for (int i = 0; i < nlv; i++) pa.jac_mol[i] = lvar[i];
     pa.P = static_cast<const double *>(P); pa.T = static_cast<const double *>(T); pa.CLW = static_cast<const double *>(CLW);
     pa.WKL = static_cast<const double *>(WKL); pa.WBRODL = static_cast<const double *>(WBRODL); pa.nlay = nlay;
     pa.xP = reinterpret_cast<double *>(wb + w_P); pa.xT = reinterpret_cast<double *>(wb + w_T); pa.xCLW = reinterpret_cast<double *>(wb + w_C);
     pa.xWBRODL = reinterpret_cast<double *>(wb + w_B); pa.xWKL = reinterpret_cast<double *>(wb + w_W); pa.xnlay = reinterpret_cast<int *>(wb + w_nl);
     launch_jac_perturb(pa, s);
     HIPCHK(c, hipGetLastError());
-    auto modm = [&](int n, int s0, void *Oout, int slot) {   // MODM of n profiles of the state arrays from state s0 on
+    auto modm = [&](int n, int s0, void *Oout) {   // MODM of n profiles of the perturbed arrays from their state s0 on
         const size_t l0 = (size_t)s0 * npl;
         return monortm_hip_modm_xs_dev(c, n, nwn, wn, dvset, pa.xnlay + (size_t)s0 * nprof, nlay_max, nmol, pa.xP + l0, pa.xT + l0, pa.xCLW + l0,
                                        pa.xWKL + l0 * nmol, pa.xWBRODL + l0, cntnm_fac, sclcpl, sclhw, y0res, ibrd, 0, nullptr, nullptr, Oout,
-                                       wb + w_OM + slot * st * nmol * 8, wb + w_OC + slot * st * MONORTM_NCONT * 8, wb + w_OL + slot * st * 8,
-                                       vends, s);
+                                       wb + w_OM, wb + w_OC, wb + w_OL, vends, s);
     };
-    if (ext) {
-        if (int rc = modm(nstate * nprof, 0, xO, 0)) return rc;
-        HIPCHK(c, hipMemcpyAsync(O, xO, st * 8, hipMemcpyDeviceToDevice, s));
-    } else {
+    // state k of O for a scalar variable: the caller's arrays, the argument at +eps (odd k) / -eps.  MODM switches a continuum off at a
+    // factor <= 0, so where fac - eps <= 0 the pair is fac + 2 eps / fac: one-sided over the same 2 eps, exact for a linear factor
+    auto modm_scalar = [&](int k, void *Oout) -> int {
+        const int v = jac_mol[(k - 3) >> 1];
+        const bool plus = !((k - 3) & 1);
+        const double e = c->opt.jac_dlnw;
+        double fac[7], sc[3] = {sclcpl, sclhw, y0res};
+        for (int i = 0; i < 7; i++) fac[i] = cntnm_fac[i];
+        if (v >= MONORTM_JVAR_CNTNM0 && v < MONORTM_JVAR_CNTNM0 + 7) {
+            double &f = fac[v - MONORTM_JVAR_CNTNM0];
+            if (f - e <= 0.) f += plus ? 2. * e : 0.;
+            else f += plus ? e : -e;
+        } else
+            sc[v - MONORTM_JVAR_SCLCPL] += plus ? e : -e;
+        if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, fac, sc[0], sc[1], sc[2], ibrd, 0,
+                                             nullptr, nullptr, Oout, wb + w_OM, wb + w_OC, wb + w_OL, vends, s))
+            return rc;
+        // A continuum factor reaches O through ONE addend, its molecule's slot of OC (O = lines + sum of OC + cloud, continuum_kernel.hip),
+        // and the adjoints read a state only in the difference O+ - O-.  The state therefore holds that slot instead of the total: a
+        // continuum of 1e-12 of O (CO2 in the microwave) would vanish in the total's rounding, its slot keeps 16 digits of its own.
+        // (XRAYL has no slot: Rayleigh goes into O directly.)
+        static const int oc_slot[7] = {0, 0, 1, 2, 3, 4, -1};   // XSELF, XFRGN: H2O; XCO2C; XO3CN; XO2CN; XN2CN: slots of molecules 1, 2, 3, 7, 22
+        const int slot = (v >= MONORTM_JVAR_CNTNM0 && v < MONORTM_JVAR_CNTNM0 + 7) ? oc_slot[v - MONORTM_JVAR_CNTNM0] : -1;
+        if (slot >= 0)
+            HIPCHK(c, hipMemcpy2DAsync(Oout, (size_t)nwn * 8, wb + w_OC + (size_t)slot * nwn * 8, (size_t)MONORTM_NCONT * nwn * 8, (size_t)nwn * 8,
+                                       npl, hipMemcpyDeviceToDevice, s));
+        return MONORTM_OK;
+    };
+    auto scalar_state = [&](int k) { return k >= 3 && jac_var_scalar(jac_mol[(k - 3) >> 1]); };
+    int k = 0, ps = 0;   // the next state of O, and of the perturbed arrays
+    if (!ext) {
         // the base state straight from the caller's arrays, into the caller's O: what monortm_hip_modm_dev returns for them
         if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw,
                                              y0res, ibrd, 0, nullptr, nullptr, O, wb + w_OM, wb + w_OC, wb + w_OL, vends, s))
             return rc;
-        for (int k = 1; k < nstate; k++)
-            if (int rc = modm(nprof, k, xO + k * st, 0)) return rc;
+        k = ps = 1;
     }
+    while (k < nstate) {
+        if (scalar_state(k)) {
+            if (int rc = modm_scalar(k, xO + k * st)) return rc;
+            k++;
+            continue;
+        }
+        int n = 1;   // ext: the run of per-layer states up to the next scalar variable in ONE launch (all of them when none is named)
+        while (ext && k + n < nstate && !scalar_state(k + n)) n++;
+        if (int rc = modm(n * nprof, ps, xO + k * st)) return rc;
+        k += n;
+        ps += n;
+    }
+    if (ext) HIPCHK(c, hipMemcpyAsync(O, xO, st * 8, hipMemcpyDeviceToDevice, s));
     return MONORTM_OK;
 }
 

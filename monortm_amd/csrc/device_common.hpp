@@ -279,7 +279,7 @@ struct RtmObsArgs {
 struct JacPerturbArgs {
     int nstate, nprof, nlay_max, nmol;
     double dt, dlnw;
-    int jac_mol[MXMOL];   // 1-based
+    int jac_mol[MXMOL];   // what states 3 + 2i / 4 + 2i scale: a 1-based molecule's WKL, or MONORTM_JVAR_P / _WBROD
     const double *P, *T, *CLW, *WKL, *WBRODL;
     const int *nlay;
     double *xP, *xT, *xCLW, *xWKL, *xWBRODL;

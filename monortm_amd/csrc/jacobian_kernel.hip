@@ -1,5 +1,6 @@
 // jacobian_kernel.hip - Jacobians of RAD / TB (monortm_hip_rtm_jac, monortm_hip_jacobian) for gfx950.  See DESIGN.md section 3.6.
-//   jac_perturb_kernel: the base and the +-h states of a Jacobian call as MODM inputs (T +- h; WKL of one molecule x (1 +- eps))
+//   jac_perturb_kernel: the base and the +-h states of a Jacobian call as MODM inputs (T +- h; WKL of one molecule, P or WBRODL
+//                       x (1 +- eps))
 //   rtm_jac_kernel:     the exact adjoint of RAD_UP_DN + RTM (reference src/RTMmono.f90:13-221), chained with the central
 //                       differences of the perturbed states' optical depths (FULL)
 #include "cloud_tkc.hpp"
@@ -10,7 +11,8 @@ using namespace monortm_dev;
 
 // ------------------------------------------------------------------------------------------------
 // jac_perturb_kernel: one thread per (state, profile, layer).  State 0 = the base, 1 / 2 = T + h / T - h, 3 + 2i / 4 + 2i =
-// WKL(jac_mol[i]) x (1 + eps) / (1 - eps).  Layers >= nlay[p] are copied unchanged (the caller's padding).
+// WKL(jac_mol[i]) x (1 + eps) / (1 - eps), or P / WBRODL x (1 +- eps) where jac_mol[i] is MONORTM_JVAR_P / _WBROD (DESIGN.md
+// section 3.11).  Layers >= nlay[p] are copied unchanged (the caller's padding).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void jac_perturb_kernel(JacPerturbArgs a) {
     const size_t npl = (size_t)a.nprof * a.nlay_max;
@@ -24,8 +26,11 @@ __global__ __launch_bounds__(256) void jac_perturb_kernel(JacPerturbArgs a) {
     double *dst_l[4] = {a.xP, a.xT, a.xCLW, a.xWBRODL};
     for (int f = 0; f < 4; f++) dst_l[f][(size_t)s * npl + pl] = src_l[f][pl];
     if (in && (s == 1 || s == 2)) a.xT[(size_t)s * npl + pl] = a.T[pl] + (s == 1 ? a.dt : -a.dt);
-    const int mol = (s >= 3) ? a.jac_mol[(s - 3) >> 1] - 1 : -1;   // 0-based molecule scaled in this state
+    const int var = (s >= 3) ? a.jac_mol[(s - 3) >> 1] : 0;   // what this state scales: a 1-based molecule, or P / WBRODL
+    const int mol = var - 1;                                  // (0-based; matches no molecule for the base, T, P and WBRODL states)
     const double fac = ((s - 3) & 1) ? 1. - a.dlnw : 1. + a.dlnw;
+    if (in && var == MONORTM_JVAR_P) a.xP[(size_t)s * npl + pl] = a.P[pl] * fac;
+    if (in && var == MONORTM_JVAR_WBROD) a.xWBRODL[(size_t)s * npl + pl] = a.WBRODL[pl] * fac;
     const double *w = a.WKL + pl * a.nmol;
     double *xw = a.xWKL + ((size_t)s * npl + pl) * a.nmol;
     for (int m = 0; m < a.nmol; m++) xw[m] = (in && m == mol) ? w[m] * fac : w[m];

@@ -1,9 +1,11 @@
 """Time of a Jacobian call against a plain step, on the configs[3] shape (1024 profiles x 64 layers x 50 channels x 500 lines, f64)
 and on a single profile of the same shape (LABNOTES).
 
-    python tools/jacobian_bench.py [--calls 30] [--warmup 5] [--out FILE]
+    python tools/jacobian_bench.py [--calls 30] [--warmup 5] [--out FILE] [--vars "1;1,p,wbrod;1,xself,xfrgn,sclcpl"]
 
-K = T + H2O (jac_mol = 1) + cloud + surface, q = TB.  Per case: device-event times of DeviceBatch.jacobian and of DeviceBatch.step,
+K = T + H2O (jac_mol = 1) + cloud + surface, q = TB; --vars: the Jacobian variables instead of H2O alone - lists separated by ";",
+each a comma-separated mix of molecules and names of api.JAC_VARS, one result per case and list.
+Per case: device-event times of DeviceBatch.jacobian and of DeviceBatch.step,
 one of each in turn (interleaved, after warm-up), median / min / max / IQR of each, the ratio of the medians, and the number of
 forward runs that brute-force differences (one layer at a time) would need for the same K.  Prints one JSON line."""
 from __future__ import annotations
@@ -56,7 +58,8 @@ def run_case(api, rt, profs, mols, calls, warmup):
     k = db.jacobian(mols=mols)
     torch.cuda.synchronize()
     finite = bool(all(torch.isfinite(v).all().item() for v in k.values()))
-    return dict(nprof=db.nprof, nlay=nlay, nwn=db.nwn, jac_mol=list(mols), jacobian_ms=j, step_ms=s, ratio=j["median"] / s["median"],
+    return dict(nprof=db.nprof, nlay=nlay, nwn=db.nwn, jac_mol=list(mols), modm_evaluations=3 + 2 * nj, jacobian_ms=j, step_ms=s,
+                ratio=j["median"] / s["median"],
                 # one base run + central differences of every layer's T, ln WKL of each molecule and CLW (surface: + 6)
                 brute_force_runs=1 + 2 * nlay * (1 + nj + 1) + 6, brute_force_runs_t_h2o=1 + 2 * nlay * (1 + nj), finite=finite)
 
@@ -67,6 +70,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--cases", default="whole,single")
+    ap.add_argument("--vars", default="1")
     args = ap.parse_args()
     import torch
 
@@ -74,6 +78,8 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("jacobian_bench needs the GPU (no CPU fallback)")
+    var_lists = [tuple(int(v) if v.strip().isdigit() else v.strip() for v in lst.split(",") if v.strip())
+                 for lst in args.vars.split(";")]
     wn = synth.c2_channels(50)
     res = dict(what="Jacobian (T + H2O + cloud + surface, TB) vs plain step, device events", cases={})
     with tempfile.TemporaryDirectory() as d:
@@ -83,7 +89,9 @@ def main():
         for name in args.cases.split(","):
             n = 1024 if name == "whole" else 1
             profs = [synth.perturbed_profile(i, wn, nlay=64, cloud=True, irt=(1 if i % 2 == 0 else 3)) for i in range(n)]
-            res["cases"][name] = run_case(api, rt, profs, (1,), args.calls, args.warmup)
+            for lst in var_lists:
+                key = name if len(var_lists) == 1 else f"{name}[{','.join(str(v) for v in lst)}]"
+                res["cases"][key] = run_case(api, rt, profs, lst, args.calls, args.warmup)
         rt.close()
     line = json.dumps(res)
     print(line)
