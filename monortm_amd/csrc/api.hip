@@ -547,16 +547,22 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
     // Per-layer variables (molecules, P, WBRODL) are states of the perturbed arrays, in slot order; the two states of a scalar variable
     // are MODM launches of the caller's own arrays with that argument changed.  State k of O, k = 3 + 2i / 4 + 2i
     // for jac_mol[i] of either kind; the perturbed arrays hold the nps states of the base, T +- h and the per-layer variables only.
+    // XRAYL is the exception among the scalars: its states are launches on ONE more state of the perturbed arrays, which holds the
+    // inputs of the Rayleigh term alone (modm_scalar below).  npa: the states of the arrays; without XRAYL npa = nps, and every size
+    // and launch is what it was.
     int lvar[MXMOL], nlv = 0;
-    for (int i = 0; i < njac; i++)
+    bool rayl = false;
+    for (int i = 0; i < njac; i++) {
         if (!jac_var_scalar(jac_mol[i])) lvar[nlv++] = jac_mol[i];
-    const int nstate = 3 + 2 * njac, nps = 3 + 2 * nlv;
+        rayl = rayl || jac_mol[i] == MONORTM_JVAR_CNTNM0 + 6;
+    }
+    const int nstate = 3 + 2 * njac, nps = 3 + 2 * nlv, npa = nps + (rayl ? 1 : 0);
     const size_t npl = (size_t)nprof * nlay_max, st = npl * nwn;
     const bool ext = (long long)nps * nprof <= 64 && (size_t)nps * npl * c->host.size() * 48 <= (64u << 20);
     const size_t nj = ext ? nps : 1;   // states whose unused MODM outputs are held at once
     Arena ws;
-    const size_t w_P = ws.add(nps * npl * 8), w_T = ws.add(nps * npl * 8), w_C = ws.add(nps * npl * 8), w_B = ws.add(nps * npl * 8),
-                 w_W = ws.add(nps * npl * nmol * 8), w_nl = ws.add(nps * (size_t)nprof * sizeof(int)), w_O = ws.add(nstate * st * 8),
+    const size_t w_P = ws.add(npa * npl * 8), w_T = ws.add(npa * npl * 8), w_C = ws.add(npa * npl * 8), w_B = ws.add(npa * npl * 8),
+                 w_W = ws.add(npa * npl * nmol * 8), w_nl = ws.add(npa * (size_t)nprof * sizeof(int)), w_O = ws.add(nstate * st * 8),
                  w_OM = ws.add(nj * st * nmol * 8), w_OC = ws.add(nj * st * MONORTM_NCONT * 8), w_OL = ws.add(nj * st * 8);
     if (ws.size > c->jac_ws_bytes) {
         if (c->jac_ws) HIPCHK(c, hipFree(c->jac_ws));
@@ -570,7 +576,7 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
     *xO_out = xO;
     *st_out = st;
     JacPerturbArgs pa{};
-    pa.nstate = nps; pa.nprof = nprof; pa.nlay_max = nlay_max; pa.nmol = nmol; pa.dt = c->opt.jac_dt; pa.dlnw = c->opt.jac_dlnw;
+    pa.nstate = npa; pa.rayl_state = rayl ? nps : 0; pa.nprof = nprof; pa.nlay_max = nlay_max; pa.nmol = nmol; pa.dt = c->opt.jac_dt; pa.dlnw = c->opt.jac_dlnw;
     for (int i = 0; i < nlv; i++) pa.jac_mol[i] = lvar[i];
     pa.P = static_cast<const double *>(P); pa.T = static_cast<const double *>(T); pa.CLW = static_cast<const double *>(CLW);
     pa.WKL = static_cast<const double *>(WKL); pa.WBRODL = static_cast<const double *>(WBRODL); pa.nlay = nlay;
@@ -591,6 +597,22 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
         const bool plus = !((k - 3) & 1);
         const double e = c->opt.jac_dlnw;
         double fac[7], sc[3] = {sclcpl, sclhw, y0res};
+        if (v == MONORTM_JVAR_CNTNM0 + 6) {
+            // XRAYL.  Rayleigh has no slot of OC - it is added into O directly - and is 1e-11 .. 1e-10 of O in the infrared: +-eps of it
+            // in the total is quantisation (what XCO2C was below 30 cm-1).  Its states hold the term itself instead: MODM on the
+            // state of the perturbed arrays that leaves nothing but Rayleigh (WKL = 0: no line, no other continuum; CLW = 0; WBRODL
+            // = WTOT, all the term reads besides T), the other six factors 0, XRAYL = 2 eps against XRAYL = 0 - and at 0 MODM
+            // switches the term off, so that state IS zero and is cleared, not launched.  O+ - O- = 2 eps dO/dXRAYL on the term's
+            // own scale, exact at any XRAYL >= 0 (O is linear in it; at 0 the derivative from the positive side); below 820 cm-1
+            // both states are exactly 0.
+            if (!plus) { HIPCHK(c, hipMemsetAsync(Oout, 0, st * 8, s)); return MONORTM_OK; }
+            for (int i = 0; i < 7; i++) fac[i] = 0.;
+            fac[6] = 2. * e;
+            const size_t l0 = (size_t)nps * npl;
+            return monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, pa.xP + l0, pa.xT + l0, pa.xCLW + l0, pa.xWKL + l0 * nmol,
+                                           pa.xWBRODL + l0, fac, sclcpl, sclhw, y0res, ibrd, 0, nullptr, nullptr, Oout, wb + w_OM, wb + w_OC,
+                                           wb + w_OL, vends, s);
+        }
         for (int i = 0; i < 7; i++) fac[i] = cntnm_fac[i];
         if (v >= MONORTM_JVAR_CNTNM0 && v < MONORTM_JVAR_CNTNM0 + 7) {
             double &f = fac[v - MONORTM_JVAR_CNTNM0];
@@ -604,7 +626,7 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
         // A continuum factor reaches O through ONE addend, its molecule's slot of OC (O = lines + sum of OC + cloud, continuum_kernel.hip),
         // and the adjoints read a state only in the difference O+ - O-.  The state therefore holds that slot instead of the total: a
         // continuum of 1e-12 of O (CO2 in the microwave) would vanish in the total's rounding, its slot keeps 16 digits of its own.
-        // (XRAYL has no slot: Rayleigh goes into O directly.)
+        // (XRAYL: above.)
         static const int oc_slot[7] = {0, 0, 1, 2, 3, 4, -1};   // XSELF, XFRGN: H2O; XCO2C; XO3CN; XO2CN; XN2CN: slots of molecules 1, 2, 3, 7, 22
         const int slot = (v >= MONORTM_JVAR_CNTNM0 && v < MONORTM_JVAR_CNTNM0 + 7) ? oc_slot[v - MONORTM_JVAR_CNTNM0] : -1;
         if (slot >= 0)

@@ -280,6 +280,7 @@ struct JacPerturbArgs {
     int nstate, nprof, nlay_max, nmol;
     double dt, dlnw;
     int jac_mol[MXMOL];   // what states 3 + 2i / 4 + 2i scale: a 1-based molecule's WKL, or MONORTM_JVAR_P / _WBROD
+    int rayl_state;       // the state (the last one) that holds the inputs of Rayleigh alone - WKL = 0, WBRODL = WTOT, CLW = 0 -, or 0: none
     const double *P, *T, *CLW, *WKL, *WBRODL;
     const int *nlay;
     double *xP, *xT, *xCLW, *xWKL, *xWBRODL;

@@ -13,6 +13,8 @@ using namespace monortm_dev;
 // jac_perturb_kernel: one thread per (state, profile, layer).  State 0 = the base, 1 / 2 = T + h / T - h, 3 + 2i / 4 + 2i =
 // WKL(jac_mol[i]) x (1 + eps) / (1 - eps), or P / WBRODL x (1 +- eps) where jac_mol[i] is MONORTM_JVAR_P / _WBROD (DESIGN.md
 // section 3.11).  Layers >= nlay[p] are copied unchanged (the caller's padding).
+// State rayl_state (when not 0) scales nothing and holds the layer as the Rayleigh term alone sees it: the term is XRAYL f(v, T) WTOT
+// with WTOT = WBRODL + sum of WKL, summed in the order of continuum_kernel.hip, and nothing else of MODM survives WKL = 0, CLW = 0.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void jac_perturb_kernel(JacPerturbArgs a) {
     const size_t npl = (size_t)a.nprof * a.nlay_max;
@@ -34,6 +36,12 @@ __global__ __launch_bounds__(256) void jac_perturb_kernel(JacPerturbArgs a) {
     const double *w = a.WKL + pl * a.nmol;
     double *xw = a.xWKL + ((size_t)s * npl + pl) * a.nmol;
     for (int m = 0; m < a.nmol; m++) xw[m] = (in && m == mol) ? w[m] * fac : w[m];
+    if (in && a.rayl_state != 0 && s == a.rayl_state) {
+        double WTOT = a.WBRODL[pl];
+        for (int m = 0; m < a.nmol; m++) { WTOT = WTOT + w[m]; xw[m] = 0.; }
+        a.xWBRODL[(size_t)s * npl + pl] = WTOT;
+        a.xCLW[(size_t)s * npl + pl] = 0.;
+    }
     if (k == 0) a.xnlay[(size_t)s * a.nprof + prof] = a.nlay[prof];
 }
 

@@ -2,10 +2,12 @@
 force, the scalar arguments of MODM (continuum factors, SCLCPL, SCLHW, Y0RES) against differences of plain runs, dead variables,
 that nothing existing moves, step halving, the three entry families, the resident batch with graph replay, sharding, refusals.
 
-Small inputs throughout: 7 channels; layer counts on both sides of 24, where the adjoint goes from 2 to 8 layer groups."""
+Small inputs throughout: 7 channels; layer counts on both sides of 24, where the adjoint goes from 2 to 8 layer groups.  (Step halving
+also on two fixtures above 1340 cm-1, through tests/jvar_truth.py; every variable against the oracle there: tests/test_jacobian_vars_truth.py.)"""
 import numpy as np
 import pytest
 
+import jvar_truth as jt
 import obs_cases as oc
 from monortm_amd import api, synth, tape3
 from test_jacobian import _replace, code, profiles, rel_err, w_floor
@@ -253,6 +255,28 @@ def halved(case, real_case):
     return out
 
 
+HIGH_INPUTS = ("uv_hartley_huggins", "ir_o2_fundamental")   # fixtures above 1340 cm-1: finish_kernel<HIGH>, XO3CN / XO2CN / XRAYL live
+HIGH_VARS = ("p", "wbrod") + jt.FACTORS
+HIGH_ALIVE = {"uv_hartley_huggins": ("p", "wbrod", "xo3cn", "xo2cn", "xrayl"),
+              "ir_o2_fundamental": ("p", "wbrod", "xself", "xfrgn", "xco2c", "xo2cn", "xrayl")}
+
+
+@pytest.fixture(scope="module")
+def halved_high(workdir, gpu):
+    """The same on the three profiles of two cases of tests/jvar_truth.py (factors off 1), where the factors the microwave leaves dead
+    halve something non-zero."""
+    out = {}
+    for name in HIGH_INPUTS:
+        c = jt.case(name, workdir)
+        rt = api.MonoRTM(c.tape3, c.wn[0], c.wn[-1])
+        try:
+            for n, ab in _two_steps(rt, c.profiles, HIGH_VARS).items():
+                out[f"{n}, {name}"] = ab
+        finally:
+            rt.close()
+    return out
+
+
 @pytest.mark.parametrize("name", NEW + ("sclhw, real_like",))
 def test_step_halving(halved, name):
     """Halving jac_dlnw moves no slot by more than 1e-6 (rel_err and floor of tests/test_jacobian.py::test_step_halving).
@@ -260,12 +284,27 @@ def test_step_halving(halved, name):
     [xco2c]: below 30 cm-1 the CO2 continuum is ~1e-12 of a layer's optical depth; differences of the TOTAL optical depth gave a slot of
     quantisation noise there (1.0 and 0.5 in this measure).  The states of a continuum factor hold its OC slot instead (DESIGN.md
     section 3.11), which resolves the slot on its own scale."""
-    a, b = halved[name]
+    _check_halving(halved[name], name, name in ("p", "wbrod", "xself", "xfrgn", "xco2c", "xn2cn", "sclcpl", "y0res", "sclhw, real_like"))
+
+
+def _check_halving(ab, name, alive):
+    a, b = ab
     errs = [rel_err(b[p], a[p], axis=0, floor=w_floor(a[p])) for p in range(a.shape[0])]
     print(f"{name}: peak |k_w| {np.abs(a).max():.3e}, step halving {max(errs):.2e}")
     assert max(errs) <= 1e-6, errs
-    if name in ("p", "wbrod", "xself", "xfrgn", "xco2c", "xn2cn", "sclcpl", "y0res", "sclhw, real_like"):
+    if alive:
         assert np.any(a != 0), "the variable is dead on this input"
+    else:
+        assert not np.any(a != 0) and not np.any(b != 0), "a variable that reaches nothing gives slots that are exactly 0"
+
+
+@pytest.mark.parametrize("name", [f"{v}, {n}" for n in HIGH_INPUTS for v in HIGH_VARS])
+def test_step_halving_above_1340(halved_high, name):
+    """test_step_halving where XO3CN, XO2CN and XRAYL are live (uv_hartley_huggins) and where Rayleigh is 4e-11 of a layer's optical
+    depth (ir_o2_fundamental): its states hold Rayleigh's own term - differences of the total gave
+    quantisation there.  Every variable of the list is either alive or exactly 0 on these inputs."""
+    v, n = name.split(", ")
+    _check_halving(halved_high[name], name, v in HIGH_ALIVE[n])
 
 
 # ---- 6. the three entry families ------------------------------------------------------------------------------------------------
