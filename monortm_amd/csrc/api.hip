@@ -38,6 +38,7 @@ struct Ctx {
     // _TILE_WAVES / _FINISH_GENERIC give their defaults ONCE, when the context is created - nothing on the launch path calls getenv)
     struct Opt : ModmPlanOpt {   // (modm_plan.hpp: the switches that decide what a MODM evaluation launches)
         int ms_ablate = 0;        // timing experiments: lines_ms_kernel without its later stages (wrong results)
+        int ms_prepare = MS_PREPARE_FUSED;   // lines_ms_kernel's prepare stage: the fused trip where it applies / the pass loop always
         double jac_dt = MONORTM_JAC_DT, jac_dlnw = MONORTM_JAC_DLNW;   // half-steps of the Jacobian's central differences
     } opt;
     void *comm = nullptr;     // RCCL communicator of a multi-process job (monortm_hip_comm_init), one rank per context
@@ -196,6 +197,9 @@ int set_option(Ctx *c, const char *name, const char *value) {
     // lines_kernel: auto = by batch size; wn = lines_kernel (one state per wave) always; ms = lines_ms_kernel (several states per wave,
     // five wavenumbers per lane) wherever its layout fits (double precision, <= 64 wavenumbers)
     else if (n == "lines_kernel" && (autov || v == "wn" || v == "ms")) c->opt.lines_ms = autov ? -1 : (v == "ms" ? 1 : 0);
+    // ms_prepare: auto = fused = a plain chunk of two or three prepare passes in one trip per lane (lines_ms_kernel.hip, ms_prepare_trip);
+    // passes = the pass loop for every chunk (A/B measurements, tests of the two against each other: identical bits)
+    else if (n == "ms_prepare" && (autov || v == "fused" || v == "passes")) c->opt.ms_prepare = v == "passes" ? MS_PREPARE_PASSES : MS_PREPARE_FUSED;
 #ifdef MONORTM_EXPERIMENT   // stage ablations of lines_ms_kernel: timing only, wrong results - experiment builds alone know the option
     else if (n == "ms_ablate" && isint && iv >= 0 && iv <= 9) c->opt.ms_ablate = (int)iv;
 #endif
@@ -999,7 +1003,7 @@ int monortm_hip_init(const char *tape3_path, double v1, double v2, int icp, int 
     }
     if (const char *e = getenv("MONORTM_HOST_TIMING")) c->host_timing = e[0] == '1';
     if (getenv("MONORTM_FINISH_GENERIC")) c->opt.finish_generic = 1;  // (set, whatever its value: the default of option "finish")
-    for (const char *k : {"lines_kernel", "nslice", "fair", "tile_waves", "far_levels", "ms_items",
+    for (const char *k : {"lines_kernel", "nslice", "fair", "tile_waves", "far_levels", "ms_items", "ms_prepare",
 #ifdef MONORTM_EXPERIMENT
                           "ms_ablate",
 #endif
@@ -1463,6 +1467,7 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
         ms.scratch = c->ms_scratch;
         ms.slot_base = c->ms_slot_base;
         ms.ablate = c->opt.ms_ablate;
+        ms.prepare = c->opt.ms_prepare;
     }
     const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
     if (pl.use_ms && pl.ms_nprof < nprof) {

@@ -412,7 +412,10 @@ struct MsArgs {
     unsigned short *reach;    // [lines of the table] slots of channels each line / its negative resonance can reach (ms_reach_kernel, once per launch)
     float *near0;             // [lines of the table] distance of the table centre to the nearest channel, rounded down (ms_reach_kernel)
     int ablate;               // MONORTM_EXPERIMENT builds only (option ms_ablate; wrong results): 1 = prologue only, 2 = no evaluate stage, 3-5 parts of it
+    int prepare;              // option ms_prepare: MS_PREPARE_FUSED (= auto: one trip per plain chunk of two or three passes) / MS_PREPARE_PASSES (the pass loop always)
 };
+#define MS_PREPARE_FUSED 0
+#define MS_PREPARE_PASSES 1
 size_t lines_ms_scratch(const MsArgs &ms, long long nwg);
 void launch_lines_ms(const ModmArgs &a, const DevLines &L, const DevTables &tb, const MsArgs &ms, bool ibrd, hipStream_t s);
 

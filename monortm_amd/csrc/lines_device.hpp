@@ -154,6 +154,54 @@ __device__ __forceinline__ void exp_prep4(const double (&x)[4], double (&out)[4]
         out[i] = ldexp(p[i], (int)n[i]);
     }
 }
+// ... and the four exponentials of SEVERAL states of one line side by side (lines_ms_kernel's fused prepare trip: a lane prepares
+// its line for two or three states at once): one Horner step of all 4 NS chains per scalar constant, so the constant is
+// materialised once per trip instead of once per state.  Per chain the operations of exp_prep in the same order: identical bits.
+__device__ __forceinline__ void horner_n_s(double (&p)[8], const double (&r)[8], double c) {
+    asm("v_fma_f64 %0, %0, %8, %16\n\tv_fma_f64 %1, %1, %9, %16\n\tv_fma_f64 %2, %2, %10, %16\n\tv_fma_f64 %3, %3, %11, %16\n\t"
+        "v_fma_f64 %4, %4, %12, %16\n\tv_fma_f64 %5, %5, %13, %16\n\tv_fma_f64 %6, %6, %14, %16\n\tv_fma_f64 %7, %7, %15, %16"
+        : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7])
+        : "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7]), "s"(c));
+}
+__device__ __forceinline__ void horner_n_s(double (&p)[12], const double (&r)[12], double c) {
+    asm("v_fma_f64 %0, %0, %12, %24\n\tv_fma_f64 %1, %1, %13, %24\n\tv_fma_f64 %2, %2, %14, %24\n\tv_fma_f64 %3, %3, %15, %24\n\t"
+        "v_fma_f64 %4, %4, %16, %24\n\tv_fma_f64 %5, %5, %17, %24\n\tv_fma_f64 %6, %6, %18, %24\n\tv_fma_f64 %7, %7, %19, %24\n\t"
+        "v_fma_f64 %8, %8, %20, %24\n\tv_fma_f64 %9, %9, %21, %24\n\tv_fma_f64 %10, %10, %22, %24\n\tv_fma_f64 %11, %11, %23, %24"
+        : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7]), "+v"(p[8]), "+v"(p[9]),
+          "+v"(p[10]), "+v"(p[11])
+        : "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7]), "v"(r[8]), "v"(r[9]), "v"(r[10]),
+          "v"(r[11]), "s"(c));
+}
+template <int N>
+__device__ __forceinline__ void exp_prep_n(const double (&x)[N], double (&out)[N]) {
+    double r[N], p[N];
+    int n[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        const double nd = rint(x[i] * 1.44269504088896338700e+00);
+        r[i] = fma(-nd, 6.93147180369123816490e-01, x[i]);
+        r[i] = fma(-nd, 1.90821492927058770002e-10, r[i]);
+        p[i] = 1.0 / 6227020800.0;
+        n[i] = (int)nd;
+    }
+    horner_n_s(p, r, 1.0 / 479001600.0);
+    horner_n_s(p, r, 1.0 / 39916800.0);
+    horner_n_s(p, r, 1.0 / 3628800.0);
+    horner_n_s(p, r, 1.0 / 362880.0);
+    horner_n_s(p, r, 1.0 / 40320.0);
+    horner_n_s(p, r, 1.0 / 5040.0);
+    horner_n_s(p, r, 1.0 / 720.0);
+    horner_n_s(p, r, 1.0 / 120.0);
+    horner_n_s(p, r, 1.0 / 24.0);
+    horner_n_s(p, r, 1.0 / 6.0);
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        p[i] = fma(p[i], r[i], 0.5);
+        p[i] = fma(p[i], r[i], 1.0);
+        p[i] = fma(p[i], r[i], 1.0);
+        out[i] = ldexp(p[i], n[i]);
+    }
+}
 #endif
 
 // tanh for the radiation term RFT = WN tanh(hc WN / 2kT) (modm.f90:436-438), argument >= 0: the library call is ~225

@@ -11,6 +11,7 @@
 //     ten consecutive channels of every state) that no line of the group can reach is jumped over (lines_ms_asm.hpp);
 //   * prepare: one lane per (state, line) as before - the same functions (line_physics_core, line_records of lines_device.hpp);
 //     a pass holds whole states (64 / CL of them), so a lane keeps ITS line through the passes of a chunk and reads the table once;
+//     a plain chunk of two or three passes is prepared in ONE trip per lane for all its states (ms_prepare_trip: identical bits);
 //   * prologue: one pass over (state, molecule) and (state, isotopologue) items for all G states.
 // The G states share ONE candidate window per molecule (the union of theirs: a line outside a state's own window lies beyond
 // 25 cm-1 of every channel and adds nothing - the clamp / the EXEC mask of its class says so), so a line index means the same
@@ -29,6 +30,12 @@ namespace {
 using namespace monortm_dev;
 
 constexpr int WPS = MS_WPS;   // wavenumbers per lane
+// ms_prepare_trip repeats the arithmetic of line_physics_core / line_records: a timing experiment that alters theirs walks the passes
+#if defined(MONORTM_ABLATE_EXP4) || defined(MONORTM_ABLATE_ZSEARCH) || defined(MONORTM_ABLATE_VOIGT) || defined(MONORTM_NO_CLAMP_GUARD)
+constexpr bool MS_HAS_TRIP = false;
+#else
+constexpr bool MS_HAS_TRIP = true;
+#endif
 static_assert(MS_REACH_SLOTS == MS_WPS, "ms_reach.hpp forms one bit per wavenumber of a lane");
 
 __device__ __forceinline__ void ms_sync() {  // one wave: order the compiler, the LDS unit keeps program order
@@ -390,7 +397,8 @@ __device__ __attribute__((noinline)) int ms_prologue(const unsigned long long *s
             }
         }
         // MODM calls TIPS_2003 for every layer and all nmol molecules (modm.f90:250): the layer temperature alone decides the stop
-        if (act_e && ce == 0 && (Tk < 70. || Tk > 3000.)) atomicOr(a.errflag, ERRBIT_TEMP);
+        // (a NaN temperature stops too: the reference's interpolation finds no node for it and its partition sum stays 0, tips_2003.f90:272-277)
+        if (act_e && ce == 0 && !(Tk >= 70. && Tk <= 3000.)) atomicOr(a.errflag, ERRBIT_TEMP);
     }
     if (lane < nmol) { l.sLo[lane] = 0x7fffffff; l.sOff[lane + 1] = 0; }
     // null records behind every state's chunk (the read-ahead of the class loops runs two records past a run)
@@ -475,6 +483,95 @@ __device__ __attribute__((noinline)) int ms_prologue(const unsigned long long *s
     return l.sOff[nmol];
 }
 
+// ---- the fused prepare trip of a plain chunk (no coupled line, no width / shift conversion, no species broadening, every molecule
+// among the first MXBRD): a lane prepares ITS line for all NS = nsteps of its states (t spp + sub, t < NS) in one straight trip.
+// What belongs to the line is formed once (the conversions of the table's float fields, RADCT E, the water-vapour self width), the
+// exponentials of all states walk one Horner step per scalar constant (exp_prep_n: 4 NS chains), and there is no divergent region:
+// a lane without an item (no line, no state, state without this layer) computes on the scalars of a state that exists - ms_prologue
+// leaves harmless ones for every state of the wave - and stores the null record.  Per (state, line) the operations of
+// line_physics_core<false, true> and line_records<double, true> in their order, each rounded: identical bits.
+// The rare blocks of those functions are not here.  An item that needs one - the zeta quotient within 1e-12 of 0.99, the
+// nearest-channel search (near_lb does not rule a Voigt candidate out), a record of a special item (the clamp guard's fY) - makes
+// the trip return false for the whole wave: the caller then walks the chunk's pass loop, which stores every word again.
+template <int NS>
+__device__ __forceinline__ bool ms_prepare_trip(const MsArgs &ms, const MsLds &ld, int nslot, bool lin, int m, int slot0, const LineFields &lf,
+                                                float near0) {
+#pragma clang fp contract(off)
+    const int G = ms.G, CL = ms.CL, spp = ms.spp;
+    // (the lane's place from an opaque lane id: derived from the kernel's own, which lives in scratch, it is re-read in mid-trip)
+    int lane = (int)__lane_id();
+    asm volatile("" : "+v"(lane));
+    const int sub = (int)(((unsigned)lane * (unsigned)ms.inv_cl) >> 16), l = lane - sub * CL;
+    const bool lane_in = sub < spp;
+    const int mol = m + 1, iso = (lf.meta >> 6) & 15;
+    const double RADCT = K_PLANCK * K_CLIGHT / K_BOLTZ;
+    // ---- the line ----------------------------------------------------------------------------------------------------------------
+    const double xnu0 = lf.xnu0, s0adj = lf.s0adj, alpf = lf.alfa, delt = lf.pshift, E = lf.epp, XTILD = lf.tmpalf;
+    const double RE = RADCT * E;
+    double alps = lf.hwhm;
+    if (mol == 1 && alps == 0.) alps = 5 * alpf;   // HALFWHM_C (modm.f90:833-857)
+    const double near_s = (double)near0 * (1. - 1e-6);
+    const int oself = 10 + min(mol, MXBRD) - 1, oslot = slot0 + (iso ? iso - 1 : 0);
+    const double w0 = ld.sWn[0], w63 = ld.sWn[63];
+    // ---- the arguments of the exponentials, state by state ---------------------------------------------------------------------------
+    double Xnu[NS], xa[4 * NS], ex[4 * NS];
+#pragma unroll
+    for (int t = 0; t < NS; t++) {
+        const int s = t * spp + sub;
+        const double *ly = ld.sLay + ((lane_in & (s < G)) ? s : 0) * 20;
+        const double RHORAT = ly[0], lnRT = ly[3], cTk = ly[4], cT0 = ly[5], dTinv = ly[6];
+        Xnu[t] = xnu0 + (delt * RHORAT);
+        xa[4 * t] = RE * dTinv;
+        xa[4 * t + 1] = -(Xnu[t] * cTk);
+        xa[4 * t + 2] = -(Xnu[t] * cT0);
+        xa[4 * t + 3] = XTILD * lnRT;
+    }
+    exp_prep_n<4 * NS>(xa, ex);
+    // ---- the records, state by state --------------------------------------------------------------------------------------------------
+    bool bad = false;
+#pragma unroll
+    for (int t = 0; t < NS; t++) {
+        const int s = t * spp + sub;
+        const bool s_in = lane_in & (s < G);
+        const int sc = s_in ? s : 0;
+        const double *ly = ld.sLay + sc * 20;
+        const bool in = lin & s_in & (ly[19] != 0.);
+        const double RHORAT = ly[0], rho_self = ly[oself];
+        const double scor = ld.sScor[sc * nslot + oslot], dopfac = ld.sDop[sc * nslot + oslot];
+        const double XIPSF = iso ? scor : 0.;
+        // INTENS (modm.f90:860-865), HALFWHM_C, HALFWHM_D
+        const double S = s0adj * ex[4 * t] * XIPSF;
+        const double STILD = S * ((1 + ex[4 * t + 1]) * frcp_any(Xnu[t] * (1 - ex[4 * t + 2])));
+        const double rtx = ex[4 * t + 3];
+        const double alfa0i = alpf * rtx, hwhmsi = alps * rtx;
+        const double HW = alfa0i * (RHORAT - rho_self) + hwhmsi * rho_self;
+        const double HWD = Xnu[t] * dopfac;
+        // line_records: zeta = HW / (HW + HWD) > 0.99 (modm.f90:427) without the division; the amplitudes (c1 = g = 0, wsc = 1)
+        const double c1 = 0., g = 0., wsc = 1.0;
+        const double zsum = HW + HWD, zthr = 0.99 * zsum;
+        const bool z_gt = HW > zthr * (1. + 1e-12), z_lt = HW < zthr * (1. - 1e-12);
+        const double A2 = STILD * HW * (1.0 / K_PI);
+        const double HW2 = HW * HW;
+        const double p = A2 * frcp_any(625. + HW2);
+        const double A2w = A2 * wsc;
+        const double pa = (mol == 7) ? 25. : ((mol == 2) ? p : p * ((1. + c1 * 25.) + g)) * wsc;
+        const double near_lb = near_s - fabs(Xnu[t] - xnu0) - 1e-9;
+        const bool fY = (mol != 7) & (mol != 2) & !((A2w >= 0.) & (HW2 == HW2) & (A2 <= 0.25 * HW2));
+        // (zeta > 0.99: no Voigt; zeta < 0.99 and no channel within 100 Doppler widths: none either; anything else is a rare block)
+        // (bitwise on purpose: no short-circuit, no divergent region)
+        bad |= in & ((!z_gt & !(z_lt & (near_lb > 100. * HWD))) | fY);
+        const bool fM2 = (mol != 2) & (w0 + Xnu[t] <= 25.);
+        const bool fAL = !(fabs(w0 - Xnu[t]) > 25.) & !(fabs(w63 - Xnu[t]) > 25.);
+        if (s_in) {
+            ld.sA[s * ms.sa_stride + l] = in ? HotA{Xnu[t], HW2, A2w, pa} : HotA{0., 1., 0., 0.};
+            ld.sFlag[s * CL + l] = in ? (unsigned char)((fAL ? 0u : 1u) | (fM2 ? 2u : 0u)) : (unsigned char)0;
+        }
+    }
+    if (__builtin_amdgcn_ballot_w64(bad) != 0ull) return false;
+    if ((sub == 0) & (l < NS)) ld.sMask[4 + l] = 0ull;   // no rare-shape records in any pass
+    return true;
+}
+
 // ---- prepare: the chunk's lines [base, base + CL) for every state.  A lane is (sub, l): line l of the chunk for state t spp + sub in
 // pass t (spp = 64 / CL whole states a pass; lanes from spp CL on idle), so its line is the same in every pass: molecule, table
 // index, the table's fields, meta and the plain / non-plain choice are resolved once per chunk, and a pass does what depends on the
@@ -513,9 +610,17 @@ __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int 
     // tables) takes the instantiation without those blocks - fifteen divergent regions less to step through
     const bool plain = ((meta >> 10) & 3u) == 0u && ((meta >> 13) & 3u) == 0u;
     const bool all_plain = __builtin_amdgcn_ballot_w64(lin && !plain) == 0ull;
-    // ---- the states: pass t serves state t spp + sub ------------------------------------------------------------------------------
+    // ---- the states of a plain chunk in one trip (option ms_prepare; two or three passes' worth - one pass has nothing to fuse) ----
+    bool done = false;
+    if constexpr (MS_HAS_TRIP && !IBRD) {
+        if (all_plain && ms.prepare != MS_PREPARE_PASSES && __builtin_amdgcn_ballot_w64(lin && m >= MXBRD) == 0ull) {
+            if (ms.nsteps == 3) done = ms_prepare_trip<3>(ms, ld, nslot, lin, m, slot0, lf, near0);
+            else if (ms.nsteps == 2) done = ms_prepare_trip<2>(ms, ld, nslot, lin, m, slot0, lf, near0);
+        }
+    }
+    // ---- the states, pass by pass: pass t serves state t spp + sub (the general path, and a chunk that a trip handed back) --------
 #pragma unroll 1
-    for (int t = 0; t < ms.nsteps; t++) {
+    for (int t = done ? ms.nsteps : 0; t < ms.nsteps; t++) {
         const int s = t * ms.spp + sub;
         const bool s_in = lane_in && s < G;
         const bool in = lin && s_in && ld.sLay[s * 20 + 19] != 0.;
