@@ -820,7 +820,7 @@ class MonoRTM:
 
     def set_option(self, name: str, value) -> None:
         """Measurement switches of the context (monortm_hip_set_option): nslice, fair, tile_waves, far_levels, lines_kernel = auto | wn |
-        ms, ms_items, ms_prepare = auto | fused | passes, jac_dt, jac_dlnw, and finish = auto | generic (generic: finish_kernel also below 820 cm-1, where finish_mw_kernel
+        ms, ms_items, ms_prepare = auto | fused | passes, ms_plan = auto | on | off, jac_dt, jac_dlnw, and finish = auto | generic (generic: finish_kernel also below 820 cm-1, where finish_mw_kernel
         serves by default; the environment variable MONORTM_FINISH_GENERIC makes it the default of a new context)."""
         self._chk(self.lib.monortm_hip_set_option(self.ctx, name.encode(), str(value).encode()))
 

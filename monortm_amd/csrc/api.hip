@@ -39,6 +39,7 @@ struct Ctx {
     struct Opt : ModmPlanOpt {   // (modm_plan.hpp: the switches that decide what a MODM evaluation launches)
         int ms_ablate = 0;        // timing experiments: lines_ms_kernel without its later stages (wrong results)
         int ms_prepare = MS_PREPARE_FUSED;   // lines_ms_kernel's prepare stage: the fused trip where it applies / the pass loop always
+        int ms_plan = 1;          // lines_ms_kernel: the launch-wide chunk plan for the waves that match it / every wave on its own
         double jac_dt = MONORTM_JAC_DT, jac_dlnw = MONORTM_JAC_DLNW;   // half-steps of the Jacobian's central differences
     } opt;
     void *comm = nullptr;     // RCCL communicator of a multi-process job (monortm_hip_comm_init), one rank per context
@@ -69,6 +70,8 @@ struct Ctx {
     void *ms_scratch = nullptr;
     unsigned short *ms_reach = nullptr;  // per table line: the slots of channels it / its negative resonance can reach (ms_reach_kernel)
     size_t ms_scratch_bytes = 0;
+    void *ms_plan = nullptr;  // the chunk plan of lines_ms_kernel (device_common.hpp, MS_PLAN_*): rewritten by every launch, grown on demand
+    size_t ms_plan_words = 0;
     double *osum = nullptr;   // per (profile, layer, wn) line sums handed from lines_kernel to finish_mw_kernel, grown on demand
     size_t osum_elems = 0;
     DevXsec xs{};             // cross-section tables (monortm_hip_xsec_tables); xs_buf holds them, replaced as a whole
@@ -200,6 +203,9 @@ int set_option(Ctx *c, const char *name, const char *value) {
     // ms_prepare: auto = fused = a plain chunk of two or three prepare passes in one trip per lane (lines_ms_kernel.hip, ms_prepare_trip);
     // passes = the pass loop for every chunk (A/B measurements, tests of the two against each other: identical bits)
     else if (n == "ms_prepare" && (autov || v == "fused" || v == "passes")) c->opt.ms_prepare = v == "passes" ? MS_PREPARE_PASSES : MS_PREPARE_FUSED;
+    // ms_plan: auto = on = a wave whose states all match the launch-wide chunk plan (lines_ms_kernel.hip, ms_plan_wave) copies its windows
+    // and the words of its plain chunks from it; off = every wave searches and ballots for itself (A/B measurements, tests: identical bits)
+    else if (n == "ms_plan" && (autov || v == "on" || v == "off")) c->opt.ms_plan = v == "off" ? 0 : 1;
 #ifdef MONORTM_EXPERIMENT   // stage ablations of lines_ms_kernel: timing only, wrong results - experiment builds alone know the option
     else if (n == "ms_ablate" && isint && iv >= 0 && iv <= 9) c->opt.ms_ablate = (int)iv;
 #endif
@@ -1003,7 +1009,7 @@ int monortm_hip_init(const char *tape3_path, double v1, double v2, int icp, int 
     }
     if (const char *e = getenv("MONORTM_HOST_TIMING")) c->host_timing = e[0] == '1';
     if (getenv("MONORTM_FINISH_GENERIC")) c->opt.finish_generic = 1;  // (set, whatever its value: the default of option "finish")
-    for (const char *k : {"lines_kernel", "nslice", "fair", "tile_waves", "far_levels", "ms_items", "ms_prepare",
+    for (const char *k : {"lines_kernel", "nslice", "fair", "tile_waves", "far_levels", "ms_items", "ms_prepare", "ms_plan",
 #ifdef MONORTM_EXPERIMENT
                           "ms_ablate",
 #endif
@@ -1043,6 +1049,15 @@ void monortm_hip_finalize(void *ctx) {
     if (c->partial) hipFree(c->partial);
     if (c->osum) hipFree(c->osum);
     if (c->ms_scratch) hipFree(c->ms_scratch);
+    if (c->ms_plan) {
+#ifdef MONORTM_EXPERIMENT   // the share of waves and chunks that took the plan's fast path, over every launch of this context
+        unsigned long long n[4] = {0, 0, 0, 0};
+        if (getenv("MONORTM_MS_PLAN_STATS") && hipDeviceSynchronize() == hipSuccess &&
+            hipMemcpy(n, static_cast<unsigned long long *>(c->ms_plan) + MS_PLAN_CNT, sizeof(n), hipMemcpyDeviceToHost) == hipSuccess)
+            fprintf(stderr, "ms_plan: waves %llu match %llu chunks %llu fast %llu\n", n[0], n[1], n[2], n[3]);
+#endif
+        hipFree(c->ms_plan);
+    }
     for (void *p : c->xs_buf) hipFree(p);
     if (c->phys) hipFree(c->phys);
     if (c->far) hipFree(c->far);
@@ -1468,6 +1483,13 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
         ms.slot_base = c->ms_slot_base;
         ms.ablate = c->opt.ms_ablate;
         ms.prepare = c->opt.ms_prepare;
+        ms.plan_on = c->opt.ms_plan;
+        if (ms.plan_on) {
+            const size_t had = c->ms_plan_words;
+            HIPCHK(c, grow(&c->ms_plan, &c->ms_plan_words, lines_ms_plan_words((long long)c->host.size(), ms.CL), sizeof(unsigned long long)));
+            if (c->ms_plan_words != had) HIPCHK(c, hipMemsetAsync(c->ms_plan, 0, c->ms_plan_words * sizeof(unsigned long long), s));
+            ms.plan = static_cast<unsigned long long *>(c->ms_plan);
+        }
     }
     const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
     if (pl.use_ms && pl.ms_nprof < nprof) {

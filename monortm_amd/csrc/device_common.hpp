@@ -411,11 +411,24 @@ struct MsArgs {
     void *scratch;            // per workgroup G x CL x (HotB + ColdLine): the records of the rare shapes of a chunk
     unsigned short *reach;    // [lines of the table] slots of channels each line / its negative resonance can reach (ms_reach_kernel, once per launch)
     float *near0;             // [lines of the table] distance of the table centre to the nearest channel, rounded down (ms_reach_kernel)
-    int ablate;               // MONORTM_EXPERIMENT builds only (option ms_ablate; wrong results): 1 = prologue only, 2 = no evaluate stage, 3-5 parts of it
+    int ablate;               // MONORTM_EXPERIMENT builds only (option ms_ablate; wrong results): 1 = prologue only, 2 = no evaluate stage, 3-5 parts of it,
+                              // 6 = as 2 without the prepare stage's tail for the chunks a trip finished
     int prepare;              // option ms_prepare: MS_PREPARE_FUSED (= auto: one trip per plain chunk of two or three passes) / MS_PREPARE_PASSES (the pass loop always)
+    int plan_on;              // option ms_plan: 1 = waves that match the launch-wide chunk plan take their windows and chunk words from it
+    unsigned long long *plan; // the chunk plan, written once per launch by the plan blocks of ms_reach_kernel's grid (layout: MS_PLAN_* below)
 };
 #define MS_PREPARE_FUSED 0
 #define MS_PREPARE_PASSES 1
+// the chunk plan in 64-bit words.  Head: the ints lo[MXMOL] (first candidate line per molecule, 0x7fffffff: none) and off[MXMOL + 1]
+// (prefix sums of the counts, off[nmol] = total) for states with RHORAT <= 1, then four counters of MONORTM_EXPERIMENT builds (waves,
+// waves that match, chunks, chunks on the fast path).  Per chunk of CL candidates MS_PLAN_CHUNK words: [0] bit 0 = no coupled line / width
+// or shift conversion in the chunk, bit 1 = a molecule beyond MXBRD; [2 + k] the lines that reach slot k, [2 + MS_WPS + k] those whose
+// negative resonance does (the words of ms_prepare's tail for a chunk without a rare shape in a wave that is not dense)
+constexpr int MS_PLAN_OFF = MXMOL;                     // (int index of off[0])
+constexpr int MS_PLAN_CNT = (2 * MXMOL + 1 + 1) / 2;   // (word index of the counters)
+constexpr int MS_PLAN_HEAD = MS_PLAN_CNT + 4;
+constexpr int MS_PLAN_CHUNK = 2 + 2 * MS_WPS;
+inline size_t lines_ms_plan_words(long long nlines, int CL) { return (size_t)MS_PLAN_HEAD + (size_t)MS_PLAN_CHUNK * (size_t)((nlines + CL - 1) / CL); }
 size_t lines_ms_scratch(const MsArgs &ms, long long nwg);
 void launch_lines_ms(const ModmArgs &a, const DevLines &L, const DevTables &tb, const MsArgs &ms, bool ibrd, hipStream_t s);
 

@@ -19,7 +19,8 @@
 // the shared reciprocals (1e-15 of a term; 1e-12 of a cell's optical depth); tests/test_ms_kernel.py holds the two kernels
 // together and both to the oracle.  A profile's last bits depend on the profiles that share its waves.
 // Memory besides the outputs: 10 KB of LDS and 21 KB of scratch in global memory per wave (records of rare shapes, radiation terms,
-// the sums of the run in progress - L2-resident), two bytes per table line (ms_reach_kernel).
+// the sums of the run in progress - L2-resident), two bytes per table line (ms_reach_kernel), 96 bytes per possible chunk of CL lines
+// (the launch-wide chunk plan that the same launch writes: ms_plan_wave).
 #define MONORTM_EXP_SGPR_CONSTANTS 1   // (exp_prep of lines_device.hpp: see there)
 #include "lines_device.hpp"
 #include "lines_ms_asm.hpp"
@@ -77,8 +78,10 @@ __device__ __forceinline__ HotB ms_hotb(const MsState &st, const MsSpec &sp, int
 // the Voigt candidates of a molecule run (VSCAN of lines_device.hpp for five wavenumbers and G states): the lines walked the
 // Lorentz loops like any other; here every (line, lane, k) within 100 Doppler widths is queued, and the queue is worked off one
 // pair per lane: Voigt value minus the Lorentz term that was added
+// (what the scan needs of MsArgs: the out-of-line function receives its arguments by value, a whole MsArgs as a copy on the stack)
+struct MsGeom { int LPS, CL, sa_stride; };
 template <int KIND>
-__device__ __forceinline__ void ms_voigt_flush(const HotA *sA, const HotB *gB, const ColdLine *gC, const MsArgs &ms, const unsigned short *vq, int n,
+__device__ __forceinline__ void ms_voigt_flush(const HotA *sA, const HotB *gB, const ColdLine *gC, const MsGeom &ms, const unsigned short *vq, int n,
                                                const double (&W)[WPS], int mol, double (&S)[WPS], int *errflag) {
     const int lane = (int)__lane_id();
     const unsigned rec = (lane < n) ? vq[lane] : 0u;
@@ -119,7 +122,7 @@ __device__ __forceinline__ void ms_voigt_flush(const HotA *sA, const HotB *gB, c
 // and wavenumbers travel through two small arrays of the caller)
 template <int KIND>
 __device__ __attribute__((noinline)) void ms_voigt_scan(unsigned long long cand, unsigned long long ymask, MsState st, MsSpec sp, const HotA *sA,
-                                              const HotB *gB, const ColdLine *gC, MsArgs ms, const double (&W)[WPS], unsigned kvalid, int mol,
+                                              const HotB *gB, const ColdLine *gC, MsGeom ms, const double (&W)[WPS], unsigned kvalid, int mol,
                                               double (&S)[WPS], int *errflag, unsigned short *vq) {
     const int lane = (int)__lane_id();
     int nq = 0;
@@ -222,7 +225,7 @@ __device__ __forceinline__ void ms_eval_run(const MsState &st, const MsSpec &sp,
         double Wt[WPS], St[WPS];   // (copies: the arrays handed to an out-of-line function live in memory)
 #pragma unroll
         for (int k = 0; k < WPS; k++) { Wt[k] = W[k]; St[k] = S[k]; }
-        ms_voigt_scan<KIND>(cand, Y, st, sp, sA, gB, gC, ms, Wt, kvalid, mol, St, errflag, vq);
+        ms_voigt_scan<KIND>(cand, Y, st, sp, sA, gB, gC, MsGeom{ms.LPS, ms.CL, ms.sa_stride}, Wt, kvalid, mol, St, errflag, vq);
 #pragma unroll
         for (int k = 0; k < WPS; k++) S[k] = St[k];
     }
@@ -251,7 +254,7 @@ struct MsLds {
     int *sSlot;            // [nmol + 1] slot of (molecule, isotopologue 1)
     unsigned long long *sMask;   // [4 + MS_MAXSTEPS + 2 WPS + 1] class masks of the chunk (NT, M2, V, Y), per prepare pass the lanes whose rare-shape records exist,
                                  // per slot k the lines that reach one of its channels (lines_ms_asm.hpp, MS_IFK), and a word that
-                                 // is non-zero when a state of the wave is denser than ms_reach_kernel's margin allows; behind it per slot
+                                 // has bit 0 set when a state of the wave is denser than ms_reach_kernel's margin allows (bit 1: the wave matches the chunk plan); behind it per slot
                                  // the lines whose NEGATIVE resonance reaches the slot (MS_IFQ)
     unsigned char *sFlag;  // [nsteps * 64] class flags per item (state * CL + line): bits 0-3 NT, M2, V, Y
     int *sRole;            // [64] the lane in the evaluate stage: se | ce << 8 | kvalid << 16 | profile exists << 24 | state active << 25 |
@@ -312,8 +315,17 @@ __device__ __forceinline__ MsLane ms_lane(const MsArgs &mc, int pg, const int *s
     return l;
 }
 
+// the chunk plan through the constant address space: wave-uniform addresses there are scalar loads (the plan is written by the launch
+// before this one, ms_reach_kernel's, and by nobody during this one)
+typedef const __attribute__((address_space(4))) unsigned long long *ms_plan_t;
+__device__ __forceinline__ ms_plan_t ms_plan_chunk(const MsArgs &ms, int ck) {
+    return (ms_plan_t)(size_t)(ms.plan + MS_PLAN_HEAD + (size_t)MS_PLAN_CHUNK * (size_t)ck);
+}
+constexpr int MS_MATCH_BIT = 0x40000000;   // ms_prologue's result: the wave matches the chunk plan
+
 // ---- prologue: the layer scalars of every state (INITI + head of LINES: modm.f90:868-883, :301-314; the expressions of
-// lines_kernel), the candidate window of the wave, partition sums and Doppler factors.  Returns the number of candidate lines.
+// lines_kernel), the candidate window of the wave, partition sums and Doppler factors.  Returns the number of candidate lines
+// (+ MS_MATCH_BIT).
 // (ks: the kernel's kernarg segment - the builtin that returns it is null in a callee)
 __device__ __attribute__((noinline)) int ms_prologue(const unsigned long long *sKseg, int lay, int pg) {
     extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
@@ -413,6 +425,41 @@ __device__ __attribute__((noinline)) int ms_prologue(const unsigned long long *s
         }
         l.sMask[4 + MS_MAXSTEPS + WPS] = dense;
     }
+    // ---- the wave against the launch-wide chunk plan (ms_plan_wave: the windows of a state with RHORAT <= 1) ---------------------------
+    // A wave MATCHES when (a) every live state has RHORAT <= 1 and neither RHORAT, WTOT nor T is a NaN, and (b) every molecule whose
+    // plan window holds a line has a non-zero column in some live state.  Then the loop below would give the plan's sLo / sOff exactly:
+    // by (a) every state that takes part for a molecule either searches with pad = max_abs_shift x 1 + 1e-6 - the plan's expression on
+    // the same channels, so the same doubles vlo / vhi and the same search over the same vnu - or keeps the molecule's whole range where the
+    // plan keeps it (coupled O2, unsorted: conditions of the table alone; the NaN clause is ruled out by (a)).  All its states thus hold
+    // the plan's window; by (b) at least one of them enters it into the union wherever it is not empty, and where it is empty no state
+    // enters anything: sLo stays 0x7fffffff, the count 0 - what the plan stores.
+    bool match = false;
+    if (ms.plan_on) {
+        const int *pi = reinterpret_cast<const int *>(ms.plan);
+        bool bad = false;
+        if (lane < G) {
+            const double *ly = l.sLay + lane * 20;
+            bad = ly[19] != 0. && (!(ly[0] <= 1.0) || ly[9] != ly[9] || ly[18] != ly[18]);
+        }
+        if (lane < nmol) {
+            bool has = false;
+            for (int s = 0; s < G; s++) has |= l.sLay[s * 20 + 19] != 0. && l.sW[s * nmol + lane] != 0.;
+            const int o0 = pi[MS_PLAN_OFF + lane], o1 = pi[MS_PLAN_OFF + lane + 1];
+            bad |= !has && o1 > o0;
+            l.sLo[lane] = pi[lane];   // (a wave that does not match overwrites both below)
+            l.sOff[lane + 1] = o1;
+        }
+        match = __builtin_amdgcn_ballot_w64(bad) == 0ull;
+        if (lane == 0) {
+            l.sOff[0] = 0;
+            if (match) l.sMask[4 + MS_MAXSTEPS + WPS] = 2ull;   // (bit 1 of the dense word, which is 0 here: kept there for the function's result)
+        }
+    }
+    if (!match) {   // (wave-uniform; the searches and the prefix as they were, not indented again)
+    if (ms.plan_on) {
+        if (lane < nmol) { l.sLo[lane] = 0x7fffffff; l.sOff[lane + 1] = 0; }
+        ms_sync();
+    }
     // ---- candidate window of every (state, molecule); the wave walks the union -----------------------------------------------------
     for (int i = lane; i < G * nmol; i += 64) {
         const int s = i / nmol, m = i - s * nmol, mol = m + 1;
@@ -449,6 +496,7 @@ __device__ __attribute__((noinline)) int ms_prologue(const unsigned long long *s
             l.sOff[m + 1] = acc;
         }
     }
+    }   // (!match)
     ms_sync();
     // ---- TIPS + Doppler factor per (state, molecule, isotopologue of the table): src/tips_2003.f90:60-296, src/modm.f90:442-454 -----
     for (int i = lane; i < G * nslot; i += 64) {
@@ -480,7 +528,7 @@ __device__ __attribute__((noinline)) int ms_prologue(const unsigned long long *s
                     if ((kvalid >> k) & 1u) obm[(size_t)m * nwn + ce + LPS * k] = 0.;
             }
     ms_sync();
-    return l.sOff[nmol];
+    return l.sOff[nmol] | ((l.sMask[4 + MS_MAXSTEPS + WPS] & 2ull) ? MS_MATCH_BIT : 0);   // (a table has far fewer than 2^30 lines)
 }
 
 // ---- the fused prepare trip of a plain chunk (no coupled line, no width / shift conversion, no species broadening, every molecule
@@ -494,8 +542,11 @@ __device__ __attribute__((noinline)) int ms_prologue(const unsigned long long *s
 // nearest-channel search (near_lb does not rule a Voigt candidate out), a record of a special item (the clamp guard's fY) - makes
 // the trip return false for the whole wave: the caller then walks the chunk's pass loop, which stores every word again.
 template <int NS>
+// In a wave that matches the chunk plan (`match`) a finished trip leaves the class words NT / M2 in sMask itself - one ballot each over the
+// flags a lane has ORed over its states, the sub-blocks folded onto the low CL bits - and stores neither the flags nor the (zero)
+// rare-shape words: nobody reads them (ms_prepare).
 __device__ __forceinline__ bool ms_prepare_trip(const MsArgs &ms, const MsLds &ld, int nslot, bool lin, int m, int slot0, const LineFields &lf,
-                                                float near0) {
+                                                float near0, bool match) {
 #pragma clang fp contract(off)
     const int G = ms.G, CL = ms.CL, spp = ms.spp;
     // (the lane's place from an opaque lane id: derived from the kernel's own, which lives in scratch, it is re-read in mid-trip)
@@ -529,6 +580,7 @@ __device__ __forceinline__ bool ms_prepare_trip(const MsArgs &ms, const MsLds &l
     exp_prep_n<4 * NS>(xa, ex);
     // ---- the records, state by state --------------------------------------------------------------------------------------------------
     bool bad = false;
+    bool anyNT = false, anyM2 = false;   // the lane's flags, ORed over its states (booleans: lane masks in scalar registers)
 #pragma unroll
     for (int t = 0; t < NS; t++) {
         const int s = t * spp + sub;
@@ -562,12 +614,24 @@ __device__ __forceinline__ bool ms_prepare_trip(const MsArgs &ms, const MsLds &l
         bad |= in & ((!z_gt & !(z_lt & (near_lb > 100. * HWD))) | fY);
         const bool fM2 = (mol != 2) & (w0 + Xnu[t] <= 25.);
         const bool fAL = !(fabs(w0 - Xnu[t]) > 25.) & !(fabs(w63 - Xnu[t]) > 25.);
+        anyNT |= in & !fAL;
+        anyM2 |= in & fM2;
         if (s_in) {
             ld.sA[s * ms.sa_stride + l] = in ? HotA{Xnu[t], HW2, A2w, pa} : HotA{0., 1., 0., 0.};
-            ld.sFlag[s * CL + l] = in ? (unsigned char)((fAL ? 0u : 1u) | (fM2 ? 2u : 0u)) : (unsigned char)0;
+            if (!match) ld.sFlag[s * CL + l] = in ? (unsigned char)((fAL ? 0u : 1u) | (fM2 ? 2u : 0u)) : (unsigned char)0;
         }
     }
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull) return false;
+    if (match) {
+        // lane = sub CL + l holds line l: bit l of the words = some sub-block's lane of line l has the flag (its states t spp + sub
+        // cover every state of the wave: the OR over the states that ms_prepare's tail forms from sFlag)
+        const unsigned long long nt = __builtin_amdgcn_ballot_w64(anyNT), m2 = __builtin_amdgcn_ballot_w64(anyM2);
+        unsigned long long ntf = 0ull, m2f = 0ull;
+        for (int q = 0, sh = 0; q < spp; q++, sh += CL) { ntf |= nt >> sh; m2f |= m2 >> sh; }
+        const unsigned long long low = (CL >= 64) ? ~0ull : ((1ull << CL) - 1ull);
+        if (lane == 0) { ld.sMask[0] = ntf & low; ld.sMask[1] = m2f & low; }
+        return true;
+    }
     if ((sub == 0) & (l < NS)) ld.sMask[4 + l] = 0ull;   // no rare-shape records in any pass
     return true;
 }
@@ -577,8 +641,11 @@ __device__ __forceinline__ bool ms_prepare_trip(const MsArgs &ms, const MsLds &l
 // index, the table's fields, meta and the plain / non-plain choice are resolved once per chunk, and a pass does what depends on the
 // state.  Leaves the records in sA (+ HotB / ColdLine of the rare shapes in the workgroup's scratch), the class of every line for
 // the wave - the most general over its states - and per pass the lanes whose rare-shape records exist in sMask.
+// In a wave that matches the chunk plan (`match`; chunk number ck) the plain / MXBRD words come from the plan, and a chunk that a trip
+// finished returns true with NT / M2 in sMask and nothing of the tail done: its V, Y and rare-shape words are zero and its slot
+// words are the plan's (the caller reads them).  Every other chunk returns false with every word in sMask.
 template <bool IBRD>
-__device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int base, int mchunk, int total, HotB *gB, ColdLine *gC) {
+__device__ __forceinline__ bool ms_prepare(const unsigned long long *sKseg, int base, int mchunk, int total, HotB *gB, ColdLine *gC, int ck, bool match) {
     extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
     const kseg_t ks = ms_kseg_from(*sKseg);
     const ModmArgs &a = *(const ModmArgs *)ks;
@@ -609,13 +676,18 @@ __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int 
     // a chunk without a coupled line or an air-width / air-shift conversion (meta bits 10-11, 13, 14: most chunks of most
     // tables) takes the instantiation without those blocks - fifteen divergent regions less to step through
     const bool plain = ((meta >> 10) & 3u) == 0u && ((meta >> 13) & 3u) == 0u;
-    const bool all_plain = __builtin_amdgcn_ballot_w64(lin && !plain) == 0ull;
+    const unsigned long long pw = match ? ms_plan_chunk(ms, ck)[0] : 0ull;   // (bit 0: all plain, bit 1: a molecule beyond MXBRD)
+    const bool all_plain = match ? (pw & 1ull) != 0ull : __builtin_amdgcn_ballot_w64(lin && !plain) == 0ull;
     // ---- the states of a plain chunk in one trip (option ms_prepare; two or three passes' worth - one pass has nothing to fuse) ----
     bool done = false;
     if constexpr (MS_HAS_TRIP && !IBRD) {
-        if (all_plain && ms.prepare != MS_PREPARE_PASSES && __builtin_amdgcn_ballot_w64(lin && m >= MXBRD) == 0ull) {
-            if (ms.nsteps == 3) done = ms_prepare_trip<3>(ms, ld, nslot, lin, m, slot0, lf, near0);
-            else if (ms.nsteps == 2) done = ms_prepare_trip<2>(ms, ld, nslot, lin, m, slot0, lf, near0);
+        if (all_plain && ms.prepare != MS_PREPARE_PASSES && (match ? (pw & 2ull) == 0ull : __builtin_amdgcn_ballot_w64(lin && m >= MXBRD) == 0ull)) {
+            if (ms.nsteps == 3) done = ms_prepare_trip<3>(ms, ld, nslot, lin, m, slot0, lf, near0, match);
+            else if (ms.nsteps == 2) done = ms_prepare_trip<2>(ms, ld, nslot, lin, m, slot0, lf, near0, match);
+        }
+        if (done && match) {   // (the records are in sA; the trip issued no global store)
+            ms_sync();
+            return true;
         }
     }
     // ---- the states, pass by pass: pass t serves state t spp + sub (the general path, and a chunk that a trip handed back) --------
@@ -678,14 +750,17 @@ __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int 
         const unsigned long long bs = __builtin_amdgcn_ballot_w64(special);
         if (lane == 0) ld.sMask[4 + t] = bs;
     }
+#ifdef MONORTM_EXPERIMENT
+    if (ms.ablate == 6 && done) return false;   // (prices the tail below for the chunks a trip finished: counters of ablate 2 less those of 6)
+#endif
     ms_sync_global();
     // the class of a line for the wave: the most general over its states
     unsigned f = 0u;
     if (lane < CL)
         for (int s = 0; s < G; s++) f |= ld.sFlag[s * CL + lane];
-    const unsigned long long NT = __builtin_amdgcn_ballot_w64(f & 1u), M2 = __builtin_amdgcn_ballot_w64(f & 2u),
+    const unsigned long long cNT = __builtin_amdgcn_ballot_w64(f & 1u), cM2 = __builtin_amdgcn_ballot_w64(f & 2u),
                              V = __builtin_amdgcn_ballot_w64(f & 4u), Y = __builtin_amdgcn_ballot_w64(f & 8u);
-    if (lane == 0) { ld.sMask[0] = NT; ld.sMask[1] = M2; ld.sMask[2] = V; ld.sMask[3] = Y; }
+    if (lane == 0) { ld.sMask[0] = cNT; ld.sMask[1] = cM2; ld.sMask[2] = V; ld.sMask[3] = Y; }
     // ... and the slots it reaches (slot k = the k-th wavenumbers of the lanes = channels k LPS .. k LPS + LPS - 1 of every state): a
     // property of the table line and the channel set up to the pressure shift, formed once per launch by ms_reach_kernel with a
     // margin for the shifts of states up to RHORAT = MS_REACH_RHO (a wave with a denser state - ms_prologue notes it in sMask's
@@ -694,7 +769,7 @@ __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int 
         unsigned r = 0u;
         if (lane < CL && lin) {   // (lanes below CL are sub 0: their l is the lane, idx the line's)
             r = ms.reach[idx];
-            if ((f & (4u | 8u)) || ld.sMask[4 + MS_MAXSTEPS + WPS] != 0ull) r = 0x1f1fu;
+            if ((f & (4u | 8u)) || (ld.sMask[4 + MS_MAXSTEPS + WPS] & 1ull) != 0ull) r = 0x1f1fu;
         }
 #pragma unroll
         for (int k = 0; k < WPS; k++) {
@@ -703,19 +778,97 @@ __device__ __forceinline__ void ms_prepare(const unsigned long long *sKseg, int 
         }
     }
     ms_sync();
+    return false;
 }
 
 // ---- ms_reach_kernel: per table line the slots (of LPS consecutive channels) it can reach, |WN - Xnu| <= 25 cm-1 for some channel
 // of the slot with the shifted centre anywhere within max_abs_shift x MS_REACH_RHO of the table's (line_table.cpp: |Xnu - XNU0| <=
 // max_abs_shift x RHORAT); a coupled O2 line (no rule, modm.f90:755-792) and a NaN centre reach every slot that holds a channel.
 // One byte per line, once per launch (the channels are the caller's device array).
-__global__ void ms_reach_kernel(const double *wn, int nwn, int LPS, DevLines L, int nlines, unsigned short *reach, float *near0) {
+//
+// The blocks from `reach_blocks` on write the launch-wide CHUNK PLAN (device_common.hpp, MS_PLAN_*; option ms_plan): what a wave of
+// lines_ms_kernel whose states all have RHORAT <= 1 and a column of every molecule would form for itself - the candidate windows
+// (ms_prologue's expressions and search with fmax(RHORAT, 1) = 1), their prefix sums, and per chunk of CL candidates the plain / MXBRD
+// bits and the slot words of ms_prepare's tail for a chunk without a rare shape (f & 12 == 0) in a wave that is not dense.  One wave
+// per chunk, each on its own: it repeats the windows (nmol searches side by side) and forms the reach bits of its lines with
+// ms_reach_word, so it waits for no other block.
+__device__ __forceinline__ void ms_plan_wave(const double *swn, int nwn, int LPS, const DevLines &L, int nmol, int CL, int ck, int nck,
+                                             unsigned long long *plan, int (*pLo)[MXMOL], int (*pOff)[MXMOL + 1]) {
+    const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
+    int *sLo = pLo[w], *sOff = pOff[w];
+    if (ck >= nck) return;
+    if (lane < nmol) {
+        const int m = lane, mol = m + 1;
+        int lo = L.mol_start[m + 1], hi = L.mol_start[m + 2];
+        if ((mol != 7 || !((L.lc_mask >> 7) & 1ull)) && ((L.sorted_mask >> mol) & 1ull)) {
+            const double pad = L.max_abs_shift * 1.0 + 1e-6;
+            const double vlo = swn[0] - 25.0 - pad, vhi = swn[63] + 25.0 + pad;
+            int l0 = lo, l1 = hi;
+            while (l0 < l1) { const int mid = (l0 + l1) >> 1; if (L.vnu[mid] < vlo) l0 = mid + 1; else l1 = mid; }
+            const int first = l0;
+            l1 = hi;
+            while (l0 < l1) { const int mid = (l0 + l1) >> 1; if (L.vnu[mid] <= vhi) l0 = mid + 1; else l1 = mid; }
+            lo = first;
+            hi = l0;
+        }
+        sLo[m] = (hi > lo) ? lo : 0x7fffffff;
+        sOff[m + 1] = (hi > lo) ? hi - lo : 0;
+    }
+    ms_sync();
+    if (lane == 0) {
+        int acc = 0;
+        sOff[0] = 0;
+        for (int m = 0; m < nmol; m++) { acc += sOff[m + 1]; sOff[m + 1] = acc; }
+    }
+    ms_sync();
+    const int total = sOff[nmol], base = ck * CL;
+    if (ck == 0) {
+        int *pi = reinterpret_cast<int *>(plan);
+        if (lane < nmol) pi[lane] = sLo[lane];
+        if (lane <= nmol) pi[MS_PLAN_OFF + lane] = sOff[lane];
+    }
+    if (base >= total) return;   // (no wave walks a chunk there)
+    const bool lin = lane < CL && base + lane < total;
+    unsigned r = 0u;
+    bool plain = true, beyond = false;
+    if (lin) {
+        const int v = base + lane;
+        int m = 0;
+        while (sOff[m + 1] <= v) m++;
+        const int idx = sLo[m] + (v - sOff[m]);
+        const uint32_t meta = L.meta[idx];
+        const double x = L.vnu[idx];
+        plain = ((meta >> 10) & 3u) == 0u && ((meta >> 13) & 3u) == 0u;
+        beyond = m >= MXBRD;
+        const bool every = ((meta & 63u) == 7u && ((meta >> 10) & 3u)) || !(x == x);
+        r = ms_reach_word(swn, nwn, LPS, x, every, ms_reach_pad(L.max_abs_shift));   // (the word ms_reach_kernel stores for the line)
+    }
+    unsigned long long *pc = plan + MS_PLAN_HEAD + (size_t)MS_PLAN_CHUNK * (size_t)ck;
+    const unsigned long long np = __builtin_amdgcn_ballot_w64(lin && !plain), nb = __builtin_amdgcn_ballot_w64(lin && beyond);
+    if (lane == 0) {
+        pc[0] = (np == 0ull ? 1ull : 0ull) | (nb != 0ull ? 2ull : 0ull);
+        pc[1] = 0ull;
+    }
+#pragma unroll
+    for (int k = 0; k < WPS; k++) {
+        const unsigned long long rk = __builtin_amdgcn_ballot_w64((r >> k) & 1u), qk = __builtin_amdgcn_ballot_w64((r >> (8 + k)) & 1u);
+        if (lane == 0) { pc[2 + k] = rk; pc[2 + WPS + k] = qk; }
+    }
+}
+
+__global__ void ms_reach_kernel(const double *wn, int nwn, int LPS, DevLines L, int nlines, unsigned short *reach, float *near0, int reach_blocks,
+                                int nmol, int CL, unsigned long long *plan) {
     // (the channels - at most 64 where this kernel runs - through LDS: the search below is a chain of dependent reads)
     __shared__ double swn[64];
+    __shared__ int pLo[4][MXMOL], pOff[4][MXMOL + 1];
     if (threadIdx.x < 64) swn[threadIdx.x] = wn[min((int)threadIdx.x, max(nwn, 1) - 1)];
     __syncthreads();
     wn = swn;
     nwn = min(nwn, 64);
+    if ((int)blockIdx.x >= reach_blocks) {   // (whole blocks: the waves of a block take the same side)
+        ms_plan_wave(swn, nwn, LPS, L, nmol, CL, ((int)blockIdx.x - reach_blocks) * 4 + ((int)threadIdx.x >> 6), (nlines + CL - 1) / CL, plan, pLo, pOff);
+        return;
+    }
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nlines) return;
     const uint32_t meta = L.meta[idx];
@@ -763,8 +916,14 @@ __global__ __launch_bounds__(64, 4) void lines_ms_kernel(ModmArgs a, DevLines L,
             tk.tips_qoft != tb.tips_qoft || tk.smass != tb.smass || mk.scratch != ms.scratch || mk.inv_cl != ms.inv_cl || mk.spp != ms.spp || mk.slot_base != ms.slot_base)
             atomicOr(a.errflag, ERRBIT_ARG);
     }
-    const int total = __builtin_amdgcn_readfirstlane(ms_prologue(&sKseg, lay, pg));
-    if (total < 0) return;
+    const int total_m = __builtin_amdgcn_readfirstlane(ms_prologue(&sKseg, lay, pg));
+    if (total_m < 0) return;
+    const int total = total_m & (MS_MATCH_BIT - 1);
+    const bool match = (total_m & MS_MATCH_BIT) != 0;   // the wave takes its windows and its plain chunks' words from the chunk plan
+#ifdef MONORTM_EXPERIMENT
+    unsigned long long *plan_cnt = ms.plan + MS_PLAN_CNT;   // (waves, waves that match, chunks, chunks on the fast path)
+    if (ms.plan_on && threadIdx.x == 0) { atomicAdd(plan_cnt, 1ull); if (match) atomicAdd(plan_cnt + 1, 1ull); }
+#endif
 #ifdef MONORTM_EXPERIMENT   // timing experiments (wrong results): tools/build_variant.sh
     if (ms.ablate == 1) return;
 #endif
@@ -797,22 +956,43 @@ __global__ __launch_bounds__(64, 4) void lines_ms_kernel(ModmArgs a, DevLines L,
         const MsLds ld = ms_lds(dyn_lds, G, mc.sa_stride, nmol, mc.nslot, const_cast<double *>(gR) + WPS * 64);
         while (mchunk + 1 < nmol && ld.sOff[mchunk + 1] <= base) mchunk++;
         mchunk = __builtin_amdgcn_readfirstlane(mchunk);
-        ms_prepare<IBRD>(&sKseg, base, mchunk, total, gB, gC);
+        const bool fast = ms_prepare<IBRD>(&sKseg, base, mchunk, total, gB, gC, ck, match);
 
         // ================= evaluate: molecule by molecule, in file order ================================================================
         // The lane's role in this stage - state se, channels ce + LPS k - is formed where it is used (ms_lane: a handful of
         // instructions on an opaque lane id), not once per chunk: values that live across a run's walk are spilled around the
         // 48 fixed registers of the class loops.
 #ifdef MONORTM_EXPERIMENT
-        if (mc.ablate == 2) continue;
+        if (mc.ablate == 2 || mc.ablate == 6) continue;
+#endif
+#ifdef MONORTM_EXPERIMENT
+        if (mc.plan_on && threadIdx.x == 0) { atomicAdd(mc.plan + MS_PLAN_CNT + 2, 1ull); if (fast) atomicAdd(mc.plan + MS_PLAN_CNT + 3, 1ull); }
 #endif
         MsSpec sp;
+        const unsigned long long NT = uni64(ld.sMask[0]), M2 = uni64(ld.sMask[1]);
+        unsigned long long V = 0ull, Y = 0ull, RS[WPS], QS[WPS];
+        if (fast) {
+            // a plain chunk of a wave that matches the plan: no rare shape (V, Y and the passes' words are zero), the slot words from
+            // the plan by scalar loads
+            const ms_plan_t pc = ms_plan_chunk(mc, ck);
 #pragma unroll
-        for (int t = 0; t < MS_MAXSTEPS; t++) sp.w[t] = uni64(ld.sMask[4 + t]);
-        const unsigned long long NT = uni64(ld.sMask[0]), M2 = uni64(ld.sMask[1]), V = uni64(ld.sMask[2]), Y = uni64(ld.sMask[3]);
-        unsigned long long RS[WPS], QS[WPS];
+            for (int t = 0; t < MS_MAXSTEPS; t++) sp.w[t] = 0ull;
 #pragma unroll
-        for (int k = 0; k < WPS; k++) { RS[k] = uni64(ld.sMask[4 + MS_MAXSTEPS + k]); QS[k] = uni64(ld.sMask[4 + MS_MAXSTEPS + WPS + 1 + k]); }
+            for (int k = 0; k < WPS; k++) {
+                // (one 64-bit load per word through an opaque address: merged into wide loads they ask for aligned runs of 8 or 16
+                // scalar registers at the one place where the kernel has none to spare)
+                ms_plan_t pr = pc + 2 + k, pq = pc + 2 + WPS + k;
+                asm volatile("" : "+s"(pr), "+s"(pq));
+                RS[k] = *pr;
+                QS[k] = *pq;
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < MS_MAXSTEPS; t++) sp.w[t] = uni64(ld.sMask[4 + t]);
+            V = uni64(ld.sMask[2]); Y = uni64(ld.sMask[3]);
+#pragma unroll
+            for (int k = 0; k < WPS; k++) { RS[k] = uni64(ld.sMask[4 + MS_MAXSTEPS + k]); QS[k] = uni64(ld.sMask[4 + MS_MAXSTEPS + WPS + 1 + k]); }
+        }
         for (int m = mchunk; m < nmol; m++) {
             const int o0 = __builtin_amdgcn_readfirstlane(ld.sOff[m]), o1 = __builtin_amdgcn_readfirstlane(ld.sOff[m + 1]);
             if (o1 <= base || o0 >= o1) continue;
@@ -875,10 +1055,16 @@ static_assert(sizeof(HotA) == MS_HOTA_BYTES, "lines_ms_lds (modm_plan.hpp) sizes
 size_t lines_ms_scratch(const MsArgs &ms, long long nwg) { return (size_t)nwg * ms_scratch_per_wg(ms.G, ms.CL); }
 void launch_lines_ms(const ModmArgs &a, const DevLines &L, const DevTables &tb, const MsArgs &ms, bool ibrd, hipStream_t s) {
     const int nlines = L.mol_start[MXMOL + 1];
-    if (nlines > 0) hipLaunchKernelGGL(ms_reach_kernel, dim3((nlines + 255) / 256), dim3(256), 0, s, a.wn, a.nwn, ms.LPS, L, nlines, ms.reach, ms.near0);
+    // (the chunk plan in the same launch: one wave per possible chunk of CL candidates, four to a block, behind the table's blocks)
+    const int reach_blocks = (nlines + 255) / 256, plan_blocks = (ms.plan_on && ms.plan) ? ((nlines + ms.CL - 1) / ms.CL + 3) / 4 : 0;
+    if (nlines > 0)
+        hipLaunchKernelGGL(ms_reach_kernel, dim3(reach_blocks + plan_blocks), dim3(256), 0, s, a.wn, a.nwn, ms.LPS, L, nlines, ms.reach, ms.near0, reach_blocks,
+                           a.nmol, ms.CL, ms.plan);
     const dim3 grid((unsigned)(ms.npg * a.nlay_max));
     const size_t lds = lines_ms_lds(ms, a.nmol);
-    if (ibrd) hipLaunchKernelGGL((lines_ms_kernel<true>), grid, dim3(64), lds, s, a, L, tb, ms);
-    else hipLaunchKernelGGL((lines_ms_kernel<false>), grid, dim3(64), lds, s, a, L, tb, ms);
+    MsArgs mk = ms;
+    mk.plan_on = (nlines > 0 && plan_blocks > 0) ? 1 : 0;   // (no plan written: no wave looks for one)
+    if (ibrd) hipLaunchKernelGGL((lines_ms_kernel<true>), grid, dim3(64), lds, s, a, L, tb, mk);
+    else hipLaunchKernelGGL((lines_ms_kernel<false>), grid, dim3(64), lds, s, a, L, tb, mk);
 }
 }  // namespace monortm_dev
