@@ -258,7 +258,8 @@ int monortm_hip_rtm_scan_dev(void *ctx, int nprof, int npath, int nwn, const dou
 #define MONORTM_JAC_DLNW 1e-4 /* WKL (1 +- eps) */
 /* O is only piecewise smooth in T (line-shape switches at zeta > 0.99 and |v - v0| > 100 HWHM_D, src/modm.f90:427): a difference
  * across a switch reports the switch.  T +- h must stay within 70-3000 K (MONORTM_ETEMP otherwise).
- * Cross-section molecules (IXSECT = 1) are not part of monortm_hip_jacobian: chain K_O with their dO.
+ * Cross-section molecules (IXSECT = 1): the *_xs entries below (monortm_hip_jacobian_xs, _scan_jacobian_xs, _obs_jacobian_xs and
+ * their _dev variants) - DESIGN.md section 3.12.
  *
  * Jacobian variables: an entry of jac_mol[] is a 1-based molecule (1..nmol) or one of the codes below, in any
  * mix; slot i of K_W belongs to jac_mol[i].  eps is the "jac_dlnw" half-step for every one of them.
@@ -267,13 +268,18 @@ int monortm_hip_rtm_scan_dev(void *ctx, int nprof, int npath, int nwn, const dou
  *   scalar      MONORTM_JVAR_CNTNM0 + i (cntnm_fac[i], i = 0..6: XSELF, XFRGN, XCO2C, XO3CN, XO2CN, XN2CN, XRAYL), _SCLCPL, _SCLHW,
  *               _Y0RES: the argument +- eps (additive); slot [k] holds the part of dq/dtheta that acts through layer k, and the SUM
  *               of the slots over the layers is dq/dtheta.  MODM switches a continuum off at a factor <= 0, so where fac - eps <= 0
- *               the difference is one-sided, (O(fac + 2 eps) - O(fac)) / (2 eps): exact as well, O being linear in the factor. */
+ *               the difference is one-sided, (O(fac + 2 eps) - O(fac)) / (2 eps): exact as well, O being linear in the factor.
+ *   per layer   MONORTM_JVAR_XS0 + x, x = 0 .. nxs - 1: cross-section molecule x - the 0-based position in the cross-section request,
+ *               i.e. the `molecule` column of monortm_hip_xsec_tables and the second axis of XAMNT (at most 38, MX_XS).  The *_xs
+ *               entries with ixsect = 1 only.  The slot holds dq/d ln XAMNT_k,x, exactly 0 where XAMNT = 0; O is linear in XAMNT, so
+ *               this is K_O times the molecule's own term and nothing is differenced. */
 #define MONORTM_JVAR_P 1001
 #define MONORTM_JVAR_WBROD 1002
 #define MONORTM_JVAR_CNTNM0 1011 /* + i, i = 0..6 */
 #define MONORTM_JVAR_SCLCPL 1021
 #define MONORTM_JVAR_SCLHW 1022
 #define MONORTM_JVAR_Y0RES 1023
+#define MONORTM_JVAR_XS0 (1101) /* + x, x = 0 .. nxs - 1: the base of a family of codes, not a variable of its own */
 /*
  * RTM adjoint only, given O (e.g. from monortm_hip_modm): RAD, TB, K_O, K_T (Planck terms only), K_TZ, K_SFC.  real_kind 8 and 4
  * (double arithmetic either way).  Host buffers; a multi-device context shards the profiles like monortm_hip_rtm. */
@@ -344,8 +350,8 @@ int monortm_hip_rtm_scan_jac_dev(void *ctx, int nprof, int npath, int nwn, const
 
 /* MODM + RTM with Jacobians along npath paths: the 3 + 2 njac MODM passes of monortm_hip_jacobian ONCE (their differences do not depend
  * on the path), then one adjoint launch for all paths.  O returns the vertical optical depths.  real_kind 8 only
- * (MONORTM_EUNSUPPORTED otherwise); jac_mol, the half-steps and the errors as monortm_hip_jacobian, the factors as above; no
- * cross-section molecules. */
+ * (MONORTM_EUNSUPPORTED otherwise); jac_mol, the half-steps and the errors as monortm_hip_jacobian, the factors as above.  Cross-section
+ * molecules: monortm_hip_scan_jacobian_xs. */
 int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
                               int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
                               const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac, double sclcpl,
@@ -418,7 +424,8 @@ int monortm_hip_rtm_obs_jac_dev(void *ctx, int nprof, int npath, int nwn, const 
 
 /* MODM + RTM with Jacobians per measurement: the 3 + 2 njac MODM passes of monortm_hip_jacobian ONCE, then one launch of the contracting
  * adjoint.  O returns the vertical optical depths exactly as monortm_hip_scan_jacobian does.  real_kind 8 only (MONORTM_EUNSUPPORTED
- * otherwise); jac_mol, the half-steps, the factors and the errors as monortm_hip_scan_jacobian; no cross-section molecules. */
+ * otherwise); jac_mol, the half-steps, the factors and the errors as monortm_hip_scan_jacobian.  Cross-section molecules:
+ * monortm_hip_obs_jacobian_xs. */
 int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
                              int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
                              const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac, double sclcpl,
@@ -439,6 +446,77 @@ int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn
                                  int sfc_per_path, int obs, monortm_real *O, monortm_real *Y, monortm_real *K_T,
                                  monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_SFC,
                                  const double *wn_ends, void *stream);
+
+/* ---- The Jacobians with the cross-section molecules (IXSECT = 1; no reference counterpart).  DESIGN.md section 3.12.
+ * The six entries above with two more arguments behind ibrd, as monortm_hip_modm_xs has them: ixsect and XAMNT [nprof][nlay_max][nxs]
+ * (read with ixsect = 1 only).  With ixsect = 0 they ARE the entries above (which call them), bit for bit.  With ixsect = 1:
+ *   O, K_O and through them every slot include the cross sections: O is what monortm_hip_modm_xs returns.
+ *   K_T and the MONORTM_JVAR_P slot include the cross sections' own dependence on T and P.  MONORTM_XSEC_SUB resamples every spectrum
+ *   on a grid whose point count, and a handful of branches besides, jump with P and T, so its ODXSEC is not differentiable as it
+ *   stands; the derivative here is that of the BASE state's finite sum - grid, temperature bracket, branches and stopping trip held
+ *   as the base state has them - evaluated at T +- h, P (1 +- eps) (xsec_jac_kernel.hip).  A layer exactly at a table temperature
+ *   takes the bracket the reference's `tave <= tx` picks: the derivative is one-sided there.
+ *   MONORTM_JVAR_XS0 + x names molecule x of the request as a Jacobian variable (table above).
+ *   States of molecules, WBRODL and the scalars are differenced without the cross sections, which would cancel.
+ *   Along a scan a path factor multiplies XAMNT like every other amount; K is with respect to the batch's own vertical XAMNT.
+ * Refused before anything is launched: real_kind 4 (MONORTM_EUNSUPPORTED); ixsect outside 0, 1, a MONORTM_JVAR_XS0 code with
+ * ixsect = 0 or with x >= the nxs of the context's tables, ixsect = 1 without tables (monortm_hip_xsec_tables) or with XAMNT NULL
+ * (MONORTM_EARG).  njac <= 39 as ever.  Host entries shard by profile as their parents do. */
+int monortm_hip_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
+                            int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW, const
+                            monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac, double sclcpl, double
+                            sclhw, double y0res, int ibrd, int ixsect, const monortm_real *XAMNT, const int *irt, const
+                            monortm_real *TZ, const monortm_real *tmpsfc, const monortm_real *emiss, const monortm_real
+                            *reflc, int quantity, int njac, const int *jac_mol, monortm_real *O, monortm_real *RAD,
+                            monortm_real *TB, monortm_real *K_T, monortm_real *K_TZ, monortm_real *K_W, monortm_real
+                            *K_CLW, monortm_real *K_O, monortm_real *K_SFC);
+int monortm_hip_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int
+                                nlay_max, int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
+                                const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac /*host*/,
+                                double sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const monortm_real
+                                *XAMNT, const int *irt, const monortm_real *TZ, const monortm_real *tmpsfc, const
+                                monortm_real *emiss, const monortm_real *reflc, int quantity, int njac, const int *jac_mol
+                                /*host*/, monortm_real *O, monortm_real *RAD, monortm_real *TB, monortm_real *K_T,
+                                monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_O,
+                                monortm_real *K_SFC, const double *wn_ends, void *stream);
+int monortm_hip_scan_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int
+                                 nlay_max, int nmol, const monortm_real *P, const monortm_real *T, const monortm_real
+                                 *CLW, const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac,
+                                 double sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const monortm_real
+                                 *XAMNT, const int *irt, const monortm_real *TZ, const monortm_real *tmpsfc, const
+                                 monortm_real *emiss, const monortm_real *reflc, int quantity, int njac, const int
+                                 *jac_mol, int npath, const monortm_real *path, int sfc_per_path, monortm_real *O,
+                                 monortm_real *RAD, monortm_real *TB, monortm_real *K_T, monortm_real *K_TZ, monortm_real
+                                 *K_W, monortm_real *K_CLW, monortm_real *K_O, monortm_real *K_PATH, monortm_real *K_SFC);
+int monortm_hip_scan_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int
+                                     nlay_max, int nmol, const monortm_real *P, const monortm_real *T, const monortm_real
+                                     *CLW, const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac
+                                     /*host*/, double sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const
+                                     monortm_real *XAMNT, const int *irt, const monortm_real *TZ, const monortm_real
+                                     *tmpsfc, const monortm_real *emiss, const monortm_real *reflc, int quantity, int
+                                     njac, const int *jac_mol /*host*/, int npath, const monortm_real *path, int
+                                     sfc_per_path, monortm_real *O, monortm_real *RAD, monortm_real *TB, monortm_real
+                                     *K_T, monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_O,
+                                     monortm_real *K_PATH, monortm_real *K_SFC, const double *wn_ends, void *stream);
+int monortm_hip_obs_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int
+                                nlay_max, int nmol, const monortm_real *P, const monortm_real *T, const monortm_real *CLW,
+                                const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac, double
+                                sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const monortm_real *XAMNT, const
+                                int *irt, const monortm_real *TZ, const monortm_real *tmpsfc, const monortm_real *emiss,
+                                const monortm_real *reflc, int quantity, int njac, const int *jac_mol, int npath, const
+                                monortm_real *path, int sfc_per_path, int obs, monortm_real *O, monortm_real *Y,
+                                monortm_real *K_T, monortm_real *K_TZ, monortm_real *K_W, monortm_real *K_CLW,
+                                monortm_real *K_SFC);
+int monortm_hip_obs_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int
+                                    nlay_max, int nmol, const monortm_real *P, const monortm_real *T, const monortm_real
+                                    *CLW, const monortm_real *WKL, const monortm_real *WBRODL, const double *cntnm_fac
+                                    /*host*/, double sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const
+                                    monortm_real *XAMNT, const int *irt, const monortm_real *TZ, const monortm_real
+                                    *tmpsfc, const monortm_real *emiss, const monortm_real *reflc, int quantity, int njac,
+                                    const int *jac_mol /*host*/, int npath, const monortm_real *path, int sfc_per_path,
+                                    int obs, monortm_real *O, monortm_real *Y, monortm_real *K_T, monortm_real *K_TZ,
+                                    monortm_real *K_W, monortm_real *K_CLW, monortm_real *K_SFC, const double *wn_ends,
+                                    void *stream);
 
 /* ---- The forward measurement operator: channel- and beam-averaged scans, y = F(x) without K (no reference counterpart; the radiance
  * recurrence along every path is RTM's, src/RTMmono.f90:13-221).  DESIGN.md section 3.10.

@@ -67,9 +67,17 @@ SYMBOLS = {
     "monortm_hip_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                        C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]
                              + [_vp] * 9),
+    "monortm_hip_jacobian_xs": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                              C.c_int, _vp]
+                                + [_vp] * 9),
     "monortm_hip_jacobian_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                            C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]
                                  + [_vp] * 11),
+    "monortm_hip_jacobian_xs_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                              C.c_int, _vp]
+                                    + [_vp] * 11),
     "monortm_hip_rtm_scan_jac": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int]
                                  + [_vp] * 9),
     "monortm_hip_rtm_scan_jac_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp,
@@ -77,9 +85,17 @@ SYMBOLS = {
     "monortm_hip_scan_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                             C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
                                             C.c_int, _vp, C.c_int] + [_vp] * 10),
+    "monortm_hip_scan_jacobian_xs": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                              C.c_int, _vp,
+                                               C.c_int, _vp, C.c_int] + [_vp] * 10),
     "monortm_hip_scan_jacobian_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
                                                 C.c_int, _vp, C.c_int] + [_vp] * 12),
+    "monortm_hip_scan_jacobian_xs_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                              C.c_int, _vp,
+                                                   C.c_int, _vp, C.c_int] + [_vp] * 12),
     "monortm_hip_obs_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _ip]),
     "monortm_hip_obs_destroy": (C.c_int, [_vp, C.c_int]),
     "monortm_hip_rtm_obs_jac": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int,
@@ -89,9 +105,17 @@ SYMBOLS = {
     "monortm_hip_obs_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                            C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
                                            C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 7),
+    "monortm_hip_obs_jacobian_xs": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                              C.c_int, _vp,
+                                              C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 7),
     "monortm_hip_obs_jacobian_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                                C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
                                                C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 9),
+    "monortm_hip_obs_jacobian_xs_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                              C.c_int, _vp,
+                                                  C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 9),
     "monortm_hip_rtm_obs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int,
                                       _vp, _vp, C.c_int, _vp, _vp]),
     "monortm_hip_rtm_obs_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int,
@@ -117,14 +141,23 @@ JAC_DLNW = 1e-4
 # ln WBRODL per layer, and the scalar arguments of MODM - the seven continuum factors, SCLCPL, SCLHW, Y0RES
 JAC_VARS = {"p": 1001, "wbrod": 1002, "xself": 1011, "xfrgn": 1012, "xco2c": 1013, "xo3cn": 1014, "xo2cn": 1015, "xn2cn": 1016,
             "xrayl": 1017, "sclcpl": 1021, "sclhw": 1022, "y0res": 1023}
+# ... and the cross-section molecules: JVAR_XS0 + x, x the 0-based position in the cross-section request
+# (Profile.xs_names, the second axis of xamnt); "xs:<NAME>" in mols= of the MonoRTM Jacobian calls with ixsect = 1
+JVAR_XS0 = 1101
 
 
-def jac_codes(seq) -> np.ndarray:
+def jac_codes(seq, xs_names=None) -> np.ndarray:
     """The `mols=` argument of the Jacobian calls as the int32 codes of the C ABI: ints (1-based molecules, or codes) pass through,
-    names are looked up in JAC_VARS (case-insensitive); an unknown name raises ValueError."""
+    names are looked up in JAC_VARS (case-insensitive); an unknown name raises ValueError.  "xs:<NAME>" is the cross-section
+    molecule NAME of xs_names (the cross-section request, case-insensitive): JVAR_XS0 + its position."""
     out = []
     for v in ([seq] if isinstance(seq, (str, int, np.integer)) else seq):
-        if isinstance(v, str):
+        if isinstance(v, str) and v.lower().startswith("xs:"):
+            names = [n.strip().upper() for n in (xs_names or [])]
+            if v[3:].strip().upper() not in names:
+                raise ValueError(f"unknown cross-section molecule {v!r}: the request holds {names}")
+            v = JVAR_XS0 + names.index(v[3:].strip().upper())
+        elif isinstance(v, str):
             if v.lower() not in JAC_VARS:
                 raise ValueError(f"unknown Jacobian variable {v!r}: a 1-based molecule or one of {sorted(JAC_VARS)}")
             v = JAC_VARS[v.lower()]
@@ -577,13 +610,35 @@ class MonoRTM:
                                                                                                   ("rad", "tb", "k_o", "k_t", "k_tz", "k_sfc")]))
         return out
 
-    def jacobian(self, profiles: list[Profile], mols=(1,), quantity="tb") -> dict:
+    def _jac_xs(self, profiles: list[Profile], ixsect: int, xs_entry: bool, lm: int):
+        """What ixsect adds to a full Jacobian call: (suffix of the entry's name, the arguments behind ibrd, the packed xamnt).
+        ixsect = 1 packs xamnt as modm() does and takes the *_xs entry; ixsect = 0 takes the entry without cross sections, or -
+        xs_entry - the *_xs entry with ixsect = 0, which is the same computation."""
+        if ixsect not in (0, 1):
+            raise ValueError("ixsect must be 0 or 1")
+        if ixsect == 0:
+            return ("_xs", (0, None), None) if xs_entry else ("", (), None)
+        p0 = profiles[0]
+        if p0.xs_names and p0.xs_dir:   # (as modm(): the tables of the call's wavenumber range)
+            from . import xsec
+
+            self.set_xsec(xsec.load_tables(p0.xs_dir, p0.xs_names, float(p0.wn.min()), float(p0.wn.max())))
+        names = p0.xs_names or []
+        XA = np.zeros((len(profiles), lm, len(names)), self.dtype)
+        for i, p in enumerate(profiles):
+            XA[i, : p.nlay] = p.xamnt
+        return "_xs", (1, _ptr(XA)), XA
+
+    def jacobian(self, profiles: list[Profile], mols=(1,), quantity="tb", ixsect: int = 0, xs_entry: bool = False) -> dict:
         """MODM + RTM with Jacobians for a batch (real_kind 8): dict of o [nprof, nlay_max, nwn], rad, tb [nprof, nwn], k_t, k_clw, k_o
         [nprof, nlay_max, nwn], k_tz [nprof, nlay_max + 1, nwn], k_w [nprof, nlay_max, len(mols), nwn] (d/d ln WKL of mols, 1-based)
         and k_sfc [nprof, 3, nwn].  Partial derivatives with respect to the MODM / RTM inputs (see include/monortm_hip.h).
         mols may mix molecules with the names (or codes) of JAC_VARS: "p", "wbrod" (d/d ln P_k, d/d ln WBRODL_k) and the scalars
         "xself" .. "xrayl", "sclcpl", "sclhw", "y0res", whose k_w slot summed over the layers is dq/dtheta (DESIGN.md section 3.11);
-        vars holds the codes in slot order.  The same holds for scan_jacobian, obs_jacobian and the DeviceBatch calls."""
+        vars holds the codes in slot order.  The same holds for scan_jacobian, obs_jacobian and the DeviceBatch calls.
+        ixsect = 1 (the tables are those of set_xsec): o, k_o and every slot include the cross-section
+        molecules, k_t and the "p" slot their own T and P dependence, and mols accepts "xs:<NAME>" (a name of profiles[0].xs_names)
+        or JVAR_XS0 + x: d/d ln XAMNT of that molecule.  Likewise for scan_jacobian and obs_jacobian; not for DeviceBatch."""
         p0 = profiles[0]
         nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
         nmol, dt = p0.nmol, self.dtype
@@ -596,14 +651,16 @@ class MonoRTM:
 
         P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
         WKL = pack(lambda p: p.wkl, nmol)
-        jm = jac_codes(mols)
+        jm = jac_codes(mols, p0.xs_names)
+        sfx, xargs, _xa = self._jac_xs(profiles, ixsect, xs_entry, lm)   # (_xa: xamnt, alive during the call)
         nj = len(jm)
         out = dict(o=np.zeros((nprof, lm, nwn), dt), rad=np.zeros((nprof, nwn), dt), tb=np.zeros((nprof, nwn), dt),
                    k_t=np.zeros((nprof, lm, nwn), dt), k_tz=np.zeros((nprof, lm + 1, nwn), dt), k_w=np.zeros((nprof, lm, nj, nwn), dt),
                    k_clw=np.zeros((nprof, lm, nwn), dt), k_o=np.zeros((nprof, lm, nwn), dt), k_sfc=np.zeros((nprof, 3, nwn), dt))
         wn, fac = _np(p0.wn), _np(p0.cntnm)
-        self._chk(self.lib.monortm_hip_jacobian(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T), _ptr(CLW),
-                                                _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, _ptr(irt), _ptr(TZ),
+        self._chk(getattr(self.lib, "monortm_hip_jacobian" + sfx)(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T),
+                _ptr(CLW),
+                                                _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, *xargs, _ptr(irt), _ptr(TZ),
                                                 _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj, _ptr(jm) if nj else None,
                                                 *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS]))
         out["vars"] = jm
@@ -638,7 +695,8 @@ class MonoRTM:
                                                     *[_ptr(out[k]) for k in SCAN_JAC_RTM_FIELDS]))
         return out
 
-    def scan_jacobian(self, profiles: list[Profile], path, mols=(1,), quantity="tb", emiss=None, reflc=None) -> dict:
+    def scan_jacobian(self, profiles: list[Profile], path, mols=(1,), quantity="tb", emiss=None, reflc=None, ixsect: int = 0,
+                      xs_entry: bool = False) -> dict:
         """MODM (the base and the perturbed states of jacobian(), ONCE) + RTM with Jacobians along npath paths per profile (real_kind
         8): the fields of rtm_scan_jacobian with the optical-depth term in k_t, plus o [nprof, nlay_max, nwn] (the vertical optical
         depths), k_w [nprof, npath, nlay_max, len(mols), nwn] and k_clw [nprof, npath, nlay_max, nwn] - derivatives with respect to
@@ -658,14 +716,16 @@ class MonoRTM:
 
         P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
         WKL = pack(lambda p: p.wkl, nmol)
-        jm = jac_codes(mols)
+        jm = jac_codes(mols, p0.xs_names)
+        sfx, xargs, _xa = self._jac_xs(profiles, ixsect, xs_entry, lm)   # (_xa: xamnt, alive during the call)
         nj = len(jm)
         z = lambda *s: np.zeros((nprof, npath) + s, dt)  # noqa: E731
         out = dict(o=np.zeros((nprof, lm, nwn), dt), rad=z(nwn), tb=z(nwn), k_t=z(lm, nwn), k_tz=z(lm + 1, nwn), k_w=z(lm, nj, nwn),
                    k_clw=z(lm, nwn), k_o=z(lm, nwn), k_path=z(lm, nwn), k_sfc=z(3, nwn))
         wn, fac = _np(p0.wn), _np(p0.cntnm)
-        self._chk(self.lib.monortm_hip_scan_jacobian(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T),
-                                                     _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd,
+        self._chk(getattr(self.lib, "monortm_hip_scan_jacobian" + sfx)(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P),
+                _ptr(T),
+                                                     _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, *xargs,
                                                      _ptr(irt), _ptr(TZ), _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj,
                                                      _ptr(jm) if nj else None, npath, _ptr(f), int(em.ndim == 3),
                                                      *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS]))
@@ -713,7 +773,8 @@ class MonoRTM:
                                                    int(obs), *[_ptr(out[k]) for k in OBS_JAC_RTM_FIELDS]))
         return out
 
-    def obs_jacobian(self, profiles: list[Profile], path, obs: int, mols=(1,), quantity="tb", emiss=None, reflc=None) -> dict:
+    def obs_jacobian(self, profiles: list[Profile], path, obs: int, mols=(1,), quantity="tb", emiss=None, reflc=None, ixsect: int = 0,
+                     xs_entry: bool = False) -> dict:
         """MODM (the base and the perturbed states of jacobian(), ONCE) + RTM with Jacobians per measurement (real_kind 8): the fields
         of rtm_obs_jacobian with the optical-depth term in k_t, plus o [nprof, nlay_max, nwn] (the vertical optical depths, as
         scan_jacobian returns them), k_w [nprof, nview, nlay_max, len(mols), nchan] and k_clw [nprof, nview, nlay_max, nchan]."""
@@ -732,14 +793,16 @@ class MonoRTM:
 
         P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
         WKL = pack(lambda p: p.wkl, nmol)
-        jm = jac_codes(mols)
+        jm = jac_codes(mols, p0.xs_names)
+        sfx, xargs, _xa = self._jac_xs(profiles, ixsect, xs_entry, lm)   # (_xa: xamnt, alive during the call)
         nj = len(jm)
         nv, nc = self._obs_shape(obs)
         z = lambda *s: np.zeros((nprof, nv) + s + (nc,), dt)  # noqa: E731
         out = dict(o=np.zeros((nprof, lm, nwn), dt), y=z(), k_t=z(lm), k_tz=z(lm + 1), k_w=z(lm, nj), k_clw=z(lm), k_sfc=z(3))
         wn, fac = _np(p0.wn), _np(p0.cntnm)
-        self._chk(self.lib.monortm_hip_obs_jacobian(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T),
-                                                    _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd,
+        self._chk(getattr(self.lib, "monortm_hip_obs_jacobian" + sfx)(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P),
+                _ptr(T),
+                                                    _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, *xargs,
                                                     _ptr(irt), _ptr(TZ), _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj,
                                                     _ptr(jm) if nj else None, npath, _ptr(f), int(em.ndim == 3), int(obs),
                                                     *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS]))

@@ -507,15 +507,36 @@ bool jac_var_scalar(int v) {
     return (v >= MONORTM_JVAR_CNTNM0 && v < MONORTM_JVAR_CNTNM0 + 7) || v == MONORTM_JVAR_SCLCPL || v == MONORTM_JVAR_SCLHW || v == MONORTM_JVAR_Y0RES;
 }
 bool jac_var_layer(int v, int nmol) { return (v >= 1 && v <= nmol) || v == MONORTM_JVAR_P || v == MONORTM_JVAR_WBROD; }
-int jac_check_mol(Ctx *c, int nmol, int njac, const int *jac_mol, const void *K_W) {
+constexpr int kMaxXs = 38;   // MX_XS: molecules of a cross-section request (monortm_hip_xsec_tables)
+bool jac_var_xs(int v) { return v >= MONORTM_JVAR_XS0 && v < MONORTM_JVAR_XS0 + kMaxXs; }
+// cross-section molecules of the context's tables (every shard of a multi-device context holds the same tables)
+int ctx_nxs(const Ctx *c) { return (c->shards.empty() ? c : c->shards[0])->xs.nxs; }
+// ixsect, XAMNT: the two arguments of the *_xs entries (the entries without them pass 0, nullptr: a cross-section code is refused)
+int jac_check_mol(Ctx *c, int nmol, int njac, const int *jac_mol, const void *K_W, int ixsect, const void *XAMNT) {
     if (njac < 0 || njac > MXMOL || (njac > 0 && (!jac_mol || !K_W))) { c->err = "njac outside 0..39, or jac_mol / K_W missing"; return MONORTM_EARG; }
+    if (ixsect != 0 && ixsect != 1) { c->err = "ixsect must be 0 or 1"; return MONORTM_EARG; }
+    const int nxs = ctx_nxs(c);
     for (int i = 0; i < njac; i++) {
-        if (!jac_var_layer(jac_mol[i], nmol) && !jac_var_scalar(jac_mol[i])) {
+        if (jac_var_xs(jac_mol[i])) {
+            if (ixsect == 0) {
+                c->err = "jac_mol[" + std::to_string(i) + "] is a cross-section molecule (MONORTM_JVAR_XS0 + x): that needs ixsect = 1 (the *_xs entries)";
+                return MONORTM_EARG;
+            }
+            if (jac_mol[i] - MONORTM_JVAR_XS0 >= nxs) {
+                c->err = "jac_mol[" + std::to_string(i) + "]: cross-section molecule " + std::to_string(jac_mol[i] - MONORTM_JVAR_XS0) +
+                         " is not among the " + std::to_string(nxs) + " of this context's tables";
+                return MONORTM_EARG;
+            }
+        } else if (!jac_var_layer(jac_mol[i], nmol) && !jac_var_scalar(jac_mol[i])) {
             c->err = "jac_mol[" + std::to_string(i) + "] neither a molecule 1..nmol nor a MONORTM_JVAR_* code";
             return MONORTM_EARG;
         }
         for (int j = 0; j < i; j++)
             if (jac_mol[j] == jac_mol[i]) { c->err = "jac_mol lists variable " + std::to_string(jac_mol[i]) + " twice"; return MONORTM_EARG; }
+    }
+    if (ixsect == 1 && (nxs < 1 || !XAMNT)) {
+        c->err = "ixsect = 1: no cross-section tables on this context (monortm_hip_xsec_tables), or XAMNT missing";
+        return MONORTM_EARG;
     }
     return MONORTM_OK;
 }
@@ -537,16 +558,25 @@ int jac_check_states(Ctx *c, int nprof, int nwn, const double *wn, const int *nl
     return MONORTM_OK;
 }
 
+int modm_dev_impl(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
+                  const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
+                  double y0res, int ibrd, int ixsect, const void *XAMNT, void *ODXSEC, bool odx_given, void *O, void *O_BY_MOL, void *OC,
+                  void *O_CLW, const double *wn_ends, void *stream);   // (defined with monortm_hip_modm_xs_dev, below)
+
 // The MODM part of a Jacobian call (monortm_hip_jacobian_dev, monortm_hip_scan_jacobian_dev): jac_perturb_kernel, then MODM of the base
 // and the 2 (1 + njac) perturbed states.  Small batches (single-profile retrievals underfill the GPU) go through ONE extended MODM launch
 // of all states; larger ones through one launch of nprof profiles per state, of the shapes of a plain MODM call - so that alternating
 // Jacobian and plain calls never resizes the MODM workspaces (an extended launch is only taken while its line-physics records stay below
 // the 64 MB under which MODM keeps them).  O gets the base state; *xO_out: the states' optical depths in the context's workspace (state k
 // at xO + k st, k >= 1), *st_out: elements of one state.
+// ixsect = 1: the base state runs with the cross sections, as monortm_hip_modm_xs_dev does; the states T +- h and
+// P (1 +- eps) take their ODXSEC from xsec_jac_kernel - the base state's walk evaluated at the perturbed (P, T), not a walk of their
+// own - and the states of a cross-section molecule are written by that kernel ("+") and cleared ("-").  With ixsect = 0 every size,
+// launch and result is what it was.
 static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
                       const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
-                      double y0res, int ibrd, int njac, const int *jac_mol, void *O, const double *wn_ends, hipStream_t s, double **xO_out,
-                      size_t *st_out) {
+                      double y0res, int ibrd, int ixsect, const void *XAMNT, int njac, const int *jac_mol, void *O, const double *wn_ends,
+                      hipStream_t s, double **xO_out, size_t *st_out) {
     double vends[2];
     if (wn_ends) { vends[0] = wn_ends[0]; vends[1] = wn_ends[1]; }
     else {   // once here, not in every MODM call below
@@ -560,20 +590,33 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
     // XRAYL is the exception among the scalars: its states are launches on ONE more state of the perturbed arrays, which holds the
     // inputs of the Rayleigh term alone (modm_scalar below).  npa: the states of the arrays; without XRAYL npa = nps, and every size
     // and launch is what it was.
-    int lvar[MXMOL], nlv = 0;
+    // A cross-section molecule (MONORTM_JVAR_XS0 + x) has no state of the perturbed arrays and no MODM launch at all: O is linear in
+    // XAMNT, and its two states of O are the molecule's own term and zero (xsec_jac_kernel).
+    const bool xs = ixsect == 1;
+    int lvar[MXMOL], nlv = 0, p_state = 0;   // p_state: the "+" state of MONORTM_JVAR_P in the perturbed arrays, or 0
     bool rayl = false;
+    XsecJacArgs xa{};
     for (int i = 0; i < njac; i++) {
-        if (!jac_var_scalar(jac_mol[i])) lvar[nlv++] = jac_mol[i];
+        if (jac_var_xs(jac_mol[i])) { xa.kplus[jac_mol[i] - MONORTM_JVAR_XS0] = 3 + 2 * i; continue; }
+        if (!jac_var_scalar(jac_mol[i])) {
+            if (jac_mol[i] == MONORTM_JVAR_P) p_state = 3 + 2 * nlv;
+            lvar[nlv++] = jac_mol[i];
+        }
         rayl = rayl || jac_mol[i] == MONORTM_JVAR_CNTNM0 + 6;
     }
     const int nstate = 3 + 2 * njac, nps = 3 + 2 * nlv, npa = nps + (rayl ? 1 : 0);
     const size_t npl = (size_t)nprof * nlay_max, st = npl * nwn;
     const bool ext = (long long)nps * nprof <= 64 && (size_t)nps * npl * c->host.size() * 48 <= (64u << 20);
     const size_t nj = ext ? nps : 1;   // states whose unused MODM outputs are held at once
+    // ODXSEC of the states (ixsect = 1).  An extended launch reads one slot per state of the perturbed arrays, in their order (zero for the
+    // states that run without the cross sections); per-state launches need the base, T +- h and P (1 +- eps) only: slots 0, 1, 2, 3, 4
+    const int nodx = !xs ? 0 : ext ? nps : (p_state ? 5 : 3);
+    auto odx_slot = [&](int ps) { return ext ? ps : ps <= 2 ? ps : ps == p_state ? 3 : ps == p_state + 1 ? 4 : -1; };
     Arena ws;
     const size_t w_P = ws.add(npa * npl * 8), w_T = ws.add(npa * npl * 8), w_C = ws.add(npa * npl * 8), w_B = ws.add(npa * npl * 8),
                  w_W = ws.add(npa * npl * nmol * 8), w_nl = ws.add(npa * (size_t)nprof * sizeof(int)), w_O = ws.add(nstate * st * 8),
-                 w_OM = ws.add(nj * st * nmol * 8), w_OC = ws.add(nj * st * MONORTM_NCONT * 8), w_OL = ws.add(nj * st * 8);
+                 w_OM = ws.add(nj * st * nmol * 8), w_OC = ws.add(nj * st * MONORTM_NCONT * 8), w_OL = ws.add(nj * st * 8),
+                 w_X = xs ? ws.add(nodx * st * 8) : 0;
     if (ws.size > c->jac_ws_bytes) {
         if (c->jac_ws) HIPCHK(c, hipFree(c->jac_ws));
         c->jac_ws = nullptr;
@@ -582,7 +625,7 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
         c->jac_ws_bytes = ws.size;
     }
     char *wb = static_cast<char *>(c->jac_ws);
-    double *xO = reinterpret_cast<double *>(wb + w_O);
+    double *xO = reinterpret_cast<double *>(wb + w_O), *xX = xs ? reinterpret_cast<double *>(wb + w_X) : nullptr;
     *xO_out = xO;
     *st_out = st;
     JacPerturbArgs pa{};
@@ -594,19 +637,48 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
     pa.xWBRODL = reinterpret_cast<double *>(wb + w_B); pa.xWKL = reinterpret_cast<double *>(wb + w_W); pa.xnlay = reinterpret_cast<int *>(wb + w_nl);
     launch_jac_perturb(pa, s);
     HIPCHK(c, hipGetLastError());
-    auto modm = [&](int n, int s0, void *Oout) {   // MODM of n profiles of the perturbed arrays from their state s0 on
+    if (xs) {
+        // the further states' ODXSEC and the named molecules' terms, in one pass over the base state's walk; the perturbed (P, T) are
+        // read from the perturbed arrays, so they are the very values the states' MODM launches see
+        xa.nprof = nprof; xa.nwn = nwn; xa.nlay_max = nlay_max; xa.nx = p_state ? 4 : 2;
+        xa.wn = wn; xa.P = pa.P; xa.T = pa.T; xa.XAMNT = static_cast<const double *>(XAMNT); xa.nlay = nlay;
+        xa.xP = pa.xP; xa.xT = pa.xT;
+        const int pst[4] = {1, 2, p_state, p_state + 1};
+        for (int i = 0; i < xa.nx; i++) { xa.pstate[i] = pst[i]; xa.oslot[i] = odx_slot(pst[i]); }
+        xa.ODX = xX; xa.xO = xO; xa.stride = st; xa.two_eps = 2. * c->opt.jac_dlnw;
+        if (ext && nps > 3) HIPCHK(c, hipMemsetAsync(xX + 3 * st, 0, (size_t)(nps - 3) * st * 8, s));   // (the P slots are written below)
+        launch_xsec_jac(xa, c->xs, s);
+        HIPCHK(c, hipGetLastError());
+        if (ext) {   // the base state's ODXSEC, by xsec_kernel on the caller's arrays: what monortm_hip_modm_xs_dev launches
+            ModmArgs ma{};
+            ma.real_kind = 8; ma.nprof = nprof; ma.nwn = nwn; ma.nlay_max = nlay_max; ma.wn = wn; ma.P = P; ma.T = T; ma.nlay = nlay;
+            ma.XAMNT = XAMNT; ma.ODXSEC = xX; ma.nxs = c->xs.nxs;
+            launch_xsec(ma, c->xs, s);
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    // MODM of n profiles of the perturbed arrays from their state s0 on.  States of molecules and WBRODL run WITHOUT the cross sections
+    // (ODXSEC does not depend on WKL or WBRODL and would cancel in their differences): ixsect = 0 in a launch of their own, a zero slot
+    // of ODXSEC inside an extended launch
+    auto modm = [&](int n, int s0, void *Oout) {
         const size_t l0 = (size_t)s0 * npl;
-        return monortm_hip_modm_xs_dev(c, n, nwn, wn, dvset, pa.xnlay + (size_t)s0 * nprof, nlay_max, nmol, pa.xP + l0, pa.xT + l0, pa.xCLW + l0,
-                                       pa.xWKL + l0 * nmol, pa.xWBRODL + l0, cntnm_fac, sclcpl, sclhw, y0res, ibrd, 0, nullptr, nullptr, Oout,
-                                       wb + w_OM, wb + w_OC, wb + w_OL, vends, s);
+        const int slot = xs ? odx_slot(s0) : -1;
+        return modm_dev_impl(c, n, nwn, wn, dvset, pa.xnlay + (size_t)s0 * nprof, nlay_max, nmol, pa.xP + l0, pa.xT + l0, pa.xCLW + l0,
+                             pa.xWKL + l0 * nmol, pa.xWBRODL + l0, cntnm_fac, sclcpl, sclhw, y0res, ibrd, slot >= 0 ? 1 : 0, nullptr,
+                             slot >= 0 ? xX + (size_t)slot * st : nullptr, slot >= 0, Oout, wb + w_OM, wb + w_OC, wb + w_OL, vends, s);
     };
     // state k of O for a scalar variable: the caller's arrays, the argument at +eps (odd k) / -eps.  MODM switches a continuum off at a
-    // factor <= 0, so where fac - eps <= 0 the pair is fac + 2 eps / fac: one-sided over the same 2 eps, exact for a linear factor
+    // factor <= 0, so where fac - eps <= 0 the pair is fac + 2 eps / fac: one-sided over the same 2 eps, exact for a linear factor.
+    // (ixsect = 0 whatever the call's: ODXSEC depends on none of the scalars and would cancel in the difference.)
     auto modm_scalar = [&](int k, void *Oout) -> int {
         const int v = jac_mol[(k - 3) >> 1];
         const bool plus = !((k - 3) & 1);
         const double e = c->opt.jac_dlnw;
         double fac[7], sc[3] = {sclcpl, sclhw, y0res};
+        if (jac_var_xs(v)) {   // "+": xsec_jac_kernel has written it; "-": zero
+            if (!plus) HIPCHK(c, hipMemsetAsync(Oout, 0, st * 8, s));
+            return MONORTM_OK;
+        }
         if (v == MONORTM_JVAR_CNTNM0 + 6) {
             // XRAYL.  Rayleigh has no slot of OC - it is added into O directly - and is 1e-11 .. 1e-10 of O in the infrared: +-eps of it
             // in the total is quantisation (what XCO2C was below 30 cm-1).  Its states hold the term itself instead: MODM on the
@@ -644,12 +716,14 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
                                        npl, hipMemcpyDeviceToDevice, s));
         return MONORTM_OK;
     };
-    auto scalar_state = [&](int k) { return k >= 3 && jac_var_scalar(jac_mol[(k - 3) >> 1]); };
+    // (a cross-section molecule's states are no MODM launch either: they interrupt a run of per-layer states as a scalar's do)
+    auto scalar_state = [&](int k) { return k >= 3 && (jac_var_scalar(jac_mol[(k - 3) >> 1]) || jac_var_xs(jac_mol[(k - 3) >> 1])); };
     int k = 0, ps = 0;   // the next state of O, and of the perturbed arrays
     if (!ext) {
-        // the base state straight from the caller's arrays, into the caller's O: what monortm_hip_modm_dev returns for them
+        // the base state straight from the caller's arrays, into the caller's O: what monortm_hip_modm_dev (ixsect = 1: _modm_xs_dev, its
+        // ODXSEC into slot 0) returns for them
         if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw,
-                                             y0res, ibrd, 0, nullptr, nullptr, O, wb + w_OM, wb + w_OC, wb + w_OL, vends, s))
+                                             y0res, ibrd, xs ? 1 : 0, xs ? XAMNT : nullptr, xX, O, wb + w_OM, wb + w_OC, wb + w_OL, vends, s))
             return rc;
         k = ps = 1;
     }
@@ -672,13 +746,13 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
 // What the full-Jacobian *_dev entries (monortm_hip_jacobian_dev, _scan_jacobian_dev, _obs_jacobian_dev) refuse first, and the chain
 // fields their adjoint launches share: the perturbed states' optical depths (jac_states) and the half-steps of the differences.
 int jac_full_check(Ctx *c, const char *entry, bool any_null, int nprof, int nwn, int nlay_max, int nmol, int quantity, int njac,
-                   const int *jac_mol, const void *K_W) {
+                   const int *jac_mol, const void *K_W, int ixsect, const void *XAMNT) {
     if (!c->shards.empty()) return multi_only_host(c);
     if (int rc = need_real8(c, entry)) return rc;
     if (any_null) { c->err = "null array argument"; return MONORTM_EARG; }
     if (int rc = check_quantity(c, quantity)) return rc;
     if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
     if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     return MONORTM_OK;
 }
@@ -1405,13 +1479,17 @@ int monortm_hip_xsec_tables(void *ctx, int nxs, int nreg, const double *reg, con
     return MONORTM_OK;
 }
 
-int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
-                            int nmol, const void *P, const void *T, const void *CLW, const void *WKL,
-                            const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw, double y0res,
-                            int ibrd, int ixsect, const void *XAMNT, void *ODXSEC, void *O, void *O_BY_MOL, void *OC,
-                            void *O_CLW, const double *wn_ends, void *stream) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
+}  // extern "C"
+
+namespace {
+// monortm_hip_modm_xs_dev, and its variant for the Jacobian entries (jac_states): odx_given - with ixsect = 1 - says that ODXSEC already
+// holds the cross sections' optical depth of every state of this launch (xsec_kernel for the base state, xsec_jac_kernel for T +- h
+// and P (1 +- eps), zero for the states that run without them): xsec_kernel is not launched, XAMNT is not read, and the finish kernel
+// adds ODXSEC into O as ever.
+int modm_dev_impl(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
+                  const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
+                  double y0res, int ibrd, int ixsect, const void *XAMNT, void *ODXSEC, bool odx_given, void *O, void *O_BY_MOL, void *OC,
+                  void *O_CLW, const double *wn_ends, void *stream) {
     if (!c->shards.empty()) return multi_only_host(c);
     hipStream_t s = (hipStream_t)stream;
     if (!c->has_lines) { c->err = "this context holds no line table (created without a TAPE3 path): MODM needs one (GET_LNFL, modm.f90:187-190)"; return MONORTM_EARG; }
@@ -1438,7 +1516,7 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
     a.wn = wn; a.P = P; a.T = T; a.CLW = CLW; a.WKL = WKL; a.WBRODL = WBRODL; a.nlay = nlay;
     a.O = O; a.O_BY_MOL = O_BY_MOL; a.OC = OC; a.O_CLW = O_CLW; a.errflag = c->errflag;
     if (ixsect == 1) {
-        if (!XAMNT || !ODXSEC) { c->err = "IXSECT = 1: XAMNT / ODXSEC missing"; return MONORTM_EARG; }
+        if ((!XAMNT && !odx_given) || !ODXSEC) { c->err = "IXSECT = 1: XAMNT / ODXSEC missing"; return MONORTM_EARG; }
         if (c->xs.nxs < 1) { c->err = "IXSECT = 1: no cross-section tables on this context (monortm_hip_xsec_tables)"; return MONORTM_EARG; }
         a.XAMNT = XAMNT; a.ODXSEC = ODXSEC; a.nxs = c->xs.nxs;
     }
@@ -1514,7 +1592,7 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
     prof_end(c, s, ev);
     HIPCHK(c, hipGetLastError());
     prof_begin(c, s, 1, ev);
-    if (ixsect == 1) launch_xsec(a, c->xs, s);   // MONORTM_XSEC_SUB comes first (modm.f90:197); the finish kernel adds its sum into O
+    if (ixsect == 1 && !odx_given) launch_xsec(a, c->xs, s);   // MONORTM_XSEC_SUB comes first (modm.f90:197); the finish kernel adds its sum into O
     a.slices_reduced = pl.slices_reduced;
     if (pl.slices_reduced) launch_reduce_slices(a, s);
     if (pl.mw) {
@@ -1528,6 +1606,20 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
     prof_end(c, s, ev);
     HIPCHK(c, hipGetLastError());
     return MONORTM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max,
+                            int nmol, const void *P, const void *T, const void *CLW, const void *WKL,
+                            const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw, double y0res,
+                            int ibrd, int ixsect, const void *XAMNT, void *ODXSEC, void *O, void *O_BY_MOL, void *OC,
+                            void *O_CLW, const double *wn_ends, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    return modm_dev_impl(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect,
+                         XAMNT, ODXSEC, false, O, O_BY_MOL, OC, O_CLW, wn_ends, stream);
 }
 
 int monortm_hip_rtm_dev(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
@@ -1727,9 +1819,10 @@ int monortm_hip_rtm_jac_dev(void *ctx, int nprof, int nwn, const double *wn, con
 }
 
 // MODM of the base and the 2 (1 + njac) perturbed states (jac_states), then the adjoint chained with their differences.
-int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+int monortm_hip_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
                              const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                             double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                             double sclcpl, double sclhw, double y0res, int ibrd,
+                             int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
                              const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD,
                              void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC, const double *wn_ends,
                              void *stream) {
@@ -1738,11 +1831,11 @@ int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, do
     hipStream_t s = (hipStream_t)stream;
     const bool any_null = !wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !O ||
                           !RAD || !TB || !K_T || !K_TZ || !K_CLW || !K_SFC;
-    if (int rc = jac_full_check(c, "monortm_hip_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W)) return rc;
+    if (int rc = jac_full_check(c, "monortm_hip_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
     if (int rcd = check_device(c)) return rcd;
     double *xO = nullptr;
     size_t st = 0;
-    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, njac,
+    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, XAMNT, njac,
                             jac_mol, O, wn_ends, s, &xO, &st))
         return rc;
     RtmJacArgs a{};
@@ -1753,6 +1846,17 @@ int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, do
     launch_rtm_jac(a, true, s);
     HIPCHK(c, hipGetLastError());
     return MONORTM_OK;
+}
+
+int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                             const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                             double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                             const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD,
+                             void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC, const double *wn_ends,
+                             void *stream) {
+    return monortm_hip_jacobian_xs_dev(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
+                                       ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, O, RAD, TB, K_T, K_TZ, K_W, K_CLW,
+                                       K_O, K_SFC, wn_ends, stream);
 }
 
 int monortm_hip_rtm_jac(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
@@ -1778,9 +1882,10 @@ int monortm_hip_rtm_jac(void *ctx, int nprof, int nwn, const double *wn, const i
     });
 }
 
-int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+int monortm_hip_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
                          const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                         double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                         double sclcpl, double sclhw, double y0res, int ibrd,
+                         int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
                          const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD, void *TB,
                          void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC) {
     Ctx *c = static_cast<Ctx *>(ctx);
@@ -1793,12 +1898,13 @@ int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double
     }
     DeviceGuard guard;
     if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
     const size_t d = 8, l = (size_t)nlay_max * d, v = (size_t)nwn * d, w = l * nwn;
     HostCall hc(8);
     hc.flag = true;
     const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
-              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l), i_TZ = hc.in(TZ, l + d),
+              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l),
+              i_XA = hc.in(ixsect == 1 ? XAMNT : nullptr, l * ctx_nxs(c)), i_TZ = hc.in(TZ, l + d),
               i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, v), i_rf = hc.in(reflc, v);
     const int o_O = hc.out(O, w), o_rad = hc.out(RAD, v), o_tb = hc.out(TB, v), o_kt = hc.out(K_T, w), o_ktz = hc.out(K_TZ, (l + d) * nwn),
               o_kw = hc.out(njac ? K_W : nullptr, w * njac), o_kc = hc.out(K_CLW, w), o_ko = hc.out(K_O, w), o_ks = hc.out(K_SFC, 3 * v);
@@ -1809,11 +1915,21 @@ int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double
     };
     return hc.run(c, nprof, pre, [&](Ctx *s, int, int n, char *const *dv) {
         const double ends[2] = {wn[0], wn[nwn - 1]};
-        return monortm_hip_jacobian_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C], dv[i_W],
-                                        dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em], dv[i_rf],
+        return monortm_hip_jacobian_xs_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C], dv[i_W],
+                                        dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, dv[i_XA],
+                                        (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em], dv[i_rf],
                                         quantity, njac, jac_mol, dv[o_O], dv[o_rad], dv[o_tb], dv[o_kt], dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ko],
                                         dv[o_ks], ends, s->hs);
     });
+}
+
+int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                         const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                         double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                         const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD, void *TB,
+                         void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC) {
+    return monortm_hip_jacobian_xs(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, 0,
+                                   nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, O, RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O, K_SFC);
 }
 
 // ---- Jacobians of path scans ----------------------------------------------------------------------
@@ -1845,9 +1961,10 @@ int monortm_hip_rtm_scan_jac_dev(void *ctx, int nprof, int npath, int nwn, const
 
 // MODM of the base and the 2 (1 + njac) perturbed states ONCE (jac_states: what monortm_hip_jacobian_dev runs), then one launch of the
 // adjoint along every path, chained with the states' differences.
-int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+int monortm_hip_scan_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
                                   const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL,
-                                  const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd, const int *irt,
+                                  const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd,
+                                  int ixsect, const void *XAMNT, const int *irt,
                                   const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
                                   const int *jac_mol, int npath, const void *path, int sfc_per_path, void *O, void *RAD, void *TB, void *K_T,
                                   void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_PATH, void *K_SFC, const double *wn_ends,
@@ -1857,12 +1974,12 @@ int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *w
     hipStream_t s = (hipStream_t)stream;
     const bool any_null = !wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path ||
                           !O || !RAD || !TB || !K_T || !K_TZ || !K_CLW || !K_SFC;
-    if (int rc = jac_full_check(c, "monortm_hip_scan_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W)) return rc;
+    if (int rc = jac_full_check(c, "monortm_hip_scan_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
     if (int rcd = check_device(c)) return rcd;
     double *xO = nullptr;
     size_t st = 0;
-    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, njac,
+    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, XAMNT, njac,
                             jac_mol, O, wn_ends, s, &xO, &st))
         return rc;
     RtmScanJacArgs a{};
@@ -1875,6 +1992,18 @@ int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *w
     launch_rtm_scan_jac(a, true, s);
     HIPCHK(c, hipGetLastError());
     return MONORTM_OK;
+}
+
+int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                                  const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL,
+                                  const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd, const int *irt,
+                                  const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
+                                  const int *jac_mol, int npath, const void *path, int sfc_per_path, void *O, void *RAD, void *TB, void *K_T,
+                                  void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_PATH, void *K_SFC, const double *wn_ends,
+                                  void *stream) {
+    return monortm_hip_scan_jacobian_xs_dev(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
+                                            ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, O,
+                                            RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O, K_PATH, K_SFC, wn_ends, stream);
 }
 
 int monortm_hip_rtm_scan_jac(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
@@ -1907,9 +2036,10 @@ int monortm_hip_rtm_scan_jac(void *ctx, int nprof, int npath, int nwn, const dou
     });
 }
 
-int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+int monortm_hip_scan_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
                               const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                              double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                              double sclcpl, double sclhw, double y0res, int ibrd,
+                              int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
                               const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
                               int sfc_per_path, void *O, void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O,
                               void *K_PATH, void *K_SFC) {
@@ -1925,7 +2055,7 @@ int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, d
     // the whole call is checked before the first device is touched: a refusal launches nothing anywhere
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
     if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
     if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
     if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
     if (int rc = jac_check_states(c, nprof, nwn, wn, nlay, nlay_max, T)) return rc;
@@ -1933,18 +2063,31 @@ int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, d
     HostCall hc(8);
     hc.flag = true;
     const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
-              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l), i_TZ = hc.in(TZ, l + d),
+              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l),
+              i_XA = hc.in(ixsect == 1 ? XAMNT : nullptr, l * ctx_nxs(c)), i_TZ = hc.in(TZ, l + d),
               i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs), i_rf = hc.in(reflc, vs);
     const int o_O = hc.out(O, w), o_rad = hc.out(RAD, vo), o_tb = hc.out(TB, vo), o_kt = hc.out(K_T, wo), o_ktz = hc.out(K_TZ, (l + d) * nwn * npath),
               o_kw = hc.out(njac ? K_W : nullptr, wo * njac), o_kc = hc.out(K_CLW, wo), o_ko = hc.out(K_O, wo), o_kp = hc.out(K_PATH, wo),
               o_ks = hc.out(K_SFC, 3 * vo);
     return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
         const double ends[2] = {wn[0], wn[nwn - 1]};
-        return monortm_hip_scan_jacobian_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C],
-                                             dv[i_W], dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em],
+        return monortm_hip_scan_jacobian_xs_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C],
+                                             dv[i_W], dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, dv[i_XA],
+                                        (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em],
                                              dv[i_rf], quantity, njac, jac_mol, npath, dv[i_f], sfc_per_path, dv[o_O], dv[o_rad], dv[o_tb], dv[o_kt],
                                              dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ko], dv[o_kp], dv[o_ks], ends, s->hs);
     });
+}
+
+int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                              const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                              double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                              const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
+                              int sfc_per_path, void *O, void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O,
+                              void *K_PATH, void *K_SFC) {
+    return monortm_hip_scan_jacobian_xs(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
+                                        ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, O, RAD,
+                                        TB, K_T, K_TZ, K_W, K_CLW, K_O, K_PATH, K_SFC);
 }
 
 
@@ -2152,9 +2295,10 @@ int monortm_hip_rtm_obs_jac_dev(void *ctx, int nprof, int npath, int nwn, const 
 }
 
 // MODM of the base and the 2 (1 + njac) perturbed states ONCE (jac_states), then one launch of the contracting adjoint
-int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+int monortm_hip_obs_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
                                  const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                                 double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                                 double sclcpl, double sclhw, double y0res, int ibrd,
+                                 int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
                                  const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
                                  int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_SFC,
                                  const double *wn_ends, void *stream) {
@@ -2163,14 +2307,14 @@ int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn
     hipStream_t s = (hipStream_t)stream;
     const bool any_null = !wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path ||
                           !O || !Y || !K_T || !K_TZ || !K_CLW || !K_SFC;
-    if (int rc = jac_full_check(c, "monortm_hip_obs_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W)) return rc;
+    if (int rc = jac_full_check(c, "monortm_hip_obs_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
     Ctx::Obs *ob = nullptr;
     if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
     if (int rcd = check_device(c)) return rcd;
     double *xO = nullptr;
     size_t st = 0;
-    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, njac,
+    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, XAMNT, njac,
                             jac_mol, O, wn_ends, s, &xO, &st))
         return rc;
     RtmObsJacArgs a{};
@@ -2184,6 +2328,17 @@ int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn
     launch_rtm_obs_jac(a, true, 8, s);
     HIPCHK(c, hipGetLastError());
     return MONORTM_OK;
+}
+
+int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                                 const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                                 double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                                 const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
+                                 int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_SFC,
+                                 const double *wn_ends, void *stream) {
+    return monortm_hip_obs_jacobian_xs_dev(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
+                                           ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, obs,
+                                           O, Y, K_T, K_TZ, K_W, K_CLW, K_SFC, wn_ends, stream);
 }
 
 int monortm_hip_rtm_obs_jac(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
@@ -2218,9 +2373,10 @@ int monortm_hip_rtm_obs_jac(void *ctx, int nprof, int npath, int nwn, const doub
     });
 }
 
-int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+int monortm_hip_obs_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
                              const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                             double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                             double sclcpl, double sclhw, double y0res, int ibrd,
+                             int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
                              const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
                              int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_SFC) {
     Ctx *c = static_cast<Ctx *>(ctx);
@@ -2235,7 +2391,7 @@ int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, do
     // the whole call is checked before the first device is touched: a refusal launches nothing anywhere
     if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
     if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W)) return rc;
+    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
     if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
     Ctx::Obs *ob = nullptr;
     if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
@@ -2246,17 +2402,29 @@ int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, do
     HostCall hc(8);
     hc.flag = true;
     const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
-              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l), i_TZ = hc.in(TZ, l + d),
+              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l),
+              i_XA = hc.in(ixsect == 1 ? XAMNT : nullptr, l * ctx_nxs(c)), i_TZ = hc.in(TZ, l + d),
               i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs), i_rf = hc.in(reflc, vs);
     const int o_O = hc.out(O, l * nwn), o_y = hc.out(Y, y), o_kt = hc.out(K_T, yk), o_ktz = hc.out(K_TZ, yk + y),
               o_kw = hc.out(njac ? K_W : nullptr, yk * njac), o_kc = hc.out(K_CLW, yk), o_ks = hc.out(K_SFC, 3 * y);
     return hc.run(c, nprof, [&](Ctx *s, int g, int n, char *const *dv) {   // (every shard holds the operator under a handle of its own)
         const double ends[2] = {wn[0], wn[nwn - 1]};
-        return monortm_hip_obs_jacobian_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C],
-                                            dv[i_W], dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em],
+        return monortm_hip_obs_jacobian_xs_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C],
+                                            dv[i_W], dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, dv[i_XA],
+                                        (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em],
                                             dv[i_rf], quantity, njac, jac_mol, npath, dv[i_f], sfc_per_path, g < 0 ? obs : ob->shard[g], dv[o_O],
                                             dv[o_y], dv[o_kt], dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ks], ends, s->hs);
     });
+}
+
+int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                             const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                             double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                             const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
+                             int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_SFC) {
+    return monortm_hip_obs_jacobian_xs(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
+                                       ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, obs, O, Y,
+                                       K_T, K_TZ, K_W, K_CLW, K_SFC);
 }
 
 // ---- the forward measurement operator: channel- and beam-averaged scans ------------------------------

@@ -287,6 +287,24 @@ struct JacPerturbArgs {
     int *xnlay;
 };
 
+// The cross-section molecules in a full Jacobian call (xsec_jac_kernel.hip), real_kind 8: ODXSEC of nx further
+// states - 2: T +- h, 4: and P (1 +- eps) - summed on the base state's plan, and the named molecules' own terms.  The base state is
+// the caller's P, T, XAMNT [nprof][nlay_max](x nxs); further state s reads its (P', T') from state pstate[s] of the perturbed arrays
+// xP, xT [state][nprof][nlay_max] (jac_perturb_kernel) and writes slot oslot[s] of ODX [slot][nprof][nlay_max][nwn].  kplus[x] != 0:
+// molecule x (0-based position in the cross-section request) is a Jacobian variable, and state kplus[x] of xO (state k at xO + k
+// stride, stride = nprof x nlay_max x nwn) gets two_eps XAMNT sigma_x radfn of the base state.
+struct XsecJacArgs {
+    int nprof, nwn, nlay_max, nx;
+    const double *wn, *P, *T, *XAMNT;
+    const int *nlay;
+    const double *xP, *xT;
+    int pstate[4], oslot[4];
+    double *ODX, *xO;
+    size_t stride;
+    int kplus[38];
+    double two_eps;
+};
+
 // exp() and 1/x for the small kernels behind the line sum (radiance recurrences, microwave continuum): Cody-Waite reduction +
 // degree-13 polynomial (the routine of the line kernel's prepare stage: 20 instructions, 1-2 ulp like the library call at ~35)
 // and v_rcp_f64 + two Newton steps (1 ulp; an IEEE division is ~11 instructions).  exp_cw: |n| < 2^31 for every argument that
@@ -478,6 +496,8 @@ hipError_t launch_finish_mw(const ModmArgs &a, const DevTables &tb, double V1, d
 void launch_kat(int which, int n, const double *in, const double *tab, double *out, int *errflag, const DevTables &tb, hipStream_t s);
 // xsec_kernel.hip: MONORTM_XSEC_SUB + convolve (src/monortm_sub.F90:1540-1834) -> a.ODXSEC
 void launch_xsec(const ModmArgs &a, const DevXsec &x, hipStream_t s);
+// xsec_jac_kernel.hip: the same walk with further states on the base state's plan -> a.ODX, a.xO
+void launch_xsec_jac(const XsecJacArgs &a, const DevXsec &x, hipStream_t s);
 // rtm_kernel.hip
 void launch_rtm(const RtmArgs &a, hipStream_t s);
 // rtm_scan_kernel.hip
