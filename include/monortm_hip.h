@@ -237,7 +237,8 @@ int monortm_hip_rtm_scan_dev(void *ctx, int nprof, int npath, int nwn, const dou
 /* ---- Jacobians for retrievals (no reference counterpart: "CURRENTLY MONORTM DOES NOT HANDLE DERIVATIVES",
  * src/monortm_sub.F90:199).  DESIGN.md section 3.6 has the method and the error budget.
  *   Inputs: the arguments of monortm_hip_modm / monortm_hip_rtm.  K holds PARTIAL derivatives with respect to them, every other
- *   input fixed (d/dT_k holds WKL, P and TZ constant); callers chain to their own state vector.
+ *   input fixed (d/dT_k holds WKL, P and TZ constant); callers chain to their own state vector (monortm_hip_oe_step reads the
+ *   per-measurement K of monortm_hip_obs_jacobian through a state map and returns the retrieval's update).
  *   quantity = 1: q = TB (needs RAD > 0);  quantity = 0: q = RAD.
  *   K_T   [nprof][nlay_max][nwn]     dq/dT_k, layer temperature: the Planck term of RTM and, in monortm_hip_jacobian, its effect on O
  *                                    through MODM (lines, continuum, cloud);  monortm_hip_rtm_jac: the Planck term only
@@ -572,6 +573,58 @@ int monortm_hip_obs_dev(void *ctx, int nprof, int nwn, const double *wn, double 
                         int ibrd, const int *irt, const monortm_real *TZ, const monortm_real *tmpsfc, const monortm_real *emiss,
                         const monortm_real *reflc, int quantity, int npath, const monortm_real *path, int sfc_per_path, int obs,
                         const double *vcen, monortm_real *O, monortm_real *Y, const double *wn_ends, void *stream);
+
+/* ---- The optimal-estimation step: a batched Gauss-Newton / Levenberg-Marquardt update from K (no reference counterpart; Rodgers,
+ * Inverse Methods for Atmospheric Sounding, eq. 5.10).  DESIGN.md section 3.13.
+ * Per profile, with m = nview x nchan measurements (measurement j = v nchan + c, the order of Y) and n = nstate state elements:
+ *   d' = (xa - x) / (1 + gamma)
+ *   W  = Sa K^T / (1 + gamma)                  [n][m]
+ *   M  = K W + diag(se) = L L^T                [m][m], Cholesky
+ *   r  = (y_obs - Y) - K d'
+ *   z  = M^-1 r
+ *   x_new = x + d' + W z
+ *   post_var_i = Sa_ii / (1 + gamma) - |L^-1 W_i|^2      the diagonal of the posterior covariance of the damped problem
+ *   avk_diag_i = (L^-1 W_i) . (L^-1 K_:,i)               the diagonal of the averaging kernel; its sum: the degrees of freedom for signal
+ *   chi2 = sum_j (y_obs_j - Y_j)^2 / se_j
+ * gamma = 0 is Rodgers (5.10); gamma > 0 equals the n-form x + [(1 + gamma) Sa^-1 + K^T Se^-1 K]^-1 [K^T Se^-1 (y_obs - Y) - Sa^-1 (x - xa)].
+ * Sa^-1 never appears (nmeas << nstate for radiometers).
+ *
+ * K [m][n] is read IN PLACE from the outputs of monortm_hip_obs_jacobian[_xs][_dev], [nprof][nview][rows][nchan], through the state map:
+ * state s is row state_row[s] of the array state_kind[s] names -
+ *   0: K_T, layer k;  1: K_TZ, level;  2: K_W, k njac + i;  3: K_CLW, layer k;  4: K_SFC, 0..2.
+ * Any order, repeats allowed; an array no state names may be NULL.  Rows of layers >= nlay[p] are 0 in K: their states relax to the prior.
+ *   Y, y_obs        [nprof][nview][nchan]
+ *   x, xa           [nprof][nstate]
+ *   Sa              [nstate][nstate], or [nprof][nstate][nstate] with sa_per_profile = 1.  ONLY THE LOWER TRIANGLE IS READ (row >= column).
+ *   se              [nmeas], or [nprof][nmeas] with se_per_profile = 1: the diagonal of the measurement-error covariance
+ *   gamma           [nprof], or NULL: 0
+ *   x_new           [nprof][nstate]                 post_var, avk_diag  [nprof][nstate], may be NULL
+ *   chi2            [nprof], may be NULL            status  int [nprof]
+ * A profile whose Cholesky meets a pivot <= 0 or not finite, whose r is not finite (a non-finite K, Sa, se, x, xa, Y or y_obs), or whose
+ * gamma is negative or not finite has status 1, x_new = x and post_var = avk_diag = chi2 = 0; every other profile has status 0 and is
+ * unaffected, bit for bit.  This is NOT an error of monortm_hip_check: one bad prior does not fail a batch.
+ * One launch (oe_kernel.hip), one workgroup per profile, no atomics, every sum in ascending order of its index: repeated calls give the
+ * same bits, and a profile gives the same bits alone and inside a batch.
+ * Refused before anything is launched: real_kind 4 (MONORTM_EUNSUPPORTED); nmeas outside 1..128, nstate outside 1..2048, a kind outside
+ * 0..4, a row outside its array, a kind whose array is NULL (MONORTM_EARG).  state_kind, state_row: host int [nstate].
+ * Host buffers: sharded by profile like monortm_hip_obs_jacobian. */
+int monortm_hip_oe_step(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                        const int *state_row, const monortm_real *K_T, const monortm_real *K_TZ, const monortm_real *K_W,
+                        const monortm_real *K_CLW, const monortm_real *K_SFC, const monortm_real *Y, const monortm_real *y_obs,
+                        const monortm_real *x, const monortm_real *xa, const monortm_real *Sa, int sa_per_profile,
+                        const monortm_real *se, int se_per_profile, const monortm_real *gamma, monortm_real *x_new,
+                        monortm_real *post_var, monortm_real *avk_diag, monortm_real *chi2, int *status);
+/* The same on device pointers (the state map stays on the host), asynchronous on `stream`; one-device context.  The workspace
+ * ([nprof][2][nmeas][nstate] doubles) and the device copy of the state map are sized at the first call of a shape and kept: after one
+ * call, a second of the same shapes and the same map allocates and copies nothing (graph capture).  A call with another map waits for
+ * the stream before it replaces the device copy. */
+int monortm_hip_oe_step_dev(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate,
+                            const int *state_kind /*host*/, const int *state_row /*host*/, const monortm_real *K_T,
+                            const monortm_real *K_TZ, const monortm_real *K_W, const monortm_real *K_CLW, const monortm_real *K_SFC,
+                            const monortm_real *Y, const monortm_real *y_obs, const monortm_real *x, const monortm_real *xa,
+                            const monortm_real *Sa, int sa_per_profile, const monortm_real *se, int se_per_profile,
+                            const monortm_real *gamma, monortm_real *x_new, monortm_real *post_var, monortm_real *avk_diag,
+                            monortm_real *chi2, int *status, void *stream);
 
 /* Device-side failure flags raised by the kernels of earlier *_dev calls (temperature range, SD-Voigt
  * sign): synchronises `stream`, returns MONORTM_OK or the first error and clears the flags. */

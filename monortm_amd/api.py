@@ -126,6 +126,8 @@ SYMBOLS = {
     "monortm_hip_obs_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                       C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int,
                                       C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "monortm_hip_oe_step": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int] + [_vp] * 6),
+    "monortm_hip_oe_step_dev": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int] + [_vp] * 7),
     "monortm_hip_check": (C.c_int, [_vp, _vp]),
     "monortm_hip_profile": (C.c_int, [_vp, C.c_int]),
     "monortm_hip_kernel_time": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_longlong)]),
@@ -163,6 +165,80 @@ def jac_codes(seq, xs_names=None) -> np.ndarray:
             v = JAC_VARS[v.lower()]
         out.append(int(v))
     return np.ascontiguousarray(np.array(out, np.int32).reshape(-1))
+
+
+# ---- the state map of the optimal-estimation step (monortm_hip_oe_step) -----------------------------------
+# molecule names in the line file's numbering (1-based), for ("w", name, layers) of a state spec
+MOLECULES = ("H2O", "CO2", "O3", "N2O", "CO", "CH4", "O2", "NO", "SO2", "NO2", "NH3", "HNO3", "OH", "HF", "HCL", "HBR", "HI", "CLO", "OCS", "H2CO",
+             "HOCL", "N2", "HCN", "CH3CL", "H2O2", "C2H2", "C2H6", "PH3", "COF2", "SF6", "H2S", "HCOOH", "HO2", "O", "CLONO2", "NO+", "HOBR",
+             "C2H4", "CH3OH")
+OE_KINDS = {"t": 0, "tz": 1, "w": 2, "clw": 3, "tmpsfc": 4, "emiss": 4, "reflc": 4}   # state kind of the C ABI: K_T, K_TZ, K_W, K_CLW, K_SFC
+OE_SFC_ROWS = {"tmpsfc": 0, "emiss": 1, "reflc": 2}
+OE_MAX_MEAS, OE_MAX_STATE = 128, 2048
+
+
+def oe_var_code(v) -> int:
+    """The Jacobian variable a ("w", v, layers) item names: a molecule name of MOLECULES (case-insensitive) is its 1-based number,
+    anything else goes through jac_codes (an int code, or a name of JAC_VARS)."""
+    if isinstance(v, str) and v.upper() in MOLECULES:
+        return MOLECULES.index(v.upper()) + 1
+    return int(jac_codes([v])[0])
+
+
+def _oe_items(spec, nlay_max: int):
+    """A state spec as a flat list of (name, code or None, layer / level / None); ValueError on anything malformed."""
+    if isinstance(spec, (str, bytes)) or not hasattr(spec, "__iter__"):
+        raise ValueError("state spec: a list of tuples such as ('t', layers), ('w', 'H2O', layers), ('tmpsfc',)")
+    out = []
+    for item in spec:
+        if not isinstance(item, (tuple, list)) or not item or not isinstance(item[0], str) or item[0].lower() not in OE_KINDS:
+            raise ValueError(f"state spec item {item!r}: the first entry must be one of {sorted(OE_KINDS)}")
+        name = item[0].lower()
+        want = {"w": 3, "tmpsfc": 1, "emiss": 1, "reflc": 1}.get(name, 2)
+        if len(item) != want:
+            raise ValueError(f"state spec item {item!r}: {name!r} takes {want - 1} argument(s)")
+        if want == 1:
+            out.append((name, None, None))
+            continue
+        code = oe_var_code(item[1]) if name == "w" else None
+        idx = item[-1]
+        idx = list(idx) if hasattr(idx, "__iter__") and not isinstance(idx, str) else [idx]
+        top = nlay_max + 1 if name == "tz" else nlay_max
+        for k in idx:
+            if not isinstance(k, (int, np.integer)) or not 0 <= int(k) < top:
+                raise ValueError(f"state spec item {item!r}: index {k!r} outside 0..{top - 1}")
+            out.append((name, code, int(k)))
+    if not out:
+        raise ValueError("state spec: no state element")
+    return out
+
+
+def oe_state_map(spec, nlay_max: int, vars=()):
+    """(state_kind, state_row) of monortm_hip_oe_step, int32 [nstate], from a readable spec: a list of
+      ("t", layers)  ("tz", levels)  ("w", "H2O" | code | JAC_VARS name, layers)  ("clw", layers)  ("tmpsfc",)  ("emiss",)  ("reflc",)
+    in the order the state vector has them; layers / levels are 0-based ints or sequences of them, repeats are allowed.  ("w", v, ...) is
+    resolved against `vars`, the codes in slot order that an obs_jacobian result carries under "vars": row = layer x len(vars) + slot."""
+    vars = [int(v) for v in np.asarray(vars).reshape(-1)]
+    kind, row = [], []
+    for name, code, k in _oe_items(spec, nlay_max):
+        kind.append(OE_KINDS[name])
+        if name == "w":
+            if code not in vars:
+                raise ValueError(f"state spec: variable {code} is not among the Jacobian's vars {vars}")
+            row.append(k * len(vars) + vars.index(code))
+        else:
+            row.append(OE_SFC_ROWS[name] if k is None else k)
+    return np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(row, np.int32)
+
+
+def _oe_map_of(state, nlay_max: int, vars):
+    """A (state_kind, state_row) pair as it is, a spec through oe_state_map."""
+    if isinstance(state, tuple) and len(state) == 2 and all(isinstance(a, np.ndarray) for a in state):
+        kind, row = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in state)
+        if kind.shape != row.shape or not len(kind):
+            raise ValueError("state map: state_kind and state_row must be two int arrays of one length >= 1")
+        return kind, row
+    return oe_state_map(state, nlay_max, vars)
 
 
 JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_sfc")
@@ -809,6 +885,36 @@ class MonoRTM:
         out["vars"] = jm
         return out
 
+    # ---- the optimal-estimation step (monortm_hip_oe_step) --------------------------------------------------------
+    def oe_step(self, jac: dict, state, y_obs, x, xa, Sa, se, gamma=None) -> dict:
+        """One Gauss-Newton / Levenberg-Marquardt update from the dict obs_jacobian (or rtm_obs_jacobian) returned: K is read in place
+        through `state`, a spec of oe_state_map or the (state_kind, state_row) pair it makes.  y_obs [nprof, nview, nchan]; x, xa
+        [nprof, nstate]; Sa [nstate, nstate] or [nprof, nstate, nstate] (lower triangle read); se [nmeas] or [nprof, nmeas]; gamma
+        None (0) or [nprof].  Dict of x_new, post_var, avk_diag [nprof, nstate], dfs (the sum of avk_diag), chi2 [nprof] and status
+        (int32 [nprof]; 1: the profile's step failed and x_new = x)."""
+        kt = jac["k_t"]
+        nprof, nv, lm, nc = kt.shape
+        kw = jac.get("k_w")
+        nj = 0 if kw is None else kw.shape[3]
+        kind, row = _oe_map_of(state, lm, jac.get("vars", ()))
+        n, m = len(kind), nv * nc
+        f = lambda a: None if a is None else _np(a)  # noqa: E731
+        K = [f(jac.get(k)) for k in ("k_t", "k_tz", "k_w", "k_clw", "k_sfc")]
+        if nj == 0:
+            K[2] = None
+        Y, yo, x, xa, Sa, se, gamma = (f(a) for a in (jac["y"], y_obs, x, xa, Sa, se, gamma))
+        for name, a, shapes in (("y_obs", yo, [(nprof, nv, nc)]), ("x", x, [(nprof, n)]), ("xa", xa, [(nprof, n)]), ("Sa", Sa, [(n, n), (nprof, n, n)]),
+                                ("se", se, [(m,), (nprof, m)]), ("gamma", gamma, [(nprof,)])):
+            if a is not None and a.shape not in shapes:
+                raise ValueError(f"{name} must be {' or '.join(str(list(s)) for s in shapes)}, got {list(a.shape)}")
+        out = dict(x_new=np.zeros((nprof, n)), post_var=np.zeros((nprof, n)), avk_diag=np.zeros((nprof, n)), chi2=np.zeros(nprof),
+                   status=np.zeros(nprof, np.int32))
+        self._chk(self.lib.monortm_hip_oe_step(self.ctx, nprof, nv, nc, lm, nj, n, _ptr(kind), _ptr(row), *[_ptr(k) for k in K], _ptr(Y), _ptr(yo),
+                                               _ptr(x), _ptr(xa), _ptr(Sa), int(Sa.ndim == 3), _ptr(se), int(se.ndim == 2), _ptr(gamma),
+                                               *[_ptr(out[k]) for k in ("x_new", "post_var", "avk_diag", "chi2", "status")]))
+        out["dfs"] = out["avk_diag"].sum(axis=1)
+        return out
+
     # ---- the forward measurement operator (monortm_hip_rtm_obs / monortm_hip_obs; DESIGN.md section 3.10) ------------------------------
     def rtm_obs(self, profiles: list[Profile], O: np.ndarray, path, obs: int, quantity="tb", emiss=None, reflc=None, vcen=None) -> dict:
         """y = F(x) per measurement from one O [nprof, nlay_max, nwn]: the radiances of rtm_scan contracted with the operator `obs`
@@ -1189,6 +1295,128 @@ class DeviceBatch:
                                             d(self.T), d(self.TZ), d(self.O), d(fd), d(self.tmpsfc0), 0, d(self.emiss), d(self.reflc),
                                             int(obs), d(vd) if q == 2 else None, d(y), sp))
         return y
+
+    # ---- the optimal-estimation step on device tensors (monortm_hip_oe_step_dev) --------------------------------
+    def oe_step(self, jac: dict, state, y_obs, x, xa, Sa, se, gamma=None, stream=None) -> dict:
+        """MonoRTM.oe_step on torch tensors, on the current (or the given) stream, asynchronously: jac is the dict obs_jacobian returned,
+        every other array a contiguous float64 tensor on the batch's device (nothing is copied or converted: ValueError otherwise).
+        The outputs - x_new, post_var, avk_diag, dfs, chi2, status - are allocated at the first call for (nprof, nview, nchan, nstate)
+        and overwritten by every later one, so that a graph capture of the call (after one warm call with the same state map) replays
+        into the same tensors.  A failed profile is status 1, never an error of check()."""
+        t = self.torch
+        kt = jac["k_t"]
+        nprof, nv, lm, nc = (int(v) for v in kt.shape)
+        kw = jac.get("k_w")
+        nj = 0 if kw is None else int(kw.shape[3])
+        vars = jac.get("vars", ())
+        kind, row = _oe_map_of(state, lm, vars.numpy() if isinstance(vars, t.Tensor) else vars)
+        n, m = len(kind), nv * nc
+        K = [jac.get(k) for k in ("k_t", "k_tz", "k_w", "k_clw", "k_sfc")]
+        if nj == 0:
+            K[2] = None
+        for name, a, shapes in [("y_obs", y_obs, [(nprof, nv, nc)]), ("x", x, [(nprof, n)]), ("xa", xa, [(nprof, n)]), ("Sa", Sa, [(n, n), (nprof, n, n)]),
+                                ("se", se, [(m,), (nprof, m)]), ("gamma", gamma, [(nprof,)]), ("y", jac["y"], [(nprof, nv, nc)])] + \
+                               [(f"K[{i}]", k, None) for i, k in enumerate(K)]:
+            if a is None and (name == "gamma" or name.startswith("K[")):
+                continue
+            if not isinstance(a, t.Tensor) or a.dtype != t.float64 or a.device != self.dev or not a.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float64 tensor on {self.dev}")
+            if shapes is not None and tuple(a.shape) not in shapes:
+                raise ValueError(f"{name} must be {' or '.join(str(list(s)) for s in shapes)}, got {list(a.shape)}")
+        cache = self.__dict__.setdefault("_oe", {})
+        key = (nprof, nv, nc, n)
+        if key not in cache:
+            z = lambda *s: t.zeros(*s, dtype=t.float64, device=self.dev)  # noqa: E731
+            cache[key] = dict(x_new=z(nprof, n), post_var=z(nprof, n), avk_diag=z(nprof, n), dfs=z(nprof), chi2=z(nprof),
+                              status=t.zeros(nprof, dtype=t.int32, device=self.dev))
+        out = cache[key]
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        rt = self.rt
+        d = lambda a: None if a is None else _vp(a.data_ptr())  # noqa: E731
+        rt._chk(rt.lib.monortm_hip_oe_step_dev(rt.ctx, nprof, nv, nc, lm, nj, n, _ptr(kind), _ptr(row), *[d(k) for k in K], d(jac["y"]), d(y_obs),
+                                               d(x), d(xa), d(Sa), int(Sa.dim() == 3), d(se), int(se.dim() == 2), d(gamma),
+                                               *[d(out[k]) for k in ("x_new", "post_var", "avk_diag", "chi2", "status")], _vp(s.cuda_stream)))
+        with t.cuda.stream(s):
+            t.sum(out["avk_diag"], dim=1, out=out["dfs"])
+        return dict(out)
+
+    def _oe_resident(self, items):
+        """The elements of a retrieval's state by the resident input they live in: [(name, molecule, columns of the state vector, their
+        layers / levels, the columns written back, their layers / levels)] - a variable named twice is read into each of its columns and
+        written back from the last; ValueError for what retrieve() cannot write back."""
+        groups = {}
+        for col, (name, code, k) in enumerate(items):
+            if name in ("emiss", "reflc"):
+                raise ValueError(f"retrieve: a state element {name!r} has no resident scalar to write back (oe_step itself takes it)")
+            if name == "w" and not 1 <= code <= self.nmol:
+                raise ValueError(f"retrieve: Jacobian variable {code} is not a molecule of the batch (oe_step itself takes it)")
+            g = groups.setdefault((name, code), ([], [], {}))
+            g[0].append(col)
+            g[1].append(0 if k is None else k)
+            g[2][0 if k is None else k] = col
+        return [(name, code, g[0], g[1], list(g[2].values()), list(g[2].keys())) for (name, code), g in groups.items()]
+
+    def retrieve(self, y_obs, path, obs: int, state, xa, Sa, se, gammas=(0,) * 6, mols=None, quantity="tb", keep=False, stream=None) -> dict:
+        """An optimal-estimation retrieval on the resident batch, one iteration per entry of `gammas` (a scalar or [nprof] each):
+        obs_jacobian -> oe_step -> x_new written back into the batch's inputs with torch ops; nothing visits the host.  `state` is a spec
+        of oe_state_map over ("t", layers), ("tz", levels), ("w", molecule, layers) - ln of the molecule's amounts -, ("clw", layers) and
+        ("tmpsfc",); "emiss", "reflc" and Jacobian variables that are no molecule are refused (ValueError).  The first iterate is what the
+        batch holds.  Written back: T, TZ, CLW and TMPSFC as they are, WKL[..., mol] = exp(x); only layers < nlay[p] (levels <= nlay[p]).
+        mols: the Jacobian's variables (default: the molecules of the spec, in the order it names them).  y_obs, xa, Sa, se as oe_step.
+        Returns the dict of the last oe_step, plus x (the iterate that step started from), chi2_history [len(gammas), nprof] and, with
+        keep=True, kept: per iteration, clones of y, the k_*, x, x_new and gamma."""
+        t = self.torch
+        items = _oe_items(state, self.lm)
+        groups = self._oe_resident(items)
+        if mols is None:
+            mols = tuple(dict.fromkeys(code for name, code, _ in items if name == "w"))
+        if not len(gammas):
+            raise ValueError("retrieve: gammas is empty")
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        idx = lambda v: t.as_tensor(v, dtype=t.long, device=self.dev)  # noqa: E731
+        n = len(items)
+        if not isinstance(xa, t.Tensor) or tuple(xa.shape) != (self.nprof, n):
+            raise ValueError(f"xa must be a tensor [{self.nprof}, {n}]")
+        with t.cuda.stream(s):
+            x = xa.clone()   # (elements of layers >= nlay[p] stay at the prior: K is 0 there)
+            gam = t.zeros(self.nprof, dtype=t.float64, device=self.dev)
+            resident = lambda name, code, ks: (self.tmpsfc0[:, None] if name == "tmpsfc" else self.WKL[:, ks, code - 1] if name == "w"  # noqa: E731
+                                               else {"t": self.T, "tz": self.TZ, "clw": self.CLW}[name][:, ks])
+            alive = lambda name, ks: ks[None, :] < self.nlay[:, None] + (2 ** 30 if name == "tmpsfc" else 1 if name == "tz" else 0)  # noqa: E731
+            plan = []
+            for name, code, cols, ks, wcols, wks in groups:
+                cols, ks, wcols, wks = idx(cols), idx(ks), idx(wcols), idx(wks)
+                v = resident(name, code, ks)
+                x[:, cols] = t.where(alive(name, ks), t.log(v) if name == "w" else v.expand(-1, len(cols)), x[:, cols])
+                plan.append((name, code, wcols, wks, alive(name, wks)))
+            hist, kept, step = [], [], None
+            for it, g in enumerate(gammas):
+                if isinstance(g, (int, float)):
+                    gam.fill_(float(g))
+                else:
+                    gam.copy_(t.as_tensor(g, dtype=t.float64).expand(self.nprof))
+                jac = self.obs_jacobian(path, obs, mols=mols, quantity=quantity, stream=s)
+                step = self.oe_step(jac, state, y_obs, x, xa, Sa, se, gamma=gam, stream=s)
+                hist.append(step["chi2"].clone())
+                if keep:
+                    kept.append(dict({k: jac[k].clone() for k in ("y", "k_t", "k_tz", "k_w", "k_clw", "k_sfc")}, x=x.clone(), x_new=step["x_new"].clone(),
+                                     gamma=gam.clone()))
+                xn = step["x_new"]
+                for name, code, wcols, wks, live in plan:
+                    if name == "tmpsfc":
+                        self.tmpsfc0.copy_(xn[:, wcols[0]])
+                        self.tmpsfc.copy_(self.tmpsfc0)
+                    elif name == "w":
+                        self.WKL[:, wks, code - 1] = t.where(live, t.exp(xn[:, wcols]), self.WKL[:, wks, code - 1])
+                    else:
+                        dst = {"t": self.T, "tz": self.TZ, "clw": self.CLW}[name]
+                        dst[:, wks] = t.where(live, xn[:, wcols], dst[:, wks])
+                if it + 1 < len(gammas):
+                    x.copy_(xn)
+        out = dict(step, x=x, chi2_history=t.stack(hist))
+        if keep:
+            out["kept"] = kept
+        return out
 
     # ---- HIP graph: the three launches of a step recorded once, replayed with a single call ------------------
     def capture(self):

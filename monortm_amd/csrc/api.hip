@@ -90,6 +90,13 @@ struct Ctx {
     // that the Jacobian does not use, grown on demand and kept (a second call of the same shapes allocates nothing)
     void *jac_ws = nullptr;
     size_t jac_ws_bytes = 0;
+    // monortm_hip_oe_step_dev: the workspace [nprof][2][nmeas][nstate] of oe_kernel.hip, and the state map on
+    // the device with the host copy it was uploaded from - a call whose map equals the copy uploads nothing.  Grown on demand and kept
+    void *oe_ws = nullptr;
+    size_t oe_ws_elems = 0;
+    void *oe_map = nullptr;
+    size_t oe_map_ints = 0;
+    std::vector<int> oe_map_host;
     // measurement operators (monortm_hip_obs_create): the device tables of up to kMaxObs operators, checked on
     // the host when they were created - the kernel never sees an unchecked index, and a call that takes a handle copies nothing
     struct Obs {
@@ -1140,6 +1147,8 @@ void monortm_hip_finalize(void *ctx) {
         if (e) hipEventDestroy(e);
     c->mw_cache.release();
     if (c->jac_ws) hipFree(c->jac_ws);
+    if (c->oe_ws) hipFree(c->oe_ws);
+    if (c->oe_map) hipFree(c->oe_map);
     for (auto &ob : c->obs)
         if (ob.dev) hipFree(ob.dev);
     for (int i = 0; i < 12; i++)
@@ -2596,6 +2605,117 @@ int monortm_hip_obs(void *ctx, int nprof, int nwn, const double *wn, double dvse
         return obs_dev_impl(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C], dv[i_W], dv[i_B],
                             cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em], dv[i_rf], quantity, npath,
                             dv[i_f], sfc_per_path, g < 0 ? obs : ob->shard[g], (double *)dv[i_vc], dv[o_O], dv[o_y], 8, ends, s->hs);
+    });
+}
+
+// ---- the optimal-estimation step -----------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+constexpr int kOeMaxMeas = 128, kOeMaxState = 2048;
+// rows of the K array of each state kind: K_T, K_TZ, K_W, K_CLW, K_SFC
+void oe_rows(int nlay_max, int njac, long long rows[5]) {
+    rows[0] = nlay_max; rows[1] = (long long)nlay_max + 1; rows[2] = (long long)nlay_max * njac; rows[3] = nlay_max; rows[4] = 3;
+}
+// everything a host can check of a call, before anything is launched (the host entry: before anything is staged on any device)
+int oe_check(Ctx *c, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind, const int *state_row,
+             const void *const K[5], int sa_per_profile, int se_per_profile) {
+    if (c->real_kind != 8) {
+        c->err = "monortm_hip_oe_step needs a real_kind = 8 context (it reads the K arrays of the full Jacobians)";
+        return MONORTM_EUNSUPPORTED;
+    }
+    if (nprof < 1 || nview < 1 || nchan < 1 || nlay_max < 1 || nlay_max > 603 || njac < 0 || njac > MXMOL) { c->err = "bad nprof/nview/nchan/nlay_max/njac"; return MONORTM_EARG; }
+    if ((long long)nview * nchan > kOeMaxMeas) { c->err = "nmeas = nview x nchan outside 1.." + std::to_string(kOeMaxMeas); return MONORTM_EARG; }
+    if (nstate < 1 || nstate > kOeMaxState) { c->err = "nstate outside 1.." + std::to_string(kOeMaxState); return MONORTM_EARG; }
+    if ((sa_per_profile != 0 && sa_per_profile != 1) || (se_per_profile != 0 && se_per_profile != 1)) { c->err = "sa_per_profile / se_per_profile must be 0 or 1"; return MONORTM_EARG; }
+    if (!state_kind || !state_row) { c->err = "null state map"; return MONORTM_EARG; }
+    long long rows[5];
+    oe_rows(nlay_max, njac, rows);
+    static const char *const names[5] = {"K_T", "K_TZ", "K_W", "K_CLW", "K_SFC"};
+    for (int s = 0; s < nstate; s++) {
+        const int k = state_kind[s];
+        if (k < 0 || k > 4) { c->err = "state " + std::to_string(s) + ": kind " + std::to_string(k) + " outside 0..4"; return MONORTM_EARG; }
+        if (state_row[s] < 0 || state_row[s] >= rows[k]) {
+            c->err = "state " + std::to_string(s) + ": row " + std::to_string(state_row[s]) + " outside the " + std::to_string(rows[k]) + " rows of " + names[k];
+            return MONORTM_EARG;
+        }
+        if (!K[k]) { c->err = "state " + std::to_string(s) + " reads " + names[k] + ", which is null"; return MONORTM_EARG; }
+    }
+    return MONORTM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int monortm_hip_oe_step_dev(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                            const int *state_row, const void *K_T, const void *K_TZ, const void *K_W, const void *K_CLW, const void *K_SFC,
+                            const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa, int sa_per_profile, const void *se,
+                            int se_per_profile, const void *gamma, void *x_new, void *post_var, void *avk_diag, void *chi2, int *status,
+                            void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!c->shards.empty()) return multi_only_host(c);
+    const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
+    if (int rc = oe_check(c, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, sa_per_profile, se_per_profile)) return rc;
+    if (!Y || !y_obs || !x || !xa || !Sa || !se || !x_new || !status) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (int rcd = check_device(c)) return rcd;
+    hipStream_t s = (hipStream_t)stream;
+    const int nmeas = nview * nchan;
+    // the state map: kinds, then rows x nchan.  It travels only when it differs from the one the device holds, and then behind
+    // whatever still reads the old one (that wait cannot be captured: the warm call of a capture has brought the map over)
+    std::vector<int> map(2 * (size_t)nstate);
+    for (int i = 0; i < nstate; i++) { map[i] = state_kind[i]; map[nstate + i] = state_row[i] * nchan; }
+    if (map != c->oe_map_host) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        c->oe_map_host.clear();
+        HIPCHK(c, grow(&c->oe_map, &c->oe_map_ints, map.size(), sizeof(int)));
+        HIPCHK(c, hipMemcpy(c->oe_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+        c->oe_map_host = map;
+    }
+    HIPCHK(c, grow(&c->oe_ws, &c->oe_ws_elems, (size_t)nprof * 2 * nmeas * nstate, sizeof(double)));
+    OeArgs a{};
+    a.nprof = nprof; a.nview = nview; a.nchan = nchan; a.nmeas = nmeas; a.nstate = nstate;
+    a.sa_per_profile = sa_per_profile; a.se_per_profile = se_per_profile;
+    long long rows[5];
+    oe_rows(nlay_max, njac, rows);
+    for (int k = 0; k < 5; k++) {
+        a.K[k] = static_cast<const double *>(K[k]);
+        a.vstride[k] = (int)(rows[k] * nchan);
+        a.kstride[k] = (size_t)nview * rows[k] * nchan;
+    }
+    a.map = static_cast<const int *>(c->oe_map);
+    a.Y = (const double *)Y; a.y_obs = (const double *)y_obs; a.x = (const double *)x; a.xa = (const double *)xa; a.Sa = (const double *)Sa;
+    a.se = (const double *)se; a.gamma = (const double *)gamma;
+    a.x_new = (double *)x_new; a.post_var = (double *)post_var; a.avk_diag = (double *)avk_diag; a.chi2 = (double *)chi2; a.status = status;
+    a.ws = static_cast<double *>(c->oe_ws);
+    HIPCHK(c, launch_oe_step(a, s));
+    return MONORTM_OK;
+}
+
+int monortm_hip_oe_step(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                        const int *state_row, const void *K_T, const void *K_TZ, const void *K_W, const void *K_CLW, const void *K_SFC,
+                        const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa, int sa_per_profile, const void *se,
+                        int se_per_profile, const void *gamma, void *x_new, void *post_var, void *avk_diag, void *chi2, int *status) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    DeviceGuard guard;
+    const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
+    if (int rc = oe_check(c, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, sa_per_profile, se_per_profile)) return rc;
+    if (!Y || !y_obs || !x || !xa || !Sa || !se || !x_new || !status) { c->err = "null array argument"; return MONORTM_EARG; }
+    long long rows[5];
+    oe_rows(nlay_max, njac, rows);
+    const size_t d = 8, y = (size_t)nview * nchan * d, n = (size_t)nstate * d;
+    HostCall hc(8);
+    int i_K[5];
+    for (int k = 0; k < 5; k++) i_K[k] = hc.in(K[k], y * rows[k]);
+    const int i_Y = hc.in(Y, y), i_yo = hc.in(y_obs, y), i_x = hc.in(x, n), i_xa = hc.in(xa, n),
+              i_Sa = sa_per_profile ? hc.in(Sa, n * nstate) : hc.in_shared(Sa, n * nstate), i_se = se_per_profile ? hc.in(se, y) : hc.in_shared(se, y),
+              i_g = hc.in(gamma, d);
+    const int o_x = hc.out(x_new, n), o_pv = hc.out(post_var, n), o_av = hc.out(avk_diag, n), o_c2 = hc.out(chi2, d), o_st = hc.out(status, sizeof(int));
+    return hc.run(c, nprof, [&](Ctx *s, int, int np, char *const *dv) {
+        return monortm_hip_oe_step_dev(s, np, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, dv[i_K[0]], dv[i_K[1]], dv[i_K[2]],
+                                       dv[i_K[3]], dv[i_K[4]], dv[i_Y], dv[i_yo], dv[i_x], dv[i_xa], dv[i_Sa], sa_per_profile, dv[i_se],
+                                       se_per_profile, dv[i_g], dv[o_x], dv[o_pv], dv[o_av], dv[o_c2], (int *)dv[o_st], s->hs);
     });
 }
 

@@ -305,6 +305,23 @@ struct XsecJacArgs {
     double two_eps;
 };
 
+// The optimal-estimation step (oe_kernel.hip), real_kind 8.  K[kind] are the K_T, K_TZ, K_W, K_CLW, K_SFC of
+// monortm_hip_obs_jacobian, [nprof][nview][rows][nchan]: kstride = nview x rows x nchan elements per profile, vstride = rows x nchan per
+// view.  map [2][nstate] on the device: the kind of state s, then state_row[s] x nchan - both checked on the host.  Sa [nstate][nstate]
+// (x nprof with sa_per_profile), lower triangle read; se [nmeas] (x nprof with se_per_profile); gamma [nprof] or null.  ws: the
+// workspace, [nprof][2][nmeas][nstate] doubles.  post_var, avk_diag, chi2 may be null.
+struct OeArgs {
+    int nprof, nview, nchan, nmeas, nstate, sa_per_profile, se_per_profile;
+    const double *K[5];
+    size_t kstride[5];
+    int vstride[5];
+    const int *map;
+    const double *Y, *y_obs, *x, *xa, *Sa, *se, *gamma;
+    double *x_new, *post_var, *avk_diag, *chi2;
+    int *status;
+    double *ws;
+};
+
 // exp() and 1/x for the small kernels behind the line sum (radiance recurrences, microwave continuum): Cody-Waite reduction +
 // degree-13 polynomial (the routine of the line kernel's prepare stage: 20 instructions, 1-2 ulp like the library call at ~35)
 // and v_rcp_f64 + two Newton steps (1 ulp; an IEEE division is ~11 instructions).  exp_cw: |n| < 2^31 for every argument that
@@ -512,5 +529,7 @@ void launch_rtm_scan_jac(const RtmScanJacArgs &a, bool full, hipStream_t s);
 void launch_rtm_obs_jac(const RtmObsJacArgs &a, bool full, int out_kind, hipStream_t s);
 // rtm_obs_kernel.hip (out_kind as for launch_rtm_obs_jac)
 void launch_rtm_obs(const RtmObsArgs &a, int out_kind, hipStream_t s);
+// oe_kernel.hip: one launch, one workgroup per profile; raises the kernel's bound on dynamic LDS where nmeas needs it
+hipError_t launch_oe_step(const OeArgs &a, hipStream_t s);
 
 }  // namespace monortm_dev
