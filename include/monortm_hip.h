@@ -626,6 +626,47 @@ int monortm_hip_oe_step_dev(void *ctx, int nprof, int nview, int nchan, int nlay
                             const monortm_real *gamma, monortm_real *x_new, monortm_real *post_var, monortm_real *avk_diag,
                             monortm_real *chi2, int *status, void *stream);
 
+/* ---- The optimal-estimation step with a full Se and the full diagnostics (Rodgers, sections 2.4 and 3.2).  DESIGN.md section 3.14.
+ * Everything monortm_hip_oe_step computes, computed the same way, with
+ *   Se, se_kind     se_kind 0: [nmeas] variances - exactly the se of monortm_hip_oe_step.
+ *                   se_kind 1: [nmeas][nmeas], the measurement-error covariance (e.g. S_y + K_b S_b K_b^T).  ONLY THE LOWER TRIANGLE IS
+ *                   READ.  M = K W + Se;  chi2 = (y_obs - Y)^T Se^-1 (y_obs - Y), from a Cholesky factor of Se.
+ *                   With se_per_profile = 1: [nprof][nmeas] or [nprof][nmeas][nmeas].
+ * and, with a = L^-1 W^T and b = L^-1 K ([nmeas][nstate] each; g = 1 / (1 + gamma)), four more outputs, each of which may be NULL:
+ *   gain_t          [nprof][nmeas][nstate]   G^T = L^-T a = M^-1 W^T: row j is the response of every state element to measurement j
+ *                                            (G = S_hat K^T Se^-1; measurement-major like K)
+ *   avk             [nprof][nstate][nstate]  A = a^T b = G K: avk[i][i'] = d x_hat_i / d x_true_i'
+ *   post_cov        [nprof][nstate][nstate]  S_hat = g Sa - a^T a = [(1 + gamma) Sa^-1 + K^T Se^-1 K]^-1, stored symmetric bit for bit
+ *   dofs            [nprof]                  tr A, the sum of avk_diag in ascending i
+ * diag(avk) is avk_diag and diag(post_cov) is post_var, bit for bit.  With se_kind 0 and the four outputs NULL the call launches what
+ * monortm_hip_oe_step launches: the same bits.  With se_kind 1 and Se = diag(se), x_new, post_var and avk_diag are still the same bits;
+ * chi2 differs by rounding.
+ * A profile fails (status 1) as in monortm_hip_oe_step, and also when the Cholesky of Se meets a pivot <= 0 or not finite: x_new = x and
+ * every diagnostic is 0, the three matrices included.  Other profiles are unaffected, bit for bit; no error of monortm_hip_check.
+ * The step kernel (gain_t: one more phase of it, the back substitution in place) and, for avk / post_cov, one second launch of
+ * oe_cov_kernel over (64 x 64 output tiles, profiles); no atomics, every element one thread's sum in ascending k: the same bits on
+ * repeated calls, alone and in a batch.  The matrices are the caller's memory: 32 MB each per profile at nstate = 2048.
+ * Refused before anything is launched: whatever monortm_hip_oe_step refuses, and se_kind outside 0..1 (MONORTM_EARG).
+ * Host buffers: sharded by profile like monortm_hip_oe_step. */
+int monortm_hip_oe_step_full(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                             const int *state_row, const monortm_real *K_T, const monortm_real *K_TZ, const monortm_real *K_W,
+                             const monortm_real *K_CLW, const monortm_real *K_SFC, const monortm_real *Y, const monortm_real *y_obs,
+                             const monortm_real *x, const monortm_real *xa, const monortm_real *Sa, int sa_per_profile,
+                             const monortm_real *Se, int se_kind, int se_per_profile, const monortm_real *gamma, monortm_real *x_new,
+                             monortm_real *post_var, monortm_real *avk_diag, monortm_real *chi2, int *status, monortm_real *gain_t,
+                             monortm_real *avk, monortm_real *post_cov, monortm_real *dofs);
+/* The same on device pointers, asynchronous on `stream`; one-device context.  Workspace and state map as monortm_hip_oe_step_dev (they
+ * are shared with it); a call that asks for dofs without avk_diag keeps a diagonal [nprof][nstate] of its own.  After one call, a second
+ * of the same shapes, map and outputs allocates and copies nothing (graph capture). */
+int monortm_hip_oe_step_full_dev(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate,
+                                 const int *state_kind /*host*/, const int *state_row /*host*/, const monortm_real *K_T,
+                                 const monortm_real *K_TZ, const monortm_real *K_W, const monortm_real *K_CLW, const monortm_real *K_SFC,
+                                 const monortm_real *Y, const monortm_real *y_obs, const monortm_real *x, const monortm_real *xa,
+                                 const monortm_real *Sa, int sa_per_profile, const monortm_real *Se, int se_kind, int se_per_profile,
+                                 const monortm_real *gamma, monortm_real *x_new, monortm_real *post_var, monortm_real *avk_diag,
+                                 monortm_real *chi2, int *status, monortm_real *gain_t, monortm_real *avk, monortm_real *post_cov,
+                                 monortm_real *dofs, void *stream);
+
 /* Device-side failure flags raised by the kernels of earlier *_dev calls (temperature range, SD-Voigt
  * sign): synchronises `stream`, returns MONORTM_OK or the first error and clears the flags. */
 int monortm_hip_check(void *ctx, void *stream);

@@ -128,6 +128,8 @@ SYMBOLS = {
                                       C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "monortm_hip_oe_step": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int] + [_vp] * 6),
     "monortm_hip_oe_step_dev": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int] + [_vp] * 7),
+    "monortm_hip_oe_step_full": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 10),
+    "monortm_hip_oe_step_full_dev": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 11),
     "monortm_hip_check": (C.c_int, [_vp, _vp]),
     "monortm_hip_profile": (C.c_int, [_vp, C.c_int]),
     "monortm_hip_kernel_time": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_longlong)]),
@@ -229,6 +231,35 @@ def oe_state_map(spec, nlay_max: int, vars=()):
         else:
             row.append(OE_SFC_ROWS[name] if k is None else k)
     return np.ascontiguousarray(kind, np.int32), np.ascontiguousarray(row, np.int32)
+
+
+OE_FULL_WANT = ("gain_t", "avk", "post_cov", "dofs")
+
+
+def oe_se_kind(shape, nprof: int, nmeas: int, se_kind=None):
+    """(se_kind, se_per_profile) of monortm_hip_oe_step_full for an Se of this shape: [nmeas] variances (0, 0), [nprof, nmeas] (0, 1),
+    [nmeas, nmeas] a covariance matrix (1, 0), [nprof, nmeas, nmeas] (1, 1).  ValueError for any other shape, and for [nmeas, nmeas]
+    when nprof = nmeas - both a matrix and per-profile variances - unless se_kind (0 or 1) says which; a se_kind that is given must fit."""
+    shape, m = tuple(int(v) for v in shape), int(nmeas)
+    if se_kind not in (None, 0, 1):
+        raise ValueError(f"se_kind must be None, 0 (variances) or 1 (covariance matrix), got {se_kind!r}")
+    fits = [k for k, s in (((0, 0), (m,)), ((0, 1), (nprof, m)), ((1, 0), (m, m)), ((1, 1), (nprof, m, m))) if s == shape and se_kind in (None, k[0])]
+    if not fits:
+        raise ValueError(f"Se must be [{m}] or [{nprof}, {m}] (se_kind 0), [{m}, {m}] or [{nprof}, {m}, {m}] (se_kind 1), got {list(shape)}"
+                         + ("" if se_kind is None else f" with se_kind = {se_kind}"))
+    if len(fits) > 1:
+        raise ValueError(f"Se {list(shape)} is ambiguous with nprof = nmeas = {m}: per-profile variances or one covariance matrix; "
+                         f"say se_kind = 0 or 1")
+    return fits[0]
+
+
+def _oe_want(want):
+    """The requested diagnostics of oe_step_full in the order of OE_FULL_WANT; ValueError for an unknown name."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [w for w in want if w not in OE_FULL_WANT]
+    if bad:
+        raise ValueError(f"unknown diagnostics {bad}: choose from {list(OE_FULL_WANT)}")
+    return tuple(w for w in OE_FULL_WANT if w in want)
 
 
 def _oe_map_of(state, nlay_max: int, vars):
@@ -915,6 +946,39 @@ class MonoRTM:
         out["dfs"] = out["avk_diag"].sum(axis=1)
         return out
 
+    # ---- the step with a full Se and the full diagnostics (monortm_hip_oe_step_full) ---------------------------------
+    def oe_step_full(self, jac: dict, state, y_obs, x, xa, Sa, Se, gamma=None, want=("avk", "post_cov", "dofs"), se_kind=None) -> dict:
+        """oe_step with Se [nmeas] / [nprof, nmeas] (variances) or [nmeas, nmeas] / [nprof, nmeas, nmeas] (a covariance matrix, lower
+        triangle read; oe_se_kind decides, se_kind settles nprof = nmeas), and the diagnostics named in `want`: "gain_t" [nprof, nmeas, nstate] (G^T), "avk" and "post_cov"
+        [nprof, nstate, nstate], "dofs" [nprof] (tr A).  Dict of x_new, post_var, avk_diag, chi2, status and what was wanted; a failed
+        profile (status 1) has x_new = x and zeros everywhere else."""
+        want = _oe_want(want)
+        kt = jac["k_t"]
+        nprof, nv, lm, nc = kt.shape
+        kw = jac.get("k_w")
+        nj = 0 if kw is None else kw.shape[3]
+        kind, row = _oe_map_of(state, lm, jac.get("vars", ()))
+        n, m = len(kind), nv * nc
+        f = lambda a: None if a is None else _np(a)  # noqa: E731
+        K = [f(jac.get(k)) for k in ("k_t", "k_tz", "k_w", "k_clw", "k_sfc")]
+        if nj == 0:
+            K[2] = None
+        Y, yo, x, xa, Sa, Se, gamma = (f(a) for a in (jac["y"], y_obs, x, xa, Sa, Se, gamma))
+        se_kind, se_pp = oe_se_kind(Se.shape, nprof, m, se_kind)
+        for name, a, shapes in (("y_obs", yo, [(nprof, nv, nc)]), ("x", x, [(nprof, n)]), ("xa", xa, [(nprof, n)]), ("Sa", Sa, [(n, n), (nprof, n, n)]),
+                                ("gamma", gamma, [(nprof,)])):
+            if a is not None and a.shape not in shapes:
+                raise ValueError(f"{name} must be {' or '.join(str(list(s)) for s in shapes)}, got {list(a.shape)}")
+        out = dict(x_new=np.zeros((nprof, n)), post_var=np.zeros((nprof, n)), avk_diag=np.zeros((nprof, n)), chi2=np.zeros(nprof),
+                   status=np.zeros(nprof, np.int32))
+        shapes = dict(gain_t=(nprof, m, n), avk=(nprof, n, n), post_cov=(nprof, n, n), dofs=(nprof,))
+        out.update({w: np.zeros(shapes[w]) for w in want})
+        self._chk(self.lib.monortm_hip_oe_step_full(self.ctx, nprof, nv, nc, lm, nj, n, _ptr(kind), _ptr(row), *[_ptr(k) for k in K], _ptr(Y),
+                                                    _ptr(yo), _ptr(x), _ptr(xa), _ptr(Sa), int(Sa.ndim == 3), _ptr(Se), se_kind, se_pp, _ptr(gamma),
+                                                    *[_ptr(out[k]) for k in ("x_new", "post_var", "avk_diag", "chi2", "status")],
+                                                    *[_ptr(out[w]) if w in want else None for w in OE_FULL_WANT]))
+        return out
+
     # ---- the forward measurement operator (monortm_hip_rtm_obs / monortm_hip_obs; DESIGN.md section 3.10) ------------------------------
     def rtm_obs(self, profiles: list[Profile], O: np.ndarray, path, obs: int, quantity="tb", emiss=None, reflc=None, vcen=None) -> dict:
         """y = F(x) per measurement from one O [nprof, nlay_max, nwn]: the radiances of rtm_scan contracted with the operator `obs`
@@ -1340,6 +1404,51 @@ class DeviceBatch:
             t.sum(out["avk_diag"], dim=1, out=out["dfs"])
         return dict(out)
 
+    def oe_step_full(self, jac: dict, state, y_obs, x, xa, Sa, Se, gamma=None, want=("avk", "post_cov", "dofs"), stream=None, se_kind=None) -> dict:
+        """MonoRTM.oe_step_full on torch tensors, asynchronously, under the rules of oe_step: Se [nmeas] or [nprof, nmeas] (variances),
+        [nmeas, nmeas] or [nprof, nmeas, nmeas] (covariance, lower triangle read) - oe_se_kind decides, ValueError where it cannot (se_kind).
+        The outputs - x_new, post_var, avk_diag, chi2, status and the diagnostics in `want` ("gain_t", "avk", "post_cov", "dofs") - are
+        allocated at the first call for (nprof, nview, nchan, nstate, want) and overwritten by every later one: a graph capture of the
+        call (after one warm call) replays into the same tensors."""
+        t = self.torch
+        want = _oe_want(want)
+        kt = jac["k_t"]
+        nprof, nv, lm, nc = (int(v) for v in kt.shape)
+        kw = jac.get("k_w")
+        nj = 0 if kw is None else int(kw.shape[3])
+        vars = jac.get("vars", ())
+        kind, row = _oe_map_of(state, lm, vars.numpy() if isinstance(vars, t.Tensor) else vars)
+        n, m = len(kind), nv * nc
+        K = [jac.get(k) for k in ("k_t", "k_tz", "k_w", "k_clw", "k_sfc")]
+        if nj == 0:
+            K[2] = None
+        for name, a, shapes in [("y_obs", y_obs, [(nprof, nv, nc)]), ("x", x, [(nprof, n)]), ("xa", xa, [(nprof, n)]), ("Sa", Sa, [(n, n), (nprof, n, n)]),
+                                ("Se", Se, None), ("gamma", gamma, [(nprof,)]), ("y", jac["y"], [(nprof, nv, nc)])] + \
+                               [(f"K[{i}]", k, None) for i, k in enumerate(K)]:
+            if a is None and (name == "gamma" or name.startswith("K[")):
+                continue
+            if not isinstance(a, t.Tensor) or a.dtype != t.float64 or a.device != self.dev or not a.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float64 tensor on {self.dev}")
+            if shapes is not None and tuple(a.shape) not in shapes:
+                raise ValueError(f"{name} must be {' or '.join(str(list(s)) for s in shapes)}, got {list(a.shape)}")
+        se_kind, se_pp = oe_se_kind(Se.shape, nprof, m, se_kind)
+        cache = self.__dict__.setdefault("_oe_full", {})
+        key = (nprof, nv, nc, n, want)
+        if key not in cache:
+            z = lambda *s: t.zeros(*s, dtype=t.float64, device=self.dev)  # noqa: E731
+            shapes = dict(gain_t=(nprof, m, n), avk=(nprof, n, n), post_cov=(nprof, n, n), dofs=(nprof,))
+            cache[key] = dict(x_new=z(nprof, n), post_var=z(nprof, n), avk_diag=z(nprof, n), chi2=z(nprof),
+                              status=t.zeros(nprof, dtype=t.int32, device=self.dev), **{w: z(*shapes[w]) for w in want})
+        out = cache[key]
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        rt = self.rt
+        d = lambda a: None if a is None else _vp(a.data_ptr())  # noqa: E731
+        rt._chk(rt.lib.monortm_hip_oe_step_full_dev(rt.ctx, nprof, nv, nc, lm, nj, n, _ptr(kind), _ptr(row), *[d(k) for k in K], d(jac["y"]),
+                                                    d(y_obs), d(x), d(xa), d(Sa), int(Sa.dim() == 3), d(Se), se_kind, se_pp, d(gamma),
+                                                    *[d(out[k]) for k in ("x_new", "post_var", "avk_diag", "chi2", "status")],
+                                                    *[d(out.get(w)) for w in OE_FULL_WANT], _vp(s.cuda_stream)))
+        return dict(out)
+
     def _oe_resident(self, items):
         """The elements of a retrieval's state by the resident input they live in: [(name, molecule, columns of the state vector, their
         layers / levels, the columns written back, their layers / levels)] - a variable named twice is read into each of its columns and
@@ -1356,7 +1465,8 @@ class DeviceBatch:
             g[2][0 if k is None else k] = col
         return [(name, code, g[0], g[1], list(g[2].values()), list(g[2].keys())) for (name, code), g in groups.items()]
 
-    def retrieve(self, y_obs, path, obs: int, state, xa, Sa, se, gammas=(0,) * 6, mols=None, quantity="tb", keep=False, stream=None) -> dict:
+    def retrieve(self, y_obs, path, obs: int, state, xa, Sa, se=None, gammas=(0,) * 6, mols=None, quantity="tb", keep=False, stream=None,
+                 Se=None, diagnostics=()) -> dict:
         """An optimal-estimation retrieval on the resident batch, one iteration per entry of `gammas` (a scalar or [nprof] each):
         obs_jacobian -> oe_step -> x_new written back into the batch's inputs with torch ops; nothing visits the host.  `state` is a spec
         of oe_state_map over ("t", layers), ("tz", levels), ("w", molecule, layers) - ln of the molecule's amounts -, ("clw", layers) and
@@ -1364,7 +1474,13 @@ class DeviceBatch:
         batch holds.  Written back: T, TZ, CLW and TMPSFC as they are, WKL[..., mol] = exp(x); only layers < nlay[p] (levels <= nlay[p]).
         mols: the Jacobian's variables (default: the molecules of the spec, in the order it names them).  y_obs, xa, Sa, se as oe_step.
         Returns the dict of the last oe_step, plus x (the iterate that step started from), chi2_history [len(gammas), nprof] and, with
-        keep=True, kept: per iteration, clones of y, the k_*, x, x_new and gamma."""
+        keep=True, kept: per iteration, clones of y, the k_*, x, x_new and gamma.
+        Se (in place of se: any shape oe_step_full takes) and / or diagnostics (names of oe_step_full's `want`) send every iteration
+        through oe_step_full; the diagnostics are asked for on the last iteration only and come back in the dict."""
+        diagnostics = _oe_want(diagnostics)
+        if (se is None) == (Se is None):
+            raise ValueError("retrieve: give se (variances) or Se (any shape of oe_step_full), not both")
+        full = Se is not None or bool(diagnostics)
         t = self.torch
         items = _oe_items(state, self.lm)
         groups = self._oe_resident(items)
@@ -1396,7 +1512,11 @@ class DeviceBatch:
                 else:
                     gam.copy_(t.as_tensor(g, dtype=t.float64).expand(self.nprof))
                 jac = self.obs_jacobian(path, obs, mols=mols, quantity=quantity, stream=s)
-                step = self.oe_step(jac, state, y_obs, x, xa, Sa, se, gamma=gam, stream=s)
+                if full:
+                    step = self.oe_step_full(jac, state, y_obs, x, xa, Sa, se if Se is None else Se, gamma=gam,
+                                             want=diagnostics if it + 1 == len(gammas) else (), stream=s)
+                else:
+                    step = self.oe_step(jac, state, y_obs, x, xa, Sa, se, gamma=gam, stream=s)
                 hist.append(step["chi2"].clone())
                 if keep:
                     kept.append(dict({k: jac[k].clone() for k in ("y", "k_t", "k_tz", "k_w", "k_clw", "k_sfc")}, x=x.clone(), x_new=step["x_new"].clone(),

@@ -97,6 +97,9 @@ struct Ctx {
     void *oe_map = nullptr;
     size_t oe_map_ints = 0;
     std::vector<int> oe_map_host;
+    // monortm_hip_oe_step_full_dev asked for dofs without avk_diag: the diagonal that the kernel sums, [nprof][nstate]
+    void *oe_diag = nullptr;
+    size_t oe_diag_elems = 0;
     // measurement operators (monortm_hip_obs_create): the device tables of up to kMaxObs operators, checked on
     // the host when they were created - the kernel never sees an unchecked index, and a call that takes a handle copies nothing
     struct Obs {
@@ -1149,6 +1152,7 @@ void monortm_hip_finalize(void *ctx) {
     if (c->jac_ws) hipFree(c->jac_ws);
     if (c->oe_ws) hipFree(c->oe_ws);
     if (c->oe_map) hipFree(c->oe_map);
+    if (c->oe_diag) hipFree(c->oe_diag);
     for (auto &ob : c->obs)
         if (ob.dev) hipFree(ob.dev);
     for (int i = 0; i < 12; i++)
@@ -2643,20 +2647,19 @@ int oe_check(Ctx *c, int nprof, int nview, int nchan, int nlay_max, int njac, in
     }
     return MONORTM_OK;
 }
-}  // namespace
+int oe_check_kind(Ctx *c, int se_kind) {
+    if (se_kind != 0 && se_kind != 1) { c->err = "se_kind must be 0 ([nmeas] variances) or 1 ([nmeas][nmeas], lower triangle)"; return MONORTM_EARG; }
+    return MONORTM_OK;
+}
 
-extern "C" {
-
-int monortm_hip_oe_step_dev(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
-                            const int *state_row, const void *K_T, const void *K_TZ, const void *K_W, const void *K_CLW, const void *K_SFC,
-                            const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa, int sa_per_profile, const void *se,
-                            int se_per_profile, const void *gamma, void *x_new, void *post_var, void *avk_diag, void *chi2, int *status,
-                            void *stream) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
+// both device entries: se is [nmeas] (se_kind 0) or Se [nmeas][nmeas] (1); gain_t, avk, post_cov, dofs null for monortm_hip_oe_step_dev
+int oe_step_dev_impl(Ctx *c, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind, const int *state_row,
+                     const void *const K[5], const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa, int sa_per_profile,
+                     const void *se, int se_kind, int se_per_profile, const void *gamma, void *x_new, void *post_var, void *avk_diag,
+                     void *chi2, int *status, void *gain_t, void *avk, void *post_cov, void *dofs, void *stream) {
     if (!c->shards.empty()) return multi_only_host(c);
-    const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
     if (int rc = oe_check(c, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, sa_per_profile, se_per_profile)) return rc;
+    if (int rc = oe_check_kind(c, se_kind)) return rc;
     if (!Y || !y_obs || !x || !xa || !Sa || !se || !x_new || !status) { c->err = "null array argument"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
     hipStream_t s = (hipStream_t)stream;
@@ -2673,6 +2676,10 @@ int monortm_hip_oe_step_dev(void *ctx, int nprof, int nview, int nchan, int nlay
         c->oe_map_host = map;
     }
     HIPCHK(c, grow(&c->oe_ws, &c->oe_ws_elems, (size_t)nprof * 2 * nmeas * nstate, sizeof(double)));
+    if (dofs && !avk_diag) {   // the kernel sums the diagonal it stored
+        HIPCHK(c, grow(&c->oe_diag, &c->oe_diag_elems, (size_t)nprof * nstate, sizeof(double)));
+        avk_diag = c->oe_diag;
+    }
     OeArgs a{};
     a.nprof = nprof; a.nview = nview; a.nchan = nchan; a.nmeas = nmeas; a.nstate = nstate;
     a.sa_per_profile = sa_per_profile; a.se_per_profile = se_per_profile;
@@ -2688,8 +2695,42 @@ int monortm_hip_oe_step_dev(void *ctx, int nprof, int nview, int nchan, int nlay
     a.se = (const double *)se; a.gamma = (const double *)gamma;
     a.x_new = (double *)x_new; a.post_var = (double *)post_var; a.avk_diag = (double *)avk_diag; a.chi2 = (double *)chi2; a.status = status;
     a.ws = static_cast<double *>(c->oe_ws);
+    a.se_kind = se_kind; a.gain_t = (double *)gain_t; a.dofs = (double *)dofs;
     HIPCHK(c, launch_oe_step(a, s));
+    OeCovArgs v{};
+    v.nprof = nprof; v.nmeas = nmeas; v.nstate = nstate; v.sa_per_profile = sa_per_profile;
+    v.ws = a.ws; v.Sa = a.Sa; v.gamma = a.gamma; v.status = status;
+    v.avk = (double *)avk; v.post_cov = (double *)post_cov;
+    HIPCHK(c, launch_oe_cov(v, s));   // (no launch without a matrix)
     return MONORTM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int monortm_hip_oe_step_dev(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                            const int *state_row, const void *K_T, const void *K_TZ, const void *K_W, const void *K_CLW, const void *K_SFC,
+                            const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa, int sa_per_profile, const void *se,
+                            int se_per_profile, const void *gamma, void *x_new, void *post_var, void *avk_diag, void *chi2, int *status,
+                            void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
+    return oe_step_dev_impl(c, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, Y, y_obs, x, xa, Sa, sa_per_profile, se, 0,
+                            se_per_profile, gamma, x_new, post_var, avk_diag, chi2, status, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int monortm_hip_oe_step_full_dev(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                                 const int *state_row, const void *K_T, const void *K_TZ, const void *K_W, const void *K_CLW,
+                                 const void *K_SFC, const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa,
+                                 int sa_per_profile, const void *Se, int se_kind, int se_per_profile, const void *gamma, void *x_new,
+                                 void *post_var, void *avk_diag, void *chi2, int *status, void *gain_t, void *avk, void *post_cov, void *dofs,
+                                 void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
+    return oe_step_dev_impl(c, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, Y, y_obs, x, xa, Sa, sa_per_profile, Se,
+                            se_kind, se_per_profile, gamma, x_new, post_var, avk_diag, chi2, status, gain_t, avk, post_cov, dofs, stream);
 }
 
 int monortm_hip_oe_step(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
@@ -2716,6 +2757,37 @@ int monortm_hip_oe_step(void *ctx, int nprof, int nview, int nchan, int nlay_max
         return monortm_hip_oe_step_dev(s, np, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, dv[i_K[0]], dv[i_K[1]], dv[i_K[2]],
                                        dv[i_K[3]], dv[i_K[4]], dv[i_Y], dv[i_yo], dv[i_x], dv[i_xa], dv[i_Sa], sa_per_profile, dv[i_se],
                                        se_per_profile, dv[i_g], dv[o_x], dv[o_pv], dv[o_av], dv[o_c2], (int *)dv[o_st], s->hs);
+    });
+}
+
+int monortm_hip_oe_step_full(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                             const int *state_row, const void *K_T, const void *K_TZ, const void *K_W, const void *K_CLW, const void *K_SFC,
+                             const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa, int sa_per_profile,
+                             const void *Se, int se_kind, int se_per_profile, const void *gamma, void *x_new, void *post_var, void *avk_diag,
+                             void *chi2, int *status, void *gain_t, void *avk, void *post_cov, void *dofs) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    DeviceGuard guard;
+    const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
+    if (int rc = oe_check(c, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, sa_per_profile, se_per_profile)) return rc;
+    if (int rc = oe_check_kind(c, se_kind)) return rc;
+    if (!Y || !y_obs || !x || !xa || !Sa || !Se || !x_new || !status) { c->err = "null array argument"; return MONORTM_EARG; }
+    long long rows[5];
+    oe_rows(nlay_max, njac, rows);
+    const size_t d = 8, m = (size_t)nview * nchan, y = m * d, n = (size_t)nstate * d, e = se_kind ? y * m : y;
+    HostCall hc(8);
+    int i_K[5];
+    for (int k = 0; k < 5; k++) i_K[k] = hc.in(K[k], y * rows[k]);
+    const int i_Y = hc.in(Y, y), i_yo = hc.in(y_obs, y), i_x = hc.in(x, n), i_xa = hc.in(xa, n),
+              i_Sa = sa_per_profile ? hc.in(Sa, n * nstate) : hc.in_shared(Sa, n * nstate), i_se = se_per_profile ? hc.in(Se, e) : hc.in_shared(Se, e),
+              i_g = hc.in(gamma, d);
+    const int o_x = hc.out(x_new, n), o_pv = hc.out(post_var, n), o_av = hc.out(avk_diag, n), o_c2 = hc.out(chi2, d), o_st = hc.out(status, sizeof(int)),
+              o_gn = hc.out(gain_t, m * n), o_ak = hc.out(avk, n * nstate), o_pc = hc.out(post_cov, n * nstate), o_df = hc.out(dofs, d);
+    return hc.run(c, nprof, [&](Ctx *s, int, int np, char *const *dv) {
+        return monortm_hip_oe_step_full_dev(s, np, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, dv[i_K[0]], dv[i_K[1]],
+                                            dv[i_K[2]], dv[i_K[3]], dv[i_K[4]], dv[i_Y], dv[i_yo], dv[i_x], dv[i_xa], dv[i_Sa], sa_per_profile,
+                                            dv[i_se], se_kind, se_per_profile, dv[i_g], dv[o_x], dv[o_pv], dv[o_av], dv[o_c2], (int *)dv[o_st],
+                                            dv[o_gn], dv[o_ak], dv[o_pc], dv[o_df], s->hs);
     });
 }
 

@@ -310,6 +310,9 @@ struct XsecJacArgs {
 // view.  map [2][nstate] on the device: the kind of state s, then state_row[s] x nchan - both checked on the host.  Sa [nstate][nstate]
 // (x nprof with sa_per_profile), lower triangle read; se [nmeas] (x nprof with se_per_profile); gamma [nprof] or null.  ws: the
 // workspace, [nprof][2][nmeas][nstate] doubles.  post_var, avk_diag, chi2 may be null.
+// The full entries (section 3.14): se_kind 1 - se is Se [nmeas][nmeas] (x nprof with se_per_profile), lower triangle read; gain_t
+// [nprof][nmeas][nstate] and dofs [nprof] may be null (dofs is summed from avk_diag, which is not null then).  After the launch the
+// workspace holds b = L^-1 K and a = L^-1 W^T of every profile of status 0: what oe_cov_kernel reads.
 struct OeArgs {
     int nprof, nview, nchan, nmeas, nstate, sa_per_profile, se_per_profile;
     const double *K[5];
@@ -320,6 +323,17 @@ struct OeArgs {
     double *x_new, *post_var, *avk_diag, *chi2;
     int *status;
     double *ws;
+    int se_kind;
+    double *gain_t, *dofs;
+};
+
+// oe_cov_kernel: avk = a^T b and post_cov = g Sa - a^T a, [nprof][nstate][nstate] each (one of them may be null), from the workspace
+// and the status the step kernel left on the same stream.
+struct OeCovArgs {
+    int nprof, nmeas, nstate, sa_per_profile;
+    const double *ws, *Sa, *gamma;
+    const int *status;
+    double *avk, *post_cov;
 };
 
 // exp() and 1/x for the small kernels behind the line sum (radiance recurrences, microwave continuum): Cody-Waite reduction +
@@ -530,6 +544,9 @@ void launch_rtm_obs_jac(const RtmObsJacArgs &a, bool full, int out_kind, hipStre
 // rtm_obs_kernel.hip (out_kind as for launch_rtm_obs_jac)
 void launch_rtm_obs(const RtmObsArgs &a, int out_kind, hipStream_t s);
 // oe_kernel.hip: one launch, one workgroup per profile; raises the kernel's bound on dynamic LDS where nmeas needs it
+// (se_kind 1 and a gain_t select the kernel's other instantiations; neither: the one launch of monortm_hip_oe_step)
 hipError_t launch_oe_step(const OeArgs &a, hipStream_t s);
+// oe_kernel.hip: grid (output tiles, profiles); no launch when both matrices are null
+hipError_t launch_oe_cov(const OeCovArgs &a, hipStream_t s);
 
 }  // namespace monortm_dev

@@ -19,6 +19,20 @@
 //   4  solves    thread per state i: a_i and b_i by forward substitution, OE_KB rows at a time, in place over W and B (coalesced in i), L
 //                broadcast from LDS; the three dot products are accumulated as the rows are finished
 // Workspace: [nprof][2][m][n] doubles (B and W; W does not fit LDS - 2048 x 128 doubles - and phase 4 needs the history of both).
+//
+// The full entries (monortm_hip_oe_step_full[_dev]) launch other instantiations of the same kernel:
+//   SEFULL  Se [m][m], lower triangle read.  Between phases 0 and 1, while nothing else needs the LDS, Se is factored there by the
+//           Cholesky of phase 3 with y - F as the extra row: chi2 = |L_e^-1 (y - F)|^2, summed by thread 0 in ascending j.  A bad pivot of
+//           Se marks the profile like one of M.  Phase 2 adds Se[j][j'] to every element of M's triangle.
+//   GAIN    5  gain  thread per state i, L still in LDS: G^T = L^-T a, gain_t[k][i] = (a[k][i] - sum_{t > k} L[t][k] gain_t[t][i]) / L[k][k]
+//           for k = m - 1 .. 0, t descending, OE_KB rows at a time; a thread reads back only what it stored itself
+// and, with dofs, thread 0 sums avk_diag in ascending i.  After the launch the workspace holds b = L^-1 K and a = L^-1 W^T.
+// oe_cov_kernel, a second launch on the same stream, turns them into the matrices: avk = a^T b, post_cov = g Sa - a^T a.
+// grid = (64 x 64 output tiles, profiles), 256 threads, a 4 x 4 register block per thread and matrix; the a- and b-rows pass through LDS
+// in slabs of OE_CK measurements, laid out [k][64 states]: a wave reads 16 consecutive doubles of one slab row and 4 more as broadcasts,
+// which fall into different bank pairs without the padding the [j][OE_ITP] tiles of phase 2 need.  Every element is one thread's sum in
+// ascending k, formed with the fused multiply-adds phase 4 compiles to: diag(post_cov) and diag(avk) are post_var and avk_diag bit for
+// bit.  post_cov is computed on and below the diagonal tiles and stored with its mirror image; Sa is read from its lower triangle.
 #include <algorithm>
 
 #include "device_common.hpp"
@@ -27,9 +41,35 @@ namespace {
 using namespace monortm_dev;
 
 constexpr int OE_THREADS = 256, OE_ST = 8, OE_JB = 16, OE_KB = 4, OE_IT = 16, OE_ITP = OE_IT + 1, OE_MB = 8;   // (16 OE_MB = the largest m)
+constexpr int OE_CT = 64, OE_CR = 4, OE_CK = 16;   // oe_cov_kernel: tile edge, register block edge (16 OE_CR = OE_CT), slab depth
 
 __device__ __forceinline__ int tri(int i) { return i * (i + 1) / 2; }
 
+// Cholesky in place on the packed lower triangle sM, right-looking, two barriers per column; sU rides along as row m, which leaves
+// L^-1 sU.  A pivot that is <= 0 or not finite sets *sBad and is replaced by 1: no barrier is skipped.  Ends on a barrier.
+__device__ __forceinline__ void oe_cholesky(double *sM, double *sU, int m, int tid, int tx, int ty, int *sBad) {
+    for (int k = 0; k < m; k++) {
+        const int kk = tri(k) + k;
+        double d = sM[kk];
+        if (!(d > 0. && isfinite(d))) {
+            if (tid == 0) *sBad = 1;
+            d = 1.;
+        }
+        const double lkk = sqrt(d);
+        for (int i = k + 1 + tid; i < m; i += OE_THREADS) sM[tri(i) + k] /= lkk;
+        if (tid == OE_THREADS - 1) sU[k] /= lkk;
+        __syncthreads();   // column k of L and u_k are final; everyone has read the pivot
+        if (tid == 0) sM[kk] = lkk;
+        for (int i = k + 1 + ty; i < m; i += 16) {
+            const double lik = sM[tri(i) + k];
+            for (int j = k + 1 + tx; j <= i; j += 16) sM[tri(i) + j] -= lik * sM[tri(j) + k];
+        }
+        for (int j = k + 1 + tid; j < m; j += OE_THREADS) sU[j] -= sM[tri(j) + k] * sU[k];
+        __syncthreads();
+    }
+}
+
+template <bool SEFULL, bool GAIN>
 __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
     extern __shared__ __attribute__((aligned(16))) double oe_lds[];
     __shared__ int sBad;
@@ -45,7 +85,7 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
     const double ginv = gam_ok ? 1. / (1. + gam) : 1.;
     const double *x = a.x + (size_t)p * n, *xa = a.xa + (size_t)p * n;
     const double *Sa = a.Sa + (a.sa_per_profile ? (size_t)p * n * n : 0);
-    const double *se = a.se + (a.se_per_profile ? (size_t)p * m : 0);
+    const double *se = a.se + (a.se_per_profile ? (size_t)p * m * (SEFULL ? m : 1) : 0);   // SEFULL: Se [m][m]
     const double *Y = a.Y + (size_t)p * m, *yo = a.y_obs + (size_t)p * m;
     if (tid == 0) sBad = gam_ok ? 0 : 1;
 
@@ -61,6 +101,22 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
         B[(size_t)j * n + s] = a.K[k][(size_t)p * a.kstride[k] + a.map[n + s] + sJo[k * m + j]];
     }
     __syncthreads();
+
+    const int tx = tid & 15, ty = tid >> 4;
+    double c2full = 0.;   // SEFULL, thread 0: (y - F)^T Se^-1 (y - F)
+    if constexpr (SEFULL) {
+        // ---- Se = L_e L_e^T in the LDS that phase 0 has released and phase 2 does not need yet; u_e = L_e^-1 (y - F) as the extra row
+        for (int e = tid; e < m * m; e += OE_THREADS) {
+            const int j = e / m, jp = e - j * m;
+            if (jp <= j) sM[tri(j) + jp] = se[e];
+        }
+        if (tid < m) sU[tid] = yo[tid] - Y[tid];
+        __syncthreads();
+        oe_cholesky(sM, sU, m, tid, tx, ty, &sBad);
+        if (tid == 0)
+            for (int j = 0; j < m; j++) c2full += sU[j] * sU[j];
+        // (thread 0 has read sU before it reaches the barrier behind phase 1; phase 2 writes the LDS behind that one)
+    }
 
     // ---- 1: W = g Sa K^T
     for (int i0 = 0; i0 < n; i0 += OE_THREADS) {
@@ -97,7 +153,6 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
     // Thread (ty, tx) of the 16 x 16 block owns M[ty + 16 a][tx + 16 b], b <= a, in registers; B and W pass through LDS in tiles of OE_IT
     // states (rows padded to OE_ITP doubles: the 16 rows a wave reads of W fall into 16 different bank pairs).  The tiles lie where M
     // will: M is written when the last tile has been consumed.  Every element is still one thread's sum in ascending i.
-    const int tx = tid & 15, ty = tid >> 4;
     {
         double acc[OE_MB * (OE_MB + 1) / 2];
 #pragma unroll
@@ -130,7 +185,11 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
 #pragma unroll
             for (int b2 = 0; b2 <= a2; b2++) {
                 const int j = ty + 16 * a2, jp = tx + 16 * b2;
-                if (j < m && jp <= j) sM[tri(j) + jp] = j == jp ? acc[a2 * (a2 + 1) / 2 + b2] + se[j] : acc[a2 * (a2 + 1) / 2 + b2];
+                if constexpr (SEFULL) {
+                    if (j < m && jp <= j) sM[tri(j) + jp] = acc[a2 * (a2 + 1) / 2 + b2] + se[(size_t)j * m + jp];
+                } else {
+                    if (j < m && jp <= j) sM[tri(j) + jp] = j == jp ? acc[a2 * (a2 + 1) / 2 + b2] + se[j] : acc[a2 * (a2 + 1) / 2 + b2];
+                }
             }
     }
     if (tid < m) {
@@ -143,33 +202,19 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
     __syncthreads();
 
     // ---- 3: Cholesky in place, u = L^-1 r as row m
-    for (int k = 0; k < m; k++) {
-        const int kk = tri(k) + k;
-        double d = sM[kk];
-        if (!(d > 0. && isfinite(d))) {
-            if (tid == 0) sBad = 1;
-            d = 1.;
-        }
-        const double lkk = sqrt(d);
-        for (int i = k + 1 + tid; i < m; i += OE_THREADS) sM[tri(i) + k] /= lkk;
-        if (tid == OE_THREADS - 1) sU[k] /= lkk;
-        __syncthreads();   // column k of L and u_k are final; everyone has read the pivot
-        if (tid == 0) sM[kk] = lkk;
-        for (int i = k + 1 + ty; i < m; i += 16) {
-            const double lik = sM[tri(i) + k];
-            for (int j = k + 1 + tx; j <= i; j += 16) sM[tri(i) + j] -= lik * sM[tri(j) + k];
-        }
-        for (int j = k + 1 + tid; j < m; j += OE_THREADS) sU[j] -= sM[tri(j) + k] * sU[k];
-        __syncthreads();
-    }
+    oe_cholesky(sM, sU, m, tid, tx, ty, &sBad);
     const bool bad = sBad != 0;
     if (tid == 0) {
         double c2 = 0.;
-        if (!bad)
-            for (int j = 0; j < m; j++) {
-                const double dy = yo[j] - Y[j];
-                c2 += dy * dy / se[j];
-            }
+        if constexpr (SEFULL) {
+            if (!bad) c2 = c2full;
+        } else {
+            if (!bad)
+                for (int j = 0; j < m; j++) {
+                    const double dy = yo[j] - Y[j];
+                    c2 += dy * dy / se[j];
+                }
+        }
         if (a.chi2) a.chi2[p] = c2;
         a.status[p] = bad ? 1 : 0;
     }
@@ -227,6 +272,150 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
         if (a.post_var) a.post_var[o] = Sa[(size_t)i * n + i] * ginv - pv;
         if (a.avk_diag) a.avk_diag[o] = av;
     }
+
+    // ---- 5: the gain, G^T = L^-T a: back substitution from the last row up, OE_KB rows at a time (thread i reads the a[k][i] and the
+    // gain_t[t][i] that it stored itself)
+    if constexpr (GAIN) {
+        double *G = a.gain_t + (size_t)p * mn;
+        for (int i = tid; i < n; i += OE_THREADS) {
+            if (bad) {
+                for (int k = 0; k < m; k++) G[(size_t)k * n + i] = 0.;
+                continue;
+            }
+            for (int kb = (m - 1) / OE_KB * OE_KB; kb >= 0; kb -= OE_KB) {
+                double g[OE_KB];
+#pragma unroll
+                for (int r = 0; r < OE_KB; r++) g[r] = W[(size_t)min(kb + r, m - 1) * n + i];
+                for (int t = m - 1; t >= kb + OE_KB; t--) {
+                    const double gt = G[(size_t)t * n + i];
+                    const double *lt = sM + tri(t) + kb;   // (t >= kb + OE_KB: columns kb .. kb + OE_KB - 1 of row t exist)
+#pragma unroll
+                    for (int r = 0; r < OE_KB; r++) g[r] -= lt[r] * gt;
+                }
+#pragma unroll
+                for (int r = OE_KB - 1; r >= 0; r--) {
+                    if (kb + r < m) {
+#pragma unroll
+                        for (int q = OE_KB - 1; q > r; q--)
+                            if (kb + q < m) g[r] -= sM[tri(kb + q) + kb + r] * g[q];
+                        g[r] /= sM[tri(kb + r) + kb + r];
+                        G[(size_t)(kb + r) * n + i] = g[r];
+                    }
+                }
+            }
+        }
+    }
+
+    // ---- the degrees of freedom for signal: avk_diag (not null with dofs: the entry sees to that) summed by one thread, i ascending
+    if (a.dofs) {
+        __syncthreads();   // the block's stores to avk_diag are visible to thread 0
+        if (tid == 0) {
+            double sum = 0.;
+            for (int i = 0; i < n; i++) sum += a.avk_diag[(size_t)p * n + i];
+            a.dofs[p] = sum;
+        }
+    }
+}
+
+// The matrices of a profile from its a = L^-1 W^T and b = L^-1 K, [m][n] each in the workspace.  Tile (ti, tj) of 64 x 64 outputs:
+// thread (ty, tx) owns rows i0 + ty + 16 r and columns j0 + tx + 16 c.  COV tiles above the diagonal have nothing to do: the tile below
+// stores their elements as its mirror image.
+template <bool AVK, bool COV>
+__global__ __launch_bounds__(OE_THREADS) void oe_cov_kernel(OeCovArgs a, int p0) {
+    __shared__ double sAi[OE_CK][OE_CT], sAj[COV ? OE_CK : 1][OE_CT], sBj[AVK ? OE_CK : 1][OE_CT];
+    const int m = a.nmeas, n = a.nstate, tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int nt = (n + OE_CT - 1) / OE_CT, ti = blockIdx.x / nt, tj = blockIdx.x - ti * nt;
+    const int p = p0 + blockIdx.y, i0 = ti * OE_CT, j0 = tj * OE_CT;
+    const bool cov = COV && ti >= tj;
+    if (!AVK && !cov) return;
+    const size_t mn = (size_t)m * n, nn = (size_t)n * n;
+    const double *Bm = a.ws + (size_t)p * 2 * mn, *Am = Bm + mn;
+    double *avk = AVK ? a.avk + (size_t)p * nn : nullptr, *pc = COV ? a.post_cov + (size_t)p * nn : nullptr;
+    if (a.status[p] != 0) {   // a failed profile: zeros (its workspace holds no a and b)
+#pragma unroll
+        for (int r = 0; r < OE_CR; r++)
+#pragma unroll
+            for (int c = 0; c < OE_CR; c++) {
+                const int i = i0 + ty + 16 * r, j = j0 + tx + 16 * c;
+                if (i < n && j < n) {
+                    if (AVK) avk[(size_t)i * n + j] = 0.;
+                    if (cov) pc[(size_t)i * n + j] = pc[(size_t)j * n + i] = 0.;
+                }
+            }
+        return;
+    }
+    double accA[OE_CR][OE_CR], accP[OE_CR][OE_CR];
+#pragma unroll
+    for (int r = 0; r < OE_CR; r++)
+#pragma unroll
+        for (int c = 0; c < OE_CR; c++) accA[r][c] = accP[r][c] = 0.;
+    // A thread moves column ii of slab rows kq, kq + 4, ..: the next slab is fetched into registers while this one is consumed
+    constexpr int OE_CQ = OE_CK * OE_CT / OE_THREADS;
+    const int ii = tid & (OE_CT - 1), kq = tid / OE_CT;
+    const bool in_i = i0 + ii < n, in_j = j0 + ii < n;
+    double pa[OE_CQ], pj[OE_CQ], pb[OE_CQ];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int q = 0; q < OE_CQ; q++) {
+            const int k = k0 + kq + q * (OE_THREADS / OE_CT);
+            const size_t row = (size_t)min(k, m - 1) * n;
+            pa[q] = k < m && in_i ? Am[row + i0 + ii] : 0.;
+            if (cov) pj[q] = k < m && in_j ? Am[row + j0 + ii] : 0.;
+            if (AVK) pb[q] = k < m && in_j ? Bm[row + j0 + ii] : 0.;
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < m; k0 += OE_CK) {
+        const int kn = min(OE_CK, m - k0);
+        __syncthreads();   // the slab before is consumed
+#pragma unroll
+        for (int q = 0; q < OE_CQ; q++) {
+            const int kk = kq + q * (OE_THREADS / OE_CT);
+            sAi[kk][ii] = pa[q];
+            if (cov) sAj[kk][ii] = pj[q];
+            if (AVK) sBj[kk][ii] = pb[q];
+        }
+        __syncthreads();
+        if (k0 + OE_CK < m) fetch(k0 + OE_CK);
+        for (int kk = 0; kk < kn; kk++) {
+            double ai[OE_CR], aj[OE_CR], bj[OE_CR];
+#pragma unroll
+            for (int r = 0; r < OE_CR; r++) {
+                ai[r] = sAi[kk][ty + 16 * r];
+                if (cov) aj[r] = sAj[kk][tx + 16 * r];
+                if (AVK) bj[r] = sBj[kk][tx + 16 * r];
+            }
+#pragma unroll
+            for (int r = 0; r < OE_CR; r++)
+#pragma unroll
+                for (int c = 0; c < OE_CR; c++) {
+                    if (AVK) accA[r][c] = fma(ai[r], bj[c], accA[r][c]);
+                    if (cov) accP[r][c] = fma(ai[r], aj[c], accP[r][c]);
+                }
+        }
+    }
+    double ginv = 1.;
+    const double *Sa = nullptr;
+    if (COV) {
+        const double gam = a.gamma ? a.gamma[p] : 0.;
+        ginv = 1. / (1. + gam);   // (status 0: gamma is finite and >= 0)
+        Sa = a.Sa + (a.sa_per_profile ? (size_t)p * nn : 0);
+    }
+#pragma unroll
+    for (int r = 0; r < OE_CR; r++)
+#pragma unroll
+        for (int c = 0; c < OE_CR; c++) {
+            const int i = i0 + ty + 16 * r, j = j0 + tx + 16 * c;
+            if (i < n && j < n) {
+                if (AVK) avk[(size_t)i * n + j] = accA[r][c];
+                if (cov) {
+                    // (a diagonal tile holds both (i, j) and (j, i): the same products in the same order, the same Sa element)
+                    const double v = fma(Sa[i >= j ? (size_t)i * n + j : (size_t)j * n + i], ginv, -accP[r][c]);
+                    pc[(size_t)i * n + j] = v;
+                    if (ti > tj) pc[(size_t)j * n + i] = v;
+                }
+            }
+        }
 }
 
 }  // namespace
@@ -238,13 +427,37 @@ static size_t oe_lds_bytes(int nmeas) {
     return sizeof(double) * (std::max(std::max(m * (m + 1) / 2, 2 * m * OE_ITP), (5 * m + 1) / 2) + m);
 }
 
-hipError_t launch_oe_step(const OeArgs &a, hipStream_t s) {
+template <bool SEFULL, bool GAIN>
+static hipError_t launch_oe_step_as(const OeArgs &a, hipStream_t s) {
     const size_t lds = oe_lds_bytes(a.nmeas);
     if (lds > (64u << 10)) {   // m >= 127: beyond the default bound of a launch's dynamic LDS
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(oe_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(oe_step_kernel<SEFULL, GAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(oe_step_kernel, dim3((unsigned)a.nprof), dim3(OE_THREADS), lds, s, a);
+    hipLaunchKernelGGL((oe_step_kernel<SEFULL, GAIN>), dim3((unsigned)a.nprof), dim3(OE_THREADS), lds, s, a);
     return hipGetLastError();
+}
+
+hipError_t launch_oe_step(const OeArgs &a, hipStream_t s) {
+    if (a.se_kind) return a.gain_t ? launch_oe_step_as<true, true>(a, s) : launch_oe_step_as<true, false>(a, s);
+    return a.gain_t ? launch_oe_step_as<false, true>(a, s) : launch_oe_step_as<false, false>(a, s);
+}
+
+template <bool AVK, bool COV>
+static hipError_t launch_oe_cov_as(const OeCovArgs &a, hipStream_t s) {
+    const unsigned nt = (unsigned)((a.nstate + OE_CT - 1) / OE_CT);
+    for (int p0 = 0; p0 < a.nprof; p0 += 65535) {   // (the bound of a grid's second dimension)
+        hipLaunchKernelGGL((oe_cov_kernel<AVK, COV>), dim3(nt * nt, (unsigned)std::min(65535, a.nprof - p0)), dim3(OE_THREADS), 0, s, a, p0);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_oe_cov(const OeCovArgs &a, hipStream_t s) {
+    if (a.avk && a.post_cov) return launch_oe_cov_as<true, true>(a, s);
+    if (a.avk) return launch_oe_cov_as<true, false>(a, s);
+    if (a.post_cov) return launch_oe_cov_as<false, true>(a, s);
+    return hipSuccess;
 }
 }  // namespace monortm_dev

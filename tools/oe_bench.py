@@ -1,7 +1,7 @@
 """Time of the optimal-estimation step (monortm_hip_oe_step_dev) on the configs[3] shape
 (bench.build_workload("c4"): 1024 profiles x 64 layers x 50 channels x 500 lines, f64), against what surrounds and what replaces it.
 
-    python tools/oe_bench.py [--calls 20] [--warmup 3] [--out FILE]
+    python tools/oe_bench.py [--calls 20] [--warmup 3] [--full] [--out FILE]
 
 Operators of 14 channels (the 50 wavenumbers in runs of 3 or 4) and 1 or 6 views of 4 paths: m = 14 and 84 measurements.  States:
 n = 64 (T of every layer), 130 (T, ln H2O, TMPSFC, EMISS), 200 (T, TZ, ln H2O, 4 layers of CLW, TMPSFC, EMISS, REFLC).  Sa is
@@ -12,6 +12,12 @@ Per m, device-event times of the variants, one of each in turn (interleaved, aft
   t<n>   the same algebra in torch: K gathered dense (cat + index), matmul, torch.linalg.cholesky and one cholesky_solve of
          [W^T | r], which gives z and the diagnostics (W_i . M^-1 W_i, K_i . M^-1 W_i).  A variant the libraries refuse (a failed
          workspace allocation has been seen) is dropped and its error recorded.
+With --full (monortm_hip_oe_step_full_dev; Se = 0.25 exp(-|j - j'| / 1.5), one matrix for the batch) also
+  f<n>   DeviceBatch.oe_step_full with the variances se and nothing wanted: the launch of k<n> through the other entry;
+  s<n>   the full Se, nothing wanted: the second Cholesky and M's off-diagonals;
+  c<n>   the full Se + avk + post_cov + dofs: the second launch, oe_cov_kernel;
+  g<n>   the full Se + avk + post_cov + dofs + gain_t: the back substitution on top;
+  u<n>   the algebra of c<n> in torch on a gathered K: cholesky, cholesky_solve of W^T, and the two matmul that form A and S_hat.
 Median / min / max / IQR of each, the largest difference of x_new between k and t relative to max |x_new - x|, and the number of
 profiles with status 1.  Prints one JSON line."""
 from __future__ import annotations
@@ -71,7 +77,18 @@ def torch_step(torch, jac, rowidx, y_obs, x, xa, Sa, se, gam):
                 avk_diag=(K * Wt).sum(1), chi2=(dy * dy / se).sum(1))
 
 
-def run_case(api, rt, profs, nview, calls, warmup):
+def torch_full(torch, jac, rowidx, x, Sa, Se, gam):
+    """avk and post_cov as torch forms them: G^T = M^-1 W^T by cholesky_solve, A = G K, S_hat = g Sa - W G^T."""
+    kall = torch.cat([jac["k_t"], jac["k_tz"], jac["k_w"].flatten(2, 3), jac["k_clw"], jac["k_sfc"]], dim=2)
+    K = kall[:, :, rowidx, :].permute(0, 1, 3, 2).reshape(x.shape[0], -1, x.shape[1])        # [nprof][m][n]
+    g = (1.0 / (1.0 + gam))[:, None, None]
+    W = torch.matmul(Sa, K.transpose(1, 2)) * g
+    L = torch.linalg.cholesky(torch.matmul(K, W) + Se)
+    Gt = torch.cholesky_solve(W.transpose(1, 2), L)                                          # [nprof][m][n]
+    return dict(avk=torch.matmul(Gt.transpose(1, 2), K), post_cov=Sa[None] * g - torch.matmul(W, Gt))
+
+
+def run_case(api, rt, profs, nview, calls, warmup, full=False):
     import torch
 
     db = api.DeviceBatch(rt, profs)
@@ -90,6 +107,8 @@ def run_case(api, rt, profs, nview, calls, warmup):
     up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev)  # noqa: E731
     y_obs = jac["y"] + up(rng.normal(0.0, 0.5, (nprof, nview, NCHAN)))
     se, gam = up(np.full(m, 0.25)), up(np.zeros(nprof))
+    jm = np.arange(m)
+    Se = up(0.25 * np.exp(-np.abs(jm[:, None] - jm[None, :]) / 1.5))
     rows = np.concatenate([[0], np.cumsum([lm, lm + 1, lm, lm, 3])])      # row offsets of the kinds in the concatenated K (njac = 1)
     cases, variants, held = {}, {"a": lambda: db.obs_jacobian(fd, h, mols=(1,))}, {}
     for n, spec in specs(lm).items():
@@ -102,6 +121,11 @@ def run_case(api, rt, profs, nview, calls, warmup):
         cases[n] = c
         variants[f"k{n}"] = lambda c=c, n=n: held.__setitem__(f"k{n}", db.oe_step(jac, c["state"], y_obs, c["x"], c["xa"], c["Sa"], se, gamma=gam))
         variants[f"t{n}"] = lambda c=c, n=n: held.__setitem__(f"t{n}", torch_step(torch, jac, c["rowidx"], y_obs, c["x"], c["xa"], c["Sa"], se, gam))
+        if full:
+            for tag, e, want in (("f", se, ()), ("s", Se, ()), ("c", Se, ("avk", "post_cov", "dofs")), ("g", Se, ("avk", "post_cov", "dofs", "gain_t"))):
+                variants[f"{tag}{n}"] = lambda c=c, n=n, tag=tag, e=e, want=want: held.__setitem__(
+                    f"{tag}{n}", db.oe_step_full(jac, c["state"], y_obs, c["x"], c["xa"], c["Sa"], e, gamma=gam, want=want))
+            variants[f"u{n}"] = lambda c=c, n=n: held.__setitem__(f"u{n}", torch_full(torch, jac, c["rowidx"], c["x"], c["Sa"], Se, gam))
     refused = {}
     for k in list(variants):
         try:
@@ -125,8 +149,10 @@ def run_case(api, rt, profs, nview, calls, warmup):
     torch.cuda.synchronize()
     db.check()
     res = dict(nprof=nprof, nlay=lm, nwn=nwn, npath=npath, nview=nview, nchan=NCHAN, nmeas=m, refused=refused)
+    names = dict(a="obs_jacobian_njac1_ms", k="oe_step_ms_n", t="torch_ms_n", f="full_variances_ms_n", s="full_se_ms_n", c="full_se_avk_cov_ms_n",
+                 g="full_se_avk_cov_gain_ms_n", u="torch_avk_cov_ms_n")
     for k in variants:
-        res[{"a": "obs_jacobian_njac1_ms"}.get(k, ("oe_step_ms_n" if k[0] == "k" else "torch_ms_n") + k[1:])] = stats([a.elapsed_time(b) for a, b in ev[k]])
+        res[names[k[0]] + k[1:]] = stats([a.elapsed_time(b) for a, b in ev[k]])
     for n, c in cases.items():
         f = variants[f"k{n}"]
         f()       # (the cached outputs hold the last shape's values only while it is the last to run)
@@ -137,6 +163,14 @@ def run_case(api, rt, profs, nview, calls, warmup):
             res[f"max_diff_post_var_n{n}"] = float((k["post_var"] - t["post_var"]).abs().max().item())
         res[f"failed_profiles_n{n}"] = int(k["status"].sum().item())
         res[f"workspace_bytes_n{n}"] = nprof * 2 * m * n * 8
+        if full and f"c{n}" in variants:
+            variants[f"c{n}"]()
+            cg, u = held[f"c{n}"], held.get(f"u{n}")
+            if u is not None:
+                res[f"max_diff_avk_n{n}"] = float((cg["avk"] - u["avk"]).abs().max().item())
+                res[f"rel_diff_post_cov_n{n}"] = float((cg["post_cov"] - u["post_cov"]).abs().max().item()) / float(c["Sa"].diagonal().max().item())
+            res[f"failed_profiles_full_n{n}"] = int(cg["status"].sum().item())
+            res[f"matrix_bytes_n{n}"] = nprof * n * n * 8
     torch.cuda.synchronize()
     rt.obs_destroy(h)
     return res
@@ -147,6 +181,7 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--views", default="1,6")
+    ap.add_argument("--full", action="store_true", help="also time DeviceBatch.oe_step_full and the torch route to avk and post_cov")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -165,7 +200,7 @@ def main():
         tape3.write_tape3(t3, rec)
         rt = api.MonoRTM(t3, wn[0], wn[-1], device=0)
         for nview in (int(v) for v in args.views.split(",")):
-            res["cases"][str(nview * NCHAN)] = run_case(api, rt, profs, nview, args.calls, args.warmup)
+            res["cases"][str(nview * NCHAN)] = run_case(api, rt, profs, nview, args.calls, args.warmup, args.full)
             torch.cuda.empty_cache()
         rt.close()
     line = json.dumps(res)
