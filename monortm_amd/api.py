@@ -502,6 +502,14 @@ def _ptr(a):
     return a.ctypes.data_as(_vp) if a is not None else None
 
 
+def pack_layers(profiles, lm: int, get, width=None, dtype=np.float64) -> np.ndarray:
+    """get(p) [nlay] (or [nlay, width]) of every profile, zero-padded to lm layers: [nprof, lm] (or [nprof, lm, width])."""
+    out = np.zeros((len(profiles), lm) if width is None else (len(profiles), lm, width), dtype)
+    for i, p in enumerate(profiles):
+        out[i, : p.nlay] = get(p)
+    return out
+
+
 def tape3_probe(path: str, v1: float, v2: float):
     """Host-only TAPE3 parse (no GPU): -> (n_physical[40], n_entries[40], n_coupled[40]) numpy int64 arrays."""
     lib = load_library()
@@ -574,35 +582,22 @@ class MonoRTM:
             from . import xsec
 
             self.set_xsec(xsec.load_tables(p0.xs_dir, p0.xs_names, float(p0.wn.min()), float(p0.wn.max())))
-        nprof, nwn, nmol = len(profiles), p0.nwn, p0.nmol
+        nprof, nwn = len(profiles), p0.nwn
         nlay = np.array([p.nlay for p in profiles], np.int32)
         lm = int(nlay.max())
-
-        def pack(get, width=None):
-            shape = (nprof, lm) if width is None else (nprof, lm, width)
-            out = np.zeros(shape, self.dtype)
-            for i, p in enumerate(profiles):
-                out[i, : p.nlay] = get(p)
-            return out
-
-        P, T, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.t), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
-        WKL = pack(lambda p: p.wkl, nmol)
+        nmol, P, T, CLW, WKL, WB, fac = self._pack_atm(profiles, lm)
         O = np.empty((nprof, lm, nwn), self.dtype)
         OBM = np.empty((nprof, lm, nmol, nwn), self.dtype)
         OC = np.empty((nprof, lm, NCONT, nwn), self.dtype)
         OCLW = np.empty((nprof, lm, nwn), self.dtype)
-        wn = _np(p0.wn)
-        fac = _np(p0.cntnm)
+        lead = (self.ctx, nprof, nwn, _ptr(_np(p0.wn)), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T), _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac),
+                p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd)
         if ixsect == 1 and p0.xs_names:
-            XA = pack(lambda p: p.xamnt, len(p0.xs_names))
+            XA = pack_layers(profiles, lm, lambda p: p.xamnt, len(p0.xs_names), self.dtype)
             ODX = np.empty((nprof, lm, nwn), self.dtype)
-            self._chk(self.lib.monortm_hip_modm_xs(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T),
-                                                   _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd,
-                                                   1, _ptr(XA), _ptr(ODX), _ptr(O), _ptr(OBM), _ptr(OC), _ptr(OCLW)))
+            self._chk(self.lib.monortm_hip_modm_xs(*lead, 1, _ptr(XA), _ptr(ODX), _ptr(O), _ptr(OBM), _ptr(OC), _ptr(OCLW)))
             return O, OBM, OC, OCLW, ODX
-        self._chk(self.lib.monortm_hip_modm(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T),
-                                            _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd,
-                                            ixsect, _ptr(O), _ptr(OBM), _ptr(OC), _ptr(OCLW)))
+        self._chk(self.lib.monortm_hip_modm(*lead, ixsect, _ptr(O), _ptr(OBM), _ptr(OC), _ptr(OCLW)))
         return O, OBM, OC, OCLW
 
     def rtm(self, profiles: list[Profile], O: np.ndarray):
@@ -702,6 +697,22 @@ class MonoRTM:
         rf = _np(np.stack([p.reflc for p in profiles]), dt)
         return nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf
 
+    def _pack_atm(self, profiles: list[Profile], lm: int):
+        """The MODM inputs of a batch, zero-padded to lm layers, and the continuum factors of profiles[0]: nmol, P, T, CLW, WKL, WB, fac."""
+        nmol = profiles[0].nmol
+        P, T, CLW, WB = (pack_layers(profiles, lm, g, None, self.dtype) for g in (lambda p: p.p, lambda p: p.t, lambda p: p.clw, lambda p: p.wbrodl))
+        return nmol, P, T, CLW, pack_layers(profiles, lm, lambda p: p.wkl, nmol, self.dtype), WB, _np(profiles[0].cntnm)
+
+    def _full_args(self, profiles: list[Profile], rtm, atm, em, rf, xargs=()):
+        """The leading arguments of the entries that run MODM and RTM in one call (monortm_hip_jacobian*, _scan_jacobian*, _obs_jacobian*,
+        _obs): ctx, nprof ... ibrd, xargs (what ixsect adds), irt, TZ, tmpsfc, emiss, reflc - from _pack_rtm, _pack_atm and the call's
+        emissivities.  The pointers keep their arrays alive."""
+        nprof, nwn, nlay, lm, irt, _, TZ, ts, _, _ = rtm
+        nmol, P, T, CLW, WKL, WB, fac = atm
+        p0 = profiles[0]
+        return (self.ctx, nprof, nwn, _ptr(_np(p0.wn)), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T), _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac),
+                p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, *xargs, _ptr(irt), _ptr(TZ), _ptr(ts), _ptr(em), _ptr(rf))
+
     def rtm_jacobian(self, profiles: list[Profile], O: np.ndarray, quantity="tb") -> dict:
         """The adjoint of RTM alone, given the optical depths O [nprof, nlay_max, nwn]: dict of rad, tb [nprof, nwn], k_o, k_t (Planck
         term only) [nprof, nlay_max, nwn], k_tz [nprof, nlay_max + 1, nwn], k_sfc [nprof, 3, nwn] (d/dTMPSFC, d/dEMISS, d/dREFLC).
@@ -730,10 +741,7 @@ class MonoRTM:
             from . import xsec
 
             self.set_xsec(xsec.load_tables(p0.xs_dir, p0.xs_names, float(p0.wn.min()), float(p0.wn.max())))
-        names = p0.xs_names or []
-        XA = np.zeros((len(profiles), lm, len(names)), self.dtype)
-        for i, p in enumerate(profiles):
-            XA[i, : p.nlay] = p.xamnt
+        XA = pack_layers(profiles, lm, lambda p: p.xamnt, len(p0.xs_names or []), self.dtype)
         return "_xs", (1, _ptr(XA)), XA
 
     def jacobian(self, profiles: list[Profile], mols=(1,), quantity="tb", ixsect: int = 0, xs_entry: bool = False) -> dict:
@@ -746,30 +754,18 @@ class MonoRTM:
         ixsect = 1 (the tables are those of set_xsec): o, k_o and every slot include the cross-section
         molecules, k_t and the "p" slot their own T and P dependence, and mols accepts "xs:<NAME>" (a name of profiles[0].xs_names)
         or JVAR_XS0 + x: d/d ln XAMNT of that molecule.  Likewise for scan_jacobian and obs_jacobian; not for DeviceBatch."""
-        p0 = profiles[0]
-        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
-        nmol, dt = p0.nmol, self.dtype
-
-        def pack(get, width=None):
-            out = np.zeros((nprof, lm) if width is None else (nprof, lm, width), dt)
-            for i, p in enumerate(profiles):
-                out[i, : p.nlay] = get(p)
-            return out
-
-        P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
-        WKL = pack(lambda p: p.wkl, nmol)
-        jm = jac_codes(mols, p0.xs_names)
+        rtm = self._pack_rtm(profiles)
+        nprof, nwn, _, lm, _, _, _, _, em, rf = rtm
+        dt = self.dtype
+        jm = jac_codes(mols, profiles[0].xs_names)
         sfx, xargs, _xa = self._jac_xs(profiles, ixsect, xs_entry, lm)   # (_xa: xamnt, alive during the call)
         nj = len(jm)
         out = dict(o=np.zeros((nprof, lm, nwn), dt), rad=np.zeros((nprof, nwn), dt), tb=np.zeros((nprof, nwn), dt),
                    k_t=np.zeros((nprof, lm, nwn), dt), k_tz=np.zeros((nprof, lm + 1, nwn), dt), k_w=np.zeros((nprof, lm, nj, nwn), dt),
                    k_clw=np.zeros((nprof, lm, nwn), dt), k_o=np.zeros((nprof, lm, nwn), dt), k_sfc=np.zeros((nprof, 3, nwn), dt))
-        wn, fac = _np(p0.wn), _np(p0.cntnm)
-        self._chk(getattr(self.lib, "monortm_hip_jacobian" + sfx)(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T),
-                _ptr(CLW),
-                                                _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, *xargs, _ptr(irt), _ptr(TZ),
-                                                _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj, _ptr(jm) if nj else None,
-                                                *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS]))
+        self._chk(getattr(self.lib, "monortm_hip_jacobian" + sfx)(*self._full_args(profiles, rtm, self._pack_atm(profiles, lm), em, rf, xargs),
+                                                                  _quantity(quantity), nj, _ptr(jm) if nj else None,
+                                                                  *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS]))
         out["vars"] = jm
         return out
 
@@ -808,34 +804,22 @@ class MonoRTM:
         8): the fields of rtm_scan_jacobian with the optical-depth term in k_t, plus o [nprof, nlay_max, nwn] (the vertical optical
         depths), k_w [nprof, npath, nlay_max, len(mols), nwn] and k_clw [nprof, npath, nlay_max, nwn] - derivatives with respect to
         the batch's own (vertical) ln WKL and CLW."""
-        p0 = profiles[0]
-        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
-        nmol, dt = p0.nmol, self.dtype
+        rtm = self._pack_rtm(profiles)
+        nprof, nwn, _, lm, _, _, _, _, em, rf = rtm
+        dt = self.dtype
         f = self._path(path, nprof, lm)
         npath = f.shape[1]
         em, rf = self._scan_sfc(em, rf, emiss, reflc, nprof, npath, nwn)
-
-        def pack(get, width=None):
-            out = np.zeros((nprof, lm) if width is None else (nprof, lm, width), dt)
-            for i, p in enumerate(profiles):
-                out[i, : p.nlay] = get(p)
-            return out
-
-        P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
-        WKL = pack(lambda p: p.wkl, nmol)
-        jm = jac_codes(mols, p0.xs_names)
+        jm = jac_codes(mols, profiles[0].xs_names)
         sfx, xargs, _xa = self._jac_xs(profiles, ixsect, xs_entry, lm)   # (_xa: xamnt, alive during the call)
         nj = len(jm)
         z = lambda *s: np.zeros((nprof, npath) + s, dt)  # noqa: E731
         out = dict(o=np.zeros((nprof, lm, nwn), dt), rad=z(nwn), tb=z(nwn), k_t=z(lm, nwn), k_tz=z(lm + 1, nwn), k_w=z(lm, nj, nwn),
                    k_clw=z(lm, nwn), k_o=z(lm, nwn), k_path=z(lm, nwn), k_sfc=z(3, nwn))
-        wn, fac = _np(p0.wn), _np(p0.cntnm)
-        self._chk(getattr(self.lib, "monortm_hip_scan_jacobian" + sfx)(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P),
-                _ptr(T),
-                                                     _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, *xargs,
-                                                     _ptr(irt), _ptr(TZ), _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj,
-                                                     _ptr(jm) if nj else None, npath, _ptr(f), int(em.ndim == 3),
-                                                     *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS]))
+        self._chk(getattr(self.lib, "monortm_hip_scan_jacobian" + sfx)(*self._full_args(profiles, rtm, self._pack_atm(profiles, lm), em, rf, xargs),
+                                                                       _quantity(quantity), nj, _ptr(jm) if nj else None, npath, _ptr(f),
+                                                                       int(em.ndim == 3),
+                                                                       *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS]))
         out["vars"] = jm
         return out
 
@@ -885,34 +869,22 @@ class MonoRTM:
         """MODM (the base and the perturbed states of jacobian(), ONCE) + RTM with Jacobians per measurement (real_kind 8): the fields
         of rtm_obs_jacobian with the optical-depth term in k_t, plus o [nprof, nlay_max, nwn] (the vertical optical depths, as
         scan_jacobian returns them), k_w [nprof, nview, nlay_max, len(mols), nchan] and k_clw [nprof, nview, nlay_max, nchan]."""
-        p0 = profiles[0]
-        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
-        nmol, dt = p0.nmol, self.dtype
+        rtm = self._pack_rtm(profiles)
+        nprof, nwn, _, lm, _, _, _, _, em, rf = rtm
+        dt = self.dtype
         f = self._path(path, nprof, lm)
         npath = f.shape[1]
         em, rf = self._scan_sfc(em, rf, emiss, reflc, nprof, npath, nwn)
-
-        def pack(get, width=None):
-            out = np.zeros((nprof, lm) if width is None else (nprof, lm, width), dt)
-            for i, p in enumerate(profiles):
-                out[i, : p.nlay] = get(p)
-            return out
-
-        P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
-        WKL = pack(lambda p: p.wkl, nmol)
-        jm = jac_codes(mols, p0.xs_names)
+        jm = jac_codes(mols, profiles[0].xs_names)
         sfx, xargs, _xa = self._jac_xs(profiles, ixsect, xs_entry, lm)   # (_xa: xamnt, alive during the call)
         nj = len(jm)
         nv, nc = self._obs_shape(obs)
         z = lambda *s: np.zeros((nprof, nv) + s + (nc,), dt)  # noqa: E731
         out = dict(o=np.zeros((nprof, lm, nwn), dt), y=z(), k_t=z(lm), k_tz=z(lm + 1), k_w=z(lm, nj), k_clw=z(lm), k_sfc=z(3))
-        wn, fac = _np(p0.wn), _np(p0.cntnm)
-        self._chk(getattr(self.lib, "monortm_hip_obs_jacobian" + sfx)(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P),
-                _ptr(T),
-                                                    _ptr(CLW), _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, *xargs,
-                                                    _ptr(irt), _ptr(TZ), _ptr(ts), _ptr(em), _ptr(rf), _quantity(quantity), nj,
-                                                    _ptr(jm) if nj else None, npath, _ptr(f), int(em.ndim == 3), int(obs),
-                                                    *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS]))
+        self._chk(getattr(self.lib, "monortm_hip_obs_jacobian" + sfx)(*self._full_args(profiles, rtm, self._pack_atm(profiles, lm), em, rf, xargs),
+                                                                      _quantity(quantity), nj, _ptr(jm) if nj else None, npath, _ptr(f),
+                                                                      int(em.ndim == 3), int(obs),
+                                                                      *[_ptr(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS]))
         out["vars"] = jm
         return out
 
@@ -1010,27 +982,15 @@ class MonoRTM:
         q = _quantity(quantity, band=True)
         nv, nc = self._obs_shape(obs)
         vc = _vcen(vcen, q, nc)
-        p0 = profiles[0]
-        nprof, nwn, nlay, lm, irt, T, TZ, ts, em, rf = self._pack_rtm(profiles)
-        nmol, dt = p0.nmol, self.dtype
+        rtm = self._pack_rtm(profiles)
+        nprof, nwn, _, lm, _, _, _, _, em, rf = rtm
+        dt = self.dtype
         f = self._path(path, nprof, lm)
         npath = f.shape[1]
         em, rf = self._scan_sfc(em, rf, emiss, reflc, nprof, npath, nwn)
-
-        def pack(get, width=None):
-            out = np.zeros((nprof, lm) if width is None else (nprof, lm, width), dt)
-            for i, p in enumerate(profiles):
-                out[i, : p.nlay] = get(p)
-            return out
-
-        P, CLW, WB = pack(lambda p: p.p), pack(lambda p: p.clw), pack(lambda p: p.wbrodl)
-        WKL = pack(lambda p: p.wkl, nmol)
         out = dict(o=np.zeros((nprof, lm, nwn), dt), y=np.zeros((nprof, nv, nc), dt))
-        wn, fac = _np(p0.wn), _np(p0.cntnm)
-        self._chk(self.lib.monortm_hip_obs(self.ctx, nprof, nwn, _ptr(wn), p0.dvset, _ptr(nlay), lm, nmol, _ptr(P), _ptr(T), _ptr(CLW),
-                                           _ptr(WKL), _ptr(WB), _ptr(fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd, _ptr(irt), _ptr(TZ),
-                                           _ptr(ts), _ptr(em), _ptr(rf), q, npath, _ptr(f), int(em.ndim == 3), int(obs), _ptr(vc),
-                                           *[_ptr(out[k]) for k in OBS_FIELDS]))
+        self._chk(self.lib.monortm_hip_obs(*self._full_args(profiles, rtm, self._pack_atm(profiles, lm), em, rf), q, npath, _ptr(f),
+                                           int(em.ndim == 3), int(obs), _ptr(vc), *[_ptr(out[k]) for k in OBS_FIELDS]))
         return out
 
     # ---- the C-ABI gather of a profile-sharded job (RCCL; what a C / Fortran caller uses instead of torch.distributed) ------
@@ -1100,11 +1060,7 @@ class DeviceBatch:
             return torch.as_tensor(np.ascontiguousarray(a)).to(dt).to(self.dev)
 
         def pack(get, width=None):
-            shape = (self.nprof, lm) if width is None else (self.nprof, lm, width)
-            out = np.zeros(shape)
-            for i, p in enumerate(profiles):
-                out[i, : p.nlay] = get(p)
-            return out
+            return pack_layers(profiles, lm, get, width)
 
         self.wn = up(p0.wn, torch.float64)
         self.nlay = up(nlay, torch.int32)
@@ -1146,6 +1102,32 @@ class DeviceBatch:
         """The [6, nprof, nwn] block the last step wrote (RAD, TB, TRTOT, TMR, RUP, RDN), contiguous, no copy."""
         return self._spec[self._cur]
 
+    def _modm_args(self):
+        """The leading arguments of the *_dev entries that run MODM on the resident batch: ctx, nprof ... ibrd."""
+        p0 = self.p0
+        d = lambda x: _vp(x.data_ptr())  # noqa: E731
+        return (self.rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol, d(self.P), d(self.T), d(self.CLW),
+                d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl, p0.sclhw, p0.y0res, p0.ibrd)
+
+    def _sfc_args(self):
+        """... and what follows ibrd in the full Jacobian entries: irt, TZ, the profiles' own TMPSFC (input only), emiss, reflc."""
+        return tuple(_vp(x.data_ptr()) for x in (self.irt, self.TZ, self.tmpsfc0, self.emiss, self.reflc))
+
+    def _modm(self, sp):
+        """MODM of the resident batch into its O, OBM, OC, OCLW, on the stream sp."""
+        d = lambda x: _vp(x.data_ptr())  # noqa: E731
+        self.rt._chk(self.rt.lib.monortm_hip_modm_dev(*self._modm_args(), 0, d(self.O), d(self.OBM), d(self.OC), d(self.OCLW), _ptr(self.wn_ends),
+                                                      sp))
+
+    def _path(self, path):
+        """The factors of a scan as a tensor [nprof, npath, nlay_max] (a view where [npath, nlay_max] was given): ValueError otherwise."""
+        f = self.torch.as_tensor(path)
+        if f.dim() == 2:
+            f = f.unsqueeze(0).expand(self.nprof, -1, -1)
+        if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
+            raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
+        return f
+
     def step(self, stream=None):
         t = self.torch
         if self.pingpong:   # (not under graph capture: a captured step keeps the block it was recorded with)
@@ -1155,10 +1137,7 @@ class DeviceBatch:
         sp = _vp(s.cuda_stream)
         p0, lib, rt = self.p0, self.rt.lib, self.rt
         d = lambda x: _vp(x.data_ptr())  # noqa: E731
-        rt._chk(lib.monortm_hip_modm_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol,
-                                         d(self.P), d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl,
-                                         p0.sclhw, p0.y0res, p0.ibrd, 0, d(self.O), d(self.OBM), d(self.OC), d(self.OCLW), _ptr(self.wn_ends),
-                                         sp))
+        self._modm(sp)
         rt._chk(lib.monortm_hip_rtm_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), d(self.nlay), self.lm, d(self.irt), p0.iout,
                                         d(self.T), d(self.TZ), d(self.O), d(self.tmpsfc), d(self.emiss), d(self.reflc),
                                         d(self.RUP), d(self.RDN), d(self.TRTOT), d(self.RAD), d(self.TB), d(self.TMR), sp))
@@ -1179,14 +1158,12 @@ class DeviceBatch:
                                k_clw=z(n, lm, nw), k_o=z(n, lm, nw), k_sfc=z(n, 3, nw)), np.ascontiguousarray(key[0], np.int32))
         out, jm = cache[key]
         s = stream if stream is not None else t.cuda.current_stream(self.dev)
-        p0, lib, rt = self.p0, self.rt.lib, self.rt
+        rt = self.rt
         d = lambda x: _vp(x.data_ptr())  # noqa: E731
         nj = len(jm)
-        rt._chk(lib.monortm_hip_jacobian_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol, d(self.P),
-                                             d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl, p0.sclhw, p0.y0res,
-                                             p0.ibrd, d(self.irt), d(self.TZ), d(self.tmpsfc0), d(self.emiss), d(self.reflc), key[1], nj,
-                                             _ptr(jm) if nj else None, *[d(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS],
-                                             _ptr(self.wn_ends), _vp(s.cuda_stream)))
+        rt._chk(rt.lib.monortm_hip_jacobian_dev(*self._modm_args(), *self._sfc_args(), key[1], nj, _ptr(jm) if nj else None,
+                                                *[d(out[k]) if (k != "k_w" or nj) else None for k in JAC_FIELDS],
+                                                _ptr(self.wn_ends), _vp(s.cuda_stream)))
         out["vars"] = t.from_numpy(jm.copy())   # (a host tensor: the codes in slot order)
         return out
 
@@ -1201,11 +1178,7 @@ class DeviceBatch:
         and cannot be captured.  Bad factors surface through check()."""
         t = self.torch
         real = t.float32 if self.rt.real_kind == 4 else t.float64  # dtype of the REAL arrays
-        f = t.as_tensor(path)
-        if f.dim() == 2:
-            f = f.unsqueeze(0).expand(self.nprof, -1, -1)
-        if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
-            raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
+        f = self._path(path)
         npath = int(f.shape[1])
         if npath not in self._scan:
             self._scan[npath] = (t.zeros(6, self.nprof, npath, self.nwn, dtype=real, device=self.dev),
@@ -1218,10 +1191,7 @@ class DeviceBatch:
         p0, lib, rt = self.p0, self.rt.lib, self.rt
         d = lambda x: _vp(x.data_ptr())  # noqa: E731
         rad, tb, trtot, tmr, rup, rdn = (blk[k] for k in range(6))
-        rt._chk(lib.monortm_hip_modm_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol,
-                                         d(self.P), d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl,
-                                         p0.sclhw, p0.y0res, p0.ibrd, 0, d(self.O), d(self.OBM), d(self.OC), d(self.OCLW), _ptr(self.wn_ends),
-                                         sp))
+        self._modm(sp)
         rt._chk(lib.monortm_hip_rtm_scan_dev(rt.ctx, self.nprof, npath, self.nwn, d(self.wn), d(self.nlay), self.lm, d(self.irt), p0.iout,
                                              d(self.T), d(self.TZ), d(self.O), d(fd), d(self.tmpsfc), 0, d(self.emiss), d(self.reflc),
                                              d(rup), d(rdn), d(trtot), d(rad), d(tb), d(tmr), sp))
@@ -1236,11 +1206,7 @@ class DeviceBatch:
         profiles' own (input only).  Bad factors surface through check()."""
         t = self.torch
         real = t.float32 if self.rt.real_kind == 4 else t.float64  # dtype of the REAL arrays
-        f = t.as_tensor(path)
-        if f.dim() == 2:
-            f = f.unsqueeze(0).expand(self.nprof, -1, -1)
-        if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
-            raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
+        f = self._path(path)
         npath = int(f.shape[1])
         key = (npath, tuple(int(m) for m in jac_codes(mols)), _quantity(quantity))
         cache = self.__dict__.setdefault("_scan_jac", {})
@@ -1254,15 +1220,12 @@ class DeviceBatch:
         s = stream if stream is not None else t.cuda.current_stream(self.dev)
         with t.cuda.stream(s):
             fd.copy_(f, non_blocking=True)
-        p0, lib, rt = self.p0, self.rt.lib, self.rt
+        rt = self.rt
         d = lambda x: _vp(x.data_ptr())  # noqa: E731
         nj = len(jm)
-        rt._chk(lib.monortm_hip_scan_jacobian_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol,
-                                                  d(self.P), d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl,
-                                                  p0.sclhw, p0.y0res, p0.ibrd, d(self.irt), d(self.TZ), d(self.tmpsfc0), d(self.emiss),
-                                                  d(self.reflc), key[2], nj, _ptr(jm) if nj else None, npath, d(fd), 0,
-                                                  *[d(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS],
-                                                  _ptr(self.wn_ends), _vp(s.cuda_stream)))
+        rt._chk(rt.lib.monortm_hip_scan_jacobian_dev(*self._modm_args(), *self._sfc_args(), key[2], nj, _ptr(jm) if nj else None, npath, d(fd), 0,
+                                                     *[d(out[k]) if (k != "k_w" or nj) else None for k in SCAN_JAC_FIELDS],
+                                                     _ptr(self.wn_ends), _vp(s.cuda_stream)))
         out["vars"] = t.from_numpy(jm.copy())   # (a host tensor: the codes in slot order)
         return out
 
@@ -1276,11 +1239,7 @@ class DeviceBatch:
         no monochromatic or per-path K is allocated anywhere.  Bad factors surface through check()."""
         t = self.torch
         real = t.float32 if self.rt.real_kind == 4 else t.float64  # dtype of the REAL arrays
-        f = t.as_tensor(path)
-        if f.dim() == 2:
-            f = f.unsqueeze(0).expand(self.nprof, -1, -1)
-        if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
-            raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
+        f = self._path(path)
         npath = int(f.shape[1])
         key = (int(obs), npath, tuple(int(m) for m in jac_codes(mols)), _quantity(quantity))
         cache = self.__dict__.setdefault("_obs_jac", {})
@@ -1298,15 +1257,12 @@ class DeviceBatch:
         s = stream if stream is not None else t.cuda.current_stream(self.dev)
         with t.cuda.stream(s):
             fd.copy_(f, non_blocking=True)
-        p0, lib, rt = self.p0, self.rt.lib, self.rt
+        rt = self.rt
         d = lambda x: _vp(x.data_ptr())  # noqa: E731
         nj = len(jm)
-        rt._chk(lib.monortm_hip_obs_jacobian_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol,
-                                                 d(self.P), d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl,
-                                                 p0.sclhw, p0.y0res, p0.ibrd, d(self.irt), d(self.TZ), d(self.tmpsfc0), d(self.emiss),
-                                                 d(self.reflc), key[3], nj, _ptr(jm) if nj else None, npath, d(fd), 0, int(obs),
-                                                 *[d(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS],
-                                                 _ptr(self.wn_ends), _vp(s.cuda_stream)))
+        rt._chk(rt.lib.monortm_hip_obs_jacobian_dev(*self._modm_args(), *self._sfc_args(), key[3], nj, _ptr(jm) if nj else None, npath, d(fd), 0,
+                                                    int(obs), *[d(out[k]) if (k != "k_w" or nj) else None for k in OBS_JAC_FIELDS],
+                                                    _ptr(self.wn_ends), _vp(s.cuda_stream)))
         out["vars"] = t.from_numpy(jm.copy())   # (a host tensor: the codes in slot order)
         return out
 
@@ -1322,11 +1278,7 @@ class DeviceBatch:
         t = self.torch
         real = t.float32 if self.rt.real_kind == 4 else t.float64  # dtype of the REAL arrays
         q = _quantity(quantity, band=True)
-        f = t.as_tensor(path)
-        if f.dim() == 2:
-            f = f.unsqueeze(0).expand(self.nprof, -1, -1)
-        if f.dim() != 3 or f.shape[0] != self.nprof or f.shape[1] < 1 or f.shape[2] != self.lm:
-            raise ValueError(f"path must be [npath, {self.lm}] or [{self.nprof}, npath, {self.lm}], got {tuple(f.shape)}")
+        f = self._path(path)
         npath = int(f.shape[1])
         key = (int(obs), npath, q)
         cache = self.__dict__.setdefault("_obs_fwd", {})
@@ -1351,10 +1303,7 @@ class DeviceBatch:
         sp = _vp(s.cuda_stream)
         p0, lib, rt = self.p0, self.rt.lib, self.rt
         d = lambda x: _vp(x.data_ptr())  # noqa: E731
-        rt._chk(lib.monortm_hip_modm_dev(rt.ctx, self.nprof, self.nwn, d(self.wn), p0.dvset, d(self.nlay), self.lm, self.nmol,
-                                         d(self.P), d(self.T), d(self.CLW), d(self.WKL), d(self.WB), _ptr(self.fac), p0.sclcpl,
-                                         p0.sclhw, p0.y0res, p0.ibrd, 0, d(self.O), d(self.OBM), d(self.OC), d(self.OCLW), _ptr(self.wn_ends),
-                                         sp))
+        self._modm(sp)
         rt._chk(lib.monortm_hip_rtm_obs_dev(rt.ctx, self.nprof, npath, self.nwn, d(self.wn), d(self.nlay), self.lm, d(self.irt), q,
                                             d(self.T), d(self.TZ), d(self.O), d(fd), d(self.tmpsfc0), 0, d(self.emiss), d(self.reflc),
                                             int(obs), d(vd) if q == 2 else None, d(y), sp))

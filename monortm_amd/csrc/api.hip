@@ -9,6 +9,7 @@
 #include <cstring>
 #include <dlfcn.h>
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -274,6 +275,12 @@ hipError_t grow(void **p, size_t *have, size_t need, size_t elem = 1) {
     return e;
 }
 
+// Ctx::jac_ws with room for `bytes`: the workspace of the Jacobian entries and of monortm_hip_obs_dev - whichever call needs more grows it
+int jac_ws_reserve(Ctx *c, size_t bytes) {
+    HIPCHK(c, grow(&c->jac_ws, &c->jac_ws_bytes, bytes));
+    return MONORTM_OK;
+}
+
 // the *_dev entry points launch on the calling thread's current device: it must be the context's
 int check_device(Ctx *c) {
     int d = -1;
@@ -411,6 +418,46 @@ struct Arena {  // layout helper: 256-byte aligned pieces of one buffer
         return off;
     }
 };
+// ---- the argument groups of a call, named ONCE -----------------------------------------------------------------------------------
+// Every extern "C" entry fills these from its parameters at its top; below that line nothing takes the groups as loose parameters.
+// A field an entry has no argument for stays zero / null.
+struct AtmIn {   // the atmosphere: what MODM reads (an entry that is handed O fills nprof, nwn, wn, nlay, nlay_max and T only)
+    int nprof = 0, nwn = 0;
+    const double *wn = nullptr;
+    double dvset = 0.;
+    const int *nlay = nullptr;
+    int nlay_max = 0, nmol = 0;
+    const void *P = nullptr, *T = nullptr, *CLW = nullptr, *WKL = nullptr, *WBRODL = nullptr;
+    const double *cntnm_fac = nullptr;
+    double sclcpl = 0., sclhw = 0., y0res = 0.;
+    int ibrd = 0, ixsect = 0;
+    const void *XAMNT = nullptr;
+    const double *wn_ends = nullptr;   // on the host: wn[0], wn[nwn - 1]; null: fetched from the device (one synchronisation)
+};
+struct SfcIn {   // the surface and what RTM is asked for
+    const int *irt = nullptr;
+    const void *TZ = nullptr, *tmpsfc = nullptr, *emiss = nullptr, *reflc = nullptr;
+    int quantity = 0;
+};
+struct ScanIn {   // the paths of a scan (npath = 0, path null: the entry has none)
+    int npath = 0;
+    const void *path = nullptr;
+    int sfc_per_path = 0;
+};
+struct JacReq {   // the Jacobian variables of a full Jacobian call
+    int njac = 0;
+    const int *jac_mol = nullptr;
+};
+struct JacOut {   // the outputs of the Jacobian families: O of the full entries, RAD / TB or Y, and the K arrays the family has
+    void *O = nullptr, *RAD = nullptr, *TB = nullptr, *Y = nullptr;
+    void *K_T = nullptr, *K_TZ = nullptr, *K_W = nullptr, *K_CLW = nullptr, *K_O = nullptr, *K_PATH = nullptr, *K_SFC = nullptr;
+};
+bool any_null(std::initializer_list<const void *> ptrs) {
+    for (const void *p : ptrs)
+        if (!p) return true;
+    return false;
+}
+
 struct HostClock {  // phase timer of a host-buffer call (only when MONORTM_HOST_TIMING=1, and for the entries that have a row of Ctx::ht)
     Ctx *c = nullptr;
     int k = -1;
@@ -461,11 +508,11 @@ int decode_flag(Ctx *c, int flag, hipStream_t s) {
 namespace {
 // ---- path scans: what the scan entries check on host arguments
 constexpr int kScanMaxPaths = 16384;   // 4096 path tiles: inside the grid's z range
-int scan_check_args(Ctx *c, int nprof, int npath, int nwn, int nlay_max, int sfc_per_path) {
-    if (nprof < 1 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
-    if (nlay_max > 603) { c->err = "nlay_max exceeds MXLAY=603 (the bound of monortm_hip_modm, which O comes from)"; return MONORTM_EARG; }
-    if (npath < 1 || npath > kScanMaxPaths) { c->err = "npath outside 1.." + std::to_string(kScanMaxPaths); return MONORTM_EARG; }
-    if (sfc_per_path != 0 && sfc_per_path != 1) { c->err = "sfc_per_path must be 0 or 1"; return MONORTM_EARG; }
+int scan_check_args(Ctx *c, const AtmIn &atm, const ScanIn &scan) {
+    if (atm.nprof < 1 || atm.nwn < 1 || atm.nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (atm.nlay_max > 603) { c->err = "nlay_max exceeds MXLAY=603 (the bound of monortm_hip_modm, which O comes from)"; return MONORTM_EARG; }
+    if (scan.npath < 1 || scan.npath > kScanMaxPaths) { c->err = "npath outside 1.." + std::to_string(kScanMaxPaths); return MONORTM_EARG; }
+    if (scan.sfc_per_path != 0 && scan.sfc_per_path != 1) { c->err = "sfc_per_path must be 0 or 1"; return MONORTM_EARG; }
     return MONORTM_OK;
 }
 template <typename R>
@@ -481,12 +528,12 @@ bool scan_path_ok(const void *path, int nprof, int npath, const int *nlay, int n
 }
 
 // nlay and the factors of the active layers of a whole host call: checked before anything is staged or launched, on every device
-int scan_check_path(Ctx *c, int nprof, int npath, const int *nlay, int nlay_max, const void *path) {
-    for (int p = 0; p < nprof; p++)
-        if (nlay[p] < 1 || nlay[p] > nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
+int scan_check_path(Ctx *c, const AtmIn &atm, const ScanIn &scan) {
+    for (int p = 0; p < atm.nprof; p++)
+        if (atm.nlay[p] < 1 || atm.nlay[p] > atm.nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
     int bp = 0, bj = 0, bl = 0;
-    const bool ok = c->real_kind == 4 ? scan_path_ok<float>(path, nprof, npath, nlay, nlay_max, &bp, &bj, &bl)
-                                      : scan_path_ok<double>(path, nprof, npath, nlay, nlay_max, &bp, &bj, &bl);
+    const bool ok = c->real_kind == 4 ? scan_path_ok<float>(scan.path, atm.nprof, scan.npath, atm.nlay, atm.nlay_max, &bp, &bj, &bl)
+                                      : scan_path_ok<double>(scan.path, atm.nprof, scan.npath, atm.nlay, atm.nlay_max, &bp, &bj, &bl);
     if (!ok) {
         c->err = "path factor negative or not finite: profile " + std::to_string(bp) + " path " + std::to_string(bj) + " layer " + std::to_string(bl);
         return MONORTM_EARG;
@@ -505,11 +552,11 @@ int need_real8(Ctx *c, const char *entry) {
     c->err = std::string(entry) + " needs a real_kind = 8 context (its differences of optical depths need double arrays)";
     return MONORTM_EUNSUPPORTED;
 }
-int jac_check_args(Ctx *c, int nprof, int nwn, const int *nlay, int nlay_max, int quantity) {
-    if (nprof < 1 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+int jac_check_args(Ctx *c, const AtmIn &atm, int quantity) {
+    if (atm.nprof < 1 || atm.nwn < 1 || atm.nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     if (int rcq = check_quantity(c, quantity)) return rcq;
-    for (int p = 0; p < nprof; p++)
-        if (nlay[p] < 1 || nlay[p] > nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
+    for (int p = 0; p < atm.nprof; p++)
+        if (atm.nlay[p] < 1 || atm.nlay[p] > atm.nlay_max) { c->err = "nlay[p] outside 1..nlay_max"; return MONORTM_EARG; }
     return MONORTM_OK;
 }
 // Jacobian variables: the scalar arguments of MODM among the MONORTM_JVAR_* codes, and the per-layer ones
@@ -522,7 +569,8 @@ bool jac_var_xs(int v) { return v >= MONORTM_JVAR_XS0 && v < MONORTM_JVAR_XS0 + 
 // cross-section molecules of the context's tables (every shard of a multi-device context holds the same tables)
 int ctx_nxs(const Ctx *c) { return (c->shards.empty() ? c : c->shards[0])->xs.nxs; }
 // ixsect, XAMNT: the two arguments of the *_xs entries (the entries without them pass 0, nullptr: a cross-section code is refused)
-int jac_check_mol(Ctx *c, int nmol, int njac, const int *jac_mol, const void *K_W, int ixsect, const void *XAMNT) {
+int jac_check_mol(Ctx *c, const AtmIn &atm, const JacReq &jq, const void *K_W) {
+    const int nmol = atm.nmol, njac = jq.njac, ixsect = atm.ixsect, *jac_mol = jq.jac_mol;
     if (njac < 0 || njac > MXMOL || (njac > 0 && (!jac_mol || !K_W))) { c->err = "njac outside 0..39, or jac_mol / K_W missing"; return MONORTM_EARG; }
     if (ixsect != 0 && ixsect != 1) { c->err = "ixsect must be 0 or 1"; return MONORTM_EARG; }
     const int nxs = ctx_nxs(c);
@@ -544,7 +592,7 @@ int jac_check_mol(Ctx *c, int nmol, int njac, const int *jac_mol, const void *K_
         for (int j = 0; j < i; j++)
             if (jac_mol[j] == jac_mol[i]) { c->err = "jac_mol lists variable " + std::to_string(jac_mol[i]) + " twice"; return MONORTM_EARG; }
     }
-    if (ixsect == 1 && (nxs < 1 || !XAMNT)) {
+    if (ixsect == 1 && (nxs < 1 || !atm.XAMNT)) {
         c->err = "ixsect = 1: no cross-section tables on this context (monortm_hip_xsec_tables), or XAMNT missing";
         return MONORTM_EARG;
     }
@@ -553,13 +601,17 @@ int jac_check_mol(Ctx *c, int nmol, int njac, const int *jac_mol, const void *K_
 
 // what the MODM passes of a full Jacobian call refuse, on host arrays: wavenumbers that do not ascend, and T +- jac_dt outside the TIPS
 // range (the MODM kernels would flag the latter as well)
-int jac_check_states(Ctx *c, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const void *T) {
-    for (int i = 1; i < nwn; i++)
-        if (!(wn[i] >= wn[i - 1])) { c->err = "wavenumbers must be ascending (the reference takes v1 = wn(1), v2 = wn(nwn), modm.f90:180-181)"; return MONORTM_EARG; }
-    const double h = c->opt.jac_dt, *Tp = static_cast<const double *>(T);
-    for (int p = 0; p < nprof; p++)
-        for (int k = 0; k < nlay[p]; k++) {
-            const double t = Tp[(size_t)p * nlay_max + k];
+int check_ascending(Ctx *c, const AtmIn &atm) {
+    for (int i = 1; i < atm.nwn; i++)
+        if (!(atm.wn[i] >= atm.wn[i - 1])) { c->err = "wavenumbers must be ascending (the reference takes v1 = wn(1), v2 = wn(nwn), modm.f90:180-181)"; return MONORTM_EARG; }
+    return MONORTM_OK;
+}
+int jac_check_states(Ctx *c, const AtmIn &atm) {
+    if (int rc = check_ascending(c, atm)) return rc;
+    const double h = c->opt.jac_dt, *Tp = static_cast<const double *>(atm.T);
+    for (int p = 0; p < atm.nprof; p++)
+        for (int k = 0; k < atm.nlay[p]; k++) {
+            const double t = Tp[(size_t)p * atm.nlay_max + k];
             if (!(t - h >= 70. && t + h <= 3000.)) {
                 c->err = "layer temperature +- jac_dt outside 70-3000 K (TIPS, tips_2003.f90:277): profile " + std::to_string(p) + " layer " + std::to_string(k);
                 return MONORTM_ETEMP;
@@ -568,10 +620,10 @@ int jac_check_states(Ctx *c, int nprof, int nwn, const double *wn, const int *nl
     return MONORTM_OK;
 }
 
-int modm_dev_impl(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
-                  const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
-                  double y0res, int ibrd, int ixsect, const void *XAMNT, void *ODXSEC, bool odx_given, void *O, void *O_BY_MOL, void *OC,
-                  void *O_CLW, const double *wn_ends, void *stream);   // (defined with monortm_hip_modm_xs_dev, below)
+struct ModmOut {   // the outputs of a MODM evaluation ([nprof][nlay_max](x nmol / NCONT)[nwn]; ODXSEC with ixsect = 1 only)
+    void *ODXSEC = nullptr, *O = nullptr, *O_BY_MOL = nullptr, *OC = nullptr, *O_CLW = nullptr;
+};
+int modm_dev_impl(Ctx *c, const AtmIn &atm, bool odx_given, const ModmOut &out, hipStream_t s);   // (defined with monortm_hip_modm_xs_dev, below)
 
 // The MODM part of a Jacobian call (monortm_hip_jacobian_dev, monortm_hip_scan_jacobian_dev): jac_perturb_kernel, then MODM of the base
 // and the 2 (1 + njac) perturbed states.  Small batches (single-profile retrievals underfill the GPU) go through ONE extended MODM launch
@@ -583,17 +635,17 @@ int modm_dev_impl(Ctx *c, int nprof, int nwn, const double *wn, double dvset, co
 // P (1 +- eps) take their ODXSEC from xsec_jac_kernel - the base state's walk evaluated at the perturbed (P, T), not a walk of their
 // own - and the states of a cross-section molecule are written by that kernel ("+") and cleared ("-").  With ixsect = 0 every size,
 // launch and result is what it was.
-static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
-                      const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
-                      double y0res, int ibrd, int ixsect, const void *XAMNT, int njac, const int *jac_mol, void *O, const double *wn_ends,
-                      hipStream_t s, double **xO_out, size_t *st_out) {
+static int jac_states(Ctx *c, const AtmIn &atm, const JacReq &jq, void *O, hipStream_t s, double **xO_out, size_t *st_out) {
+    const int nprof = atm.nprof, nwn = atm.nwn, nlay_max = atm.nlay_max, nmol = atm.nmol, njac = jq.njac, *jac_mol = jq.jac_mol;
     double vends[2];
-    if (wn_ends) { vends[0] = wn_ends[0]; vends[1] = wn_ends[1]; }
+    if (atm.wn_ends) { vends[0] = atm.wn_ends[0]; vends[1] = atm.wn_ends[1]; }
     else {   // once here, not in every MODM call below
-        HIPCHK(c, hipMemcpyAsync(&vends[0], wn, sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&vends[1], wn + nwn - 1, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&vends[0], atm.wn, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&vends[1], atm.wn + nwn - 1, sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
     }
+    AtmIn base = atm;   // the caller's state with the grid's ends on the host: what every MODM launch below starts from
+    base.wn_ends = vends;
     // Per-layer variables (molecules, P, WBRODL) are states of the perturbed arrays, in slot order; the two states of a scalar variable
     // are MODM launches of the caller's own arrays with that argument changed.  State k of O, k = 3 + 2i / 4 + 2i
     // for jac_mol[i] of either kind; the perturbed arrays hold the nps states of the base, T +- h and the per-layer variables only.
@@ -602,7 +654,7 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
     // and launch is what it was.
     // A cross-section molecule (MONORTM_JVAR_XS0 + x) has no state of the perturbed arrays and no MODM launch at all: O is linear in
     // XAMNT, and its two states of O are the molecule's own term and zero (xsec_jac_kernel).
-    const bool xs = ixsect == 1;
+    const bool xs = atm.ixsect == 1;
     int lvar[MXMOL], nlv = 0, p_state = 0;   // p_state: the "+" state of MONORTM_JVAR_P in the perturbed arrays, or 0
     bool rayl = false;
     XsecJacArgs xa{};
@@ -627,13 +679,7 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
                  w_W = ws.add(npa * npl * nmol * 8), w_nl = ws.add(npa * (size_t)nprof * sizeof(int)), w_O = ws.add(nstate * st * 8),
                  w_OM = ws.add(nj * st * nmol * 8), w_OC = ws.add(nj * st * MONORTM_NCONT * 8), w_OL = ws.add(nj * st * 8),
                  w_X = xs ? ws.add(nodx * st * 8) : 0;
-    if (ws.size > c->jac_ws_bytes) {
-        if (c->jac_ws) HIPCHK(c, hipFree(c->jac_ws));
-        c->jac_ws = nullptr;
-        c->jac_ws_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->jac_ws, ws.size));
-        c->jac_ws_bytes = ws.size;
-    }
+    if (int rc = jac_ws_reserve(c, ws.size)) return rc;
     char *wb = static_cast<char *>(c->jac_ws);
     double *xO = reinterpret_cast<double *>(wb + w_O), *xX = xs ? reinterpret_cast<double *>(wb + w_X) : nullptr;
     *xO_out = xO;
@@ -641,8 +687,8 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
     JacPerturbArgs pa{};
     pa.nstate = npa; pa.rayl_state = rayl ? nps : 0; pa.nprof = nprof; pa.nlay_max = nlay_max; pa.nmol = nmol; pa.dt = c->opt.jac_dt; pa.dlnw = c->opt.jac_dlnw;
     for (int i = 0; i < nlv; i++) pa.jac_mol[i] = lvar[i];
-    pa.P = static_cast<const double *>(P); pa.T = static_cast<const double *>(T); pa.CLW = static_cast<const double *>(CLW);
-    pa.WKL = static_cast<const double *>(WKL); pa.WBRODL = static_cast<const double *>(WBRODL); pa.nlay = nlay;
+    pa.P = static_cast<const double *>(atm.P); pa.T = static_cast<const double *>(atm.T); pa.CLW = static_cast<const double *>(atm.CLW);
+    pa.WKL = static_cast<const double *>(atm.WKL); pa.WBRODL = static_cast<const double *>(atm.WBRODL); pa.nlay = atm.nlay;
     pa.xP = reinterpret_cast<double *>(wb + w_P); pa.xT = reinterpret_cast<double *>(wb + w_T); pa.xCLW = reinterpret_cast<double *>(wb + w_C);
     pa.xWBRODL = reinterpret_cast<double *>(wb + w_B); pa.xWKL = reinterpret_cast<double *>(wb + w_W); pa.xnlay = reinterpret_cast<int *>(wb + w_nl);
     launch_jac_perturb(pa, s);
@@ -651,7 +697,7 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
         // the further states' ODXSEC and the named molecules' terms, in one pass over the base state's walk; the perturbed (P, T) are
         // read from the perturbed arrays, so they are the very values the states' MODM launches see
         xa.nprof = nprof; xa.nwn = nwn; xa.nlay_max = nlay_max; xa.nx = p_state ? 4 : 2;
-        xa.wn = wn; xa.P = pa.P; xa.T = pa.T; xa.XAMNT = static_cast<const double *>(XAMNT); xa.nlay = nlay;
+        xa.wn = atm.wn; xa.P = pa.P; xa.T = pa.T; xa.XAMNT = static_cast<const double *>(atm.XAMNT); xa.nlay = atm.nlay;
         xa.xP = pa.xP; xa.xT = pa.xT;
         const int pst[4] = {1, 2, p_state, p_state + 1};
         for (int i = 0; i < xa.nx; i++) { xa.pstate[i] = pst[i]; xa.oslot[i] = odx_slot(pst[i]); }
@@ -661,21 +707,27 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
         HIPCHK(c, hipGetLastError());
         if (ext) {   // the base state's ODXSEC, by xsec_kernel on the caller's arrays: what monortm_hip_modm_xs_dev launches
             ModmArgs ma{};
-            ma.real_kind = 8; ma.nprof = nprof; ma.nwn = nwn; ma.nlay_max = nlay_max; ma.wn = wn; ma.P = P; ma.T = T; ma.nlay = nlay;
-            ma.XAMNT = XAMNT; ma.ODXSEC = xX; ma.nxs = c->xs.nxs;
+            ma.real_kind = 8; ma.nprof = nprof; ma.nwn = nwn; ma.nlay_max = nlay_max; ma.wn = atm.wn; ma.P = atm.P; ma.T = atm.T; ma.nlay = atm.nlay;
+            ma.XAMNT = atm.XAMNT; ma.ODXSEC = xX; ma.nxs = c->xs.nxs;
             launch_xsec(ma, c->xs, s);
             HIPCHK(c, hipGetLastError());
         }
     }
     // MODM of n profiles of the perturbed arrays from their state s0 on.  States of molecules and WBRODL run WITHOUT the cross sections
     // (ODXSEC does not depend on WKL or WBRODL and would cancel in their differences): ixsect = 0 in a launch of their own, a zero slot
-    // of ODXSEC inside an extended launch
-    auto modm = [&](int n, int s0, void *Oout) {
+    // of ODXSEC inside an extended launch.  (The MODM outputs that the Jacobian does not use go to the workspace.)
+    auto outputs = [&](void *Oout, void *odx) { return ModmOut{.ODXSEC = odx, .O = Oout, .O_BY_MOL = wb + w_OM, .OC = wb + w_OC, .O_CLW = wb + w_OL}; };
+    auto perturbed = [&](AtmIn m, int s0) {   // m with the layer arrays of the perturbed arrays' state s0 (nlay: set by the caller)
         const size_t l0 = (size_t)s0 * npl;
+        m.P = pa.xP + l0; m.T = pa.xT + l0; m.CLW = pa.xCLW + l0; m.WKL = pa.xWKL + l0 * nmol; m.WBRODL = pa.xWBRODL + l0;
+        m.ixsect = 0; m.XAMNT = nullptr;
+        return m;
+    };
+    auto modm = [&](int n, int s0, void *Oout) {
         const int slot = xs ? odx_slot(s0) : -1;
-        return modm_dev_impl(c, n, nwn, wn, dvset, pa.xnlay + (size_t)s0 * nprof, nlay_max, nmol, pa.xP + l0, pa.xT + l0, pa.xCLW + l0,
-                             pa.xWKL + l0 * nmol, pa.xWBRODL + l0, cntnm_fac, sclcpl, sclhw, y0res, ibrd, slot >= 0 ? 1 : 0, nullptr,
-                             slot >= 0 ? xX + (size_t)slot * st : nullptr, slot >= 0, Oout, wb + w_OM, wb + w_OC, wb + w_OL, vends, s);
+        AtmIn m = perturbed(base, s0);
+        m.nprof = n; m.nlay = pa.xnlay + (size_t)s0 * nprof; m.ixsect = slot >= 0 ? 1 : 0;
+        return modm_dev_impl(c, m, slot >= 0, outputs(Oout, slot >= 0 ? xX + (size_t)slot * st : nullptr), s);
     };
     // state k of O for a scalar variable: the caller's arrays, the argument at +eps (odd k) / -eps.  MODM switches a continuum off at a
     // factor <= 0, so where fac - eps <= 0 the pair is fac + 2 eps / fac: one-sided over the same 2 eps, exact for a linear factor.
@@ -684,7 +736,7 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
         const int v = jac_mol[(k - 3) >> 1];
         const bool plus = !((k - 3) & 1);
         const double e = c->opt.jac_dlnw;
-        double fac[7], sc[3] = {sclcpl, sclhw, y0res};
+        double fac[7];
         if (jac_var_xs(v)) {   // "+": xsec_jac_kernel has written it; "-": zero
             if (!plus) HIPCHK(c, hipMemsetAsync(Oout, 0, st * 8, s));
             return MONORTM_OK;
@@ -700,21 +752,21 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
             if (!plus) { HIPCHK(c, hipMemsetAsync(Oout, 0, st * 8, s)); return MONORTM_OK; }
             for (int i = 0; i < 7; i++) fac[i] = 0.;
             fac[6] = 2. * e;
-            const size_t l0 = (size_t)nps * npl;
-            return monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, pa.xP + l0, pa.xT + l0, pa.xCLW + l0, pa.xWKL + l0 * nmol,
-                                           pa.xWBRODL + l0, fac, sclcpl, sclhw, y0res, ibrd, 0, nullptr, nullptr, Oout, wb + w_OM, wb + w_OC,
-                                           wb + w_OL, vends, s);
+            AtmIn m = perturbed(base, nps);
+            m.cntnm_fac = fac;
+            return modm_dev_impl(c, m, false, outputs(Oout, nullptr), s);
         }
-        for (int i = 0; i < 7; i++) fac[i] = cntnm_fac[i];
+        AtmIn m = base;
+        m.ixsect = 0; m.XAMNT = nullptr;
+        for (int i = 0; i < 7; i++) fac[i] = atm.cntnm_fac[i];
         if (v >= MONORTM_JVAR_CNTNM0 && v < MONORTM_JVAR_CNTNM0 + 7) {
             double &f = fac[v - MONORTM_JVAR_CNTNM0];
             if (f - e <= 0.) f += plus ? 2. * e : 0.;
             else f += plus ? e : -e;
+            m.cntnm_fac = fac;
         } else
-            sc[v - MONORTM_JVAR_SCLCPL] += plus ? e : -e;
-        if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, fac, sc[0], sc[1], sc[2], ibrd, 0,
-                                             nullptr, nullptr, Oout, wb + w_OM, wb + w_OC, wb + w_OL, vends, s))
-            return rc;
+            (v == MONORTM_JVAR_SCLCPL ? m.sclcpl : v == MONORTM_JVAR_SCLHW ? m.sclhw : m.y0res) += plus ? e : -e;
+        if (int rc = modm_dev_impl(c, m, false, outputs(Oout, nullptr), s)) return rc;
         // A continuum factor reaches O through ONE addend, its molecule's slot of OC (O = lines + sum of OC + cloud, continuum_kernel.hip),
         // and the adjoints read a state only in the difference O+ - O-.  The state therefore holds that slot instead of the total: a
         // continuum of 1e-12 of O (CO2 in the microwave) would vanish in the total's rounding, its slot keeps 16 digits of its own.
@@ -732,9 +784,7 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
     if (!ext) {
         // the base state straight from the caller's arrays, into the caller's O: what monortm_hip_modm_dev (ixsect = 1: _modm_xs_dev, its
         // ODXSEC into slot 0) returns for them
-        if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw,
-                                             y0res, ibrd, xs ? 1 : 0, xs ? XAMNT : nullptr, xX, O, wb + w_OM, wb + w_OC, wb + w_OL, vends, s))
-            return rc;
+        if (int rc = modm_dev_impl(c, base, false, outputs(O, xX), s)) return rc;
         k = ps = 1;
     }
     while (k < nstate) {
@@ -755,16 +805,32 @@ static int jac_states(Ctx *c, int nprof, int nwn, const double *wn, double dvset
 
 // What the full-Jacobian *_dev entries (monortm_hip_jacobian_dev, _scan_jacobian_dev, _obs_jacobian_dev) refuse first, and the chain
 // fields their adjoint launches share: the perturbed states' optical depths (jac_states) and the half-steps of the differences.
-int jac_full_check(Ctx *c, const char *entry, bool any_null, int nprof, int nwn, int nlay_max, int nmol, int quantity, int njac,
-                   const int *jac_mol, const void *K_W, int ixsect, const void *XAMNT) {
+int jac_full_check(Ctx *c, const char *entry, bool null, const AtmIn &atm, int quantity, const JacReq &jq, const void *K_W) {
     if (!c->shards.empty()) return multi_only_host(c);
     if (int rc = need_real8(c, entry)) return rc;
-    if (any_null) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (null) { c->err = "null array argument"; return MONORTM_EARG; }
     if (int rc = check_quantity(c, quantity)) return rc;
-    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
-    if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (atm.nmol < 7 || atm.nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
+    if (int rc = jac_check_mol(c, atm, jq, K_W)) return rc;
+    if (atm.nprof < 1 || atm.nprof > 65535 || atm.nwn < 1 || atm.nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     return MONORTM_OK;
+}
+// the fields all Rtm*Args share (O: the optical depths the launch reads), and those of the scans among them
+template <class Args>
+void rtm_args(Args &a, const AtmIn &atm, const SfcIn &sfc, const void *O) {
+    a.nprof = atm.nprof; a.nwn = atm.nwn; a.nlay_max = atm.nlay_max;
+    a.wn = atm.wn; a.T = atm.T; a.TZ = sfc.TZ; a.O = O; a.emiss = sfc.emiss; a.reflc = sfc.reflc; a.nlay = atm.nlay; a.irt = sfc.irt;
+}
+template <class Args>
+void scan_args(Args &a, const ScanIn &scan) {
+    a.npath = scan.npath; a.path = scan.path; a.sfc_per_path = scan.sfc_per_path;
+}
+// ... and what the adjoints (RtmJacArgs, RtmScanJacArgs, RtmObsJacArgs) take besides: the quantity, TMPSFC as an input, the K arrays of all three
+template <class Args>
+void adjoint_args(Args &a, const AtmIn &atm, const SfcIn &sfc, const void *O, const JacOut &out) {
+    rtm_args(a, atm, sfc, O);
+    a.quantity = sfc.quantity; a.tmpsfc = sfc.tmpsfc;
+    a.K_T = out.K_T; a.K_TZ = out.K_TZ; a.K_SFC = out.K_SFC;
 }
 template <class Args>   // RtmJacArgs, RtmScanJacArgs, RtmObsJacArgs
 void jac_chain_args(Args &a, const Ctx *c, int njac, void *K_W, void *K_CLW, const double *xO, size_t st) {
@@ -1499,24 +1565,21 @@ namespace {
 // holds the cross sections' optical depth of every state of this launch (xsec_kernel for the base state, xsec_jac_kernel for T +- h
 // and P (1 +- eps), zero for the states that run without them): xsec_kernel is not launched, XAMNT is not read, and the finish kernel
 // adds ODXSEC into O as ever.
-int modm_dev_impl(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
-                  const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw,
-                  double y0res, int ibrd, int ixsect, const void *XAMNT, void *ODXSEC, bool odx_given, void *O, void *O_BY_MOL, void *OC,
-                  void *O_CLW, const double *wn_ends, void *stream) {
+int modm_dev_impl(Ctx *c, const AtmIn &atm, bool odx_given, const ModmOut &out, hipStream_t s) {
+    const int nprof = atm.nprof, nwn = atm.nwn, nlay_max = atm.nlay_max, nmol = atm.nmol, ibrd = atm.ibrd, ixsect = atm.ixsect;
     if (!c->shards.empty()) return multi_only_host(c);
-    hipStream_t s = (hipStream_t)stream;
     if (!c->has_lines) { c->err = "this context holds no line table (created without a TAPE3 path): MODM needs one (GET_LNFL, modm.f90:187-190)"; return MONORTM_EARG; }
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !O || !O_BY_MOL || !OC || !O_CLW) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (any_null({atm.wn, atm.nlay, atm.P, atm.T, atm.CLW, atm.WKL, atm.WBRODL, atm.cntnm_fac, out.O, out.O_BY_MOL, out.OC, out.O_CLW})) { c->err = "null array argument"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
     // first / last wavenumber decide the ABSRB grid (modm.f90:180-185).  A caller that knows them passes them in
     // wn_ends (host) and the call stays asynchronous; otherwise they are fetched from device memory (one sync).
     double vends[2];
-    if (wn_ends) {
-        vends[0] = wn_ends[0];
-        vends[1] = wn_ends[1];
+    if (atm.wn_ends) {
+        vends[0] = atm.wn_ends[0];
+        vends[1] = atm.wn_ends[1];
     } else {
-        HIPCHK(c, hipMemcpyAsync(&vends[0], wn, sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&vends[1], wn + (nwn > 0 ? nwn - 1 : 0), sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&vends[0], atm.wn, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&vends[1], atm.wn + (nwn > 0 ? nwn - 1 : 0), sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
     }
     int rc = check_modm_args(c, nprof, nwn, nlay_max, nmol, ibrd, ixsect, vends[1]);
@@ -1524,14 +1587,14 @@ int modm_dev_impl(Ctx *c, int nprof, int nwn, const double *wn, double dvset, co
     ModmArgs a{};
     a.real_kind = c->real_kind;
     a.nprof = nprof; a.nwn = nwn; a.nlay_max = nlay_max; a.nmol = nmol; a.ibrd = ibrd;
-    a.dvset = dvset; a.sclcpl = sclcpl; a.sclhw = sclhw; a.y0res = y0res;
-    for (int i = 0; i < 7; i++) a.cntnm[i] = cntnm_fac[i];
-    a.wn = wn; a.P = P; a.T = T; a.CLW = CLW; a.WKL = WKL; a.WBRODL = WBRODL; a.nlay = nlay;
-    a.O = O; a.O_BY_MOL = O_BY_MOL; a.OC = OC; a.O_CLW = O_CLW; a.errflag = c->errflag;
+    a.dvset = atm.dvset; a.sclcpl = atm.sclcpl; a.sclhw = atm.sclhw; a.y0res = atm.y0res;
+    for (int i = 0; i < 7; i++) a.cntnm[i] = atm.cntnm_fac[i];
+    a.wn = atm.wn; a.P = atm.P; a.T = atm.T; a.CLW = atm.CLW; a.WKL = atm.WKL; a.WBRODL = atm.WBRODL; a.nlay = atm.nlay;
+    a.O = out.O; a.O_BY_MOL = out.O_BY_MOL; a.OC = out.OC; a.O_CLW = out.O_CLW; a.errflag = c->errflag;
     if (ixsect == 1) {
-        if ((!XAMNT && !odx_given) || !ODXSEC) { c->err = "IXSECT = 1: XAMNT / ODXSEC missing"; return MONORTM_EARG; }
+        if ((!atm.XAMNT && !odx_given) || !out.ODXSEC) { c->err = "IXSECT = 1: XAMNT / ODXSEC missing"; return MONORTM_EARG; }
         if (c->xs.nxs < 1) { c->err = "IXSECT = 1: no cross-section tables on this context (monortm_hip_xsec_tables)"; return MONORTM_EARG; }
-        a.XAMNT = XAMNT; a.ODXSEC = ODXSEC; a.nxs = c->xs.nxs;
+        a.XAMNT = atm.XAMNT; a.ODXSEC = out.ODXSEC; a.nxs = c->xs.nxs;
     }
 
     // what the call launches: decided from the shape, the table's and the device's constants alone (modm_plan.hpp)
@@ -1631,8 +1694,11 @@ int monortm_hip_modm_xs_dev(void *ctx, int nprof, int nwn, const double *wn, dou
                             void *O_CLW, const double *wn_ends, void *stream) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    return modm_dev_impl(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect,
-                         XAMNT, ODXSEC, false, O, O_BY_MOL, OC, O_CLW, wn_ends, stream);
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .dvset = dvset, .nlay = nlay, .nlay_max = nlay_max, .nmol = nmol, .P = P, .T = T,
+                    .CLW = CLW, .WKL = WKL, .WBRODL = WBRODL, .cntnm_fac = cntnm_fac, .sclcpl = sclcpl, .sclhw = sclhw, .y0res = y0res,
+                    .ibrd = ibrd, .ixsect = ixsect, .XAMNT = XAMNT, .wn_ends = wn_ends};
+    const ModmOut out{.ODXSEC = ODXSEC, .O = O, .O_BY_MOL = O_BY_MOL, .OC = OC, .O_CLW = O_CLW};
+    return modm_dev_impl(c, atm, false, out, (hipStream_t)stream);
 }
 
 int monortm_hip_rtm_dev(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
@@ -1646,10 +1712,11 @@ int monortm_hip_rtm_dev(void *ctx, int nprof, int nwn, const double *wn, const i
     if (!wn || !nlay || !irt || !T || !TZ || !O || !tmpsfc || !emiss || !reflc || !RUP || !RDN || !TRTOT || !RAD || !TB) { c->err = "null array argument"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
     if (nprof < 1 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc};
     RtmArgs a{};
-    a.real_kind = c->real_kind;
-    a.nprof = nprof; a.nwn = nwn; a.nlay_max = nlay_max; a.iout = iout;
-    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    rtm_args(a, atm, sfc, O);
+    a.real_kind = c->real_kind; a.iout = iout;
     a.tmpsfc = tmpsfc; a.RUP = RUP; a.RDN = RDN; a.TRTOT = TRTOT; a.RAD = RAD; a.TB = TB; a.TMR = TMR;
     Ctx::Ev ev{};
     prof_begin(c, s, 2, ev);
@@ -1765,13 +1832,16 @@ int monortm_hip_rtm_scan_dev(void *ctx, int nprof, int npath, int nwn, const dou
     if (!c) return null_ctx();
     if (!c->shards.empty()) return multi_only_host(c);
     hipStream_t s = (hipStream_t)stream;
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !RUP || !RDN || !TRTOT || !RAD || !TB) { c->err = "null array argument"; return MONORTM_EARG; }
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    if (any_null({wn, nlay, irt, T, TZ, O, path, tmpsfc, emiss, reflc, RUP, RDN, TRTOT, RAD, TB})) { c->err = "null array argument"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
     RtmScanArgs a{};
-    a.real_kind = c->real_kind;
-    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.iout = iout; a.sfc_per_path = sfc_per_path;
-    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
+    rtm_args(a, atm, sfc, O);
+    scan_args(a, scan);
+    a.real_kind = c->real_kind; a.iout = iout;
     a.tmpsfc = tmpsfc; a.RUP = RUP; a.RDN = RDN; a.TRTOT = TRTOT; a.RAD = RAD; a.TB = TB; a.TMR = TMR;
     a.errflag = c->errflag;
     Ctx::Ev ev{};
@@ -1788,10 +1858,12 @@ int monortm_hip_rtm_scan(void *ctx, int nprof, int npath, int nwn, const double 
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
     DeviceGuard guard;
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !RUP || !RDN || !TRTOT || !RAD || !TB) { c->err = "null array argument"; return MONORTM_EARG; }
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    if (any_null({wn, nlay, irt, T, TZ, O, path, tmpsfc, emiss, reflc, RUP, RDN, TRTOT, RAD, TB})) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
     // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
-    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
+    if (int rc = scan_check_path(c, atm, scan)) return rc;
     const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vo = (size_t)nwn * npath * d, vs = sfc_per_path ? vo : (size_t)nwn * d;
     HostCall hc(4, 2);
     const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
@@ -1808,305 +1880,9 @@ int monortm_hip_rtm_scan(void *ctx, int nprof, int npath, int nwn, const double 
     });
 }
 
-// ---- Jacobians (DESIGN.md section 3.6) ----------------------------------------------------------------------------------
-int monortm_hip_rtm_jac_dev(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
-                            const void *T, const void *TZ, const void *O, const void *tmpsfc, const void *emiss, const void *reflc,
-                            void *RAD, void *TB, void *K_O, void *K_T, void *K_TZ, void *K_SFC, void *stream) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
-    if (!c->shards.empty()) return multi_only_host(c);
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !tmpsfc || !emiss || !reflc || !RAD || !TB || !K_O || !K_T || !K_TZ || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    if (int rcq = check_quantity(c, quantity)) return rcq;
-    if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
-    if (int rcd = check_device(c)) return rcd;
-    RtmJacArgs a{};
-    a.nprof = nprof; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = c->real_kind;
-    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
-    launch_rtm_jac(a, false, (hipStream_t)stream);
-    HIPCHK(c, hipGetLastError());
-    return MONORTM_OK;
-}
-
-// MODM of the base and the 2 (1 + njac) perturbed states (jac_states), then the adjoint chained with their differences.
-int monortm_hip_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                             const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                             double sclcpl, double sclhw, double y0res, int ibrd,
-                             int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
-                             const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD,
-                             void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC, const double *wn_ends,
-                             void *stream) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
-    hipStream_t s = (hipStream_t)stream;
-    const bool any_null = !wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !O ||
-                          !RAD || !TB || !K_T || !K_TZ || !K_CLW || !K_SFC;
-    if (int rc = jac_full_check(c, "monortm_hip_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
-    if (int rcd = check_device(c)) return rcd;
-    double *xO = nullptr;
-    size_t st = 0;
-    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, XAMNT, njac,
-                            jac_mol, O, wn_ends, s, &xO, &st))
-        return rc;
-    RtmJacArgs a{};
-    a.nprof = nprof; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity;
-    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
-    jac_chain_args(a, c, njac, K_W, K_CLW, xO, st);
-    launch_rtm_jac(a, true, s);
-    HIPCHK(c, hipGetLastError());
-    return MONORTM_OK;
-}
-
-int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                             const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                             double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
-                             const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD,
-                             void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC, const double *wn_ends,
-                             void *stream) {
-    return monortm_hip_jacobian_xs_dev(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
-                                       ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, O, RAD, TB, K_T, K_TZ, K_W, K_CLW,
-                                       K_O, K_SFC, wn_ends, stream);
-}
-
-int monortm_hip_rtm_jac(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
-                        const void *T, const void *TZ, const void *O, const void *tmpsfc, const void *emiss, const void *reflc, void *RAD,
-                        void *TB, void *K_O, void *K_T, void *K_TZ, void *K_SFC) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !tmpsfc || !emiss || !reflc || !RAD || !TB || !K_O || !K_T || !K_TZ || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    DeviceGuard guard;
-    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, v = (size_t)nwn * d, w = l * nwn;
-    HostCall hc(8);
-    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
-              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, w), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, v), i_rf = hc.in(reflc, v);
-    const int o_rad = hc.out(RAD, v), o_tb = hc.out(TB, v), o_ko = hc.out(K_O, w), o_kt = hc.out(K_T, w), o_ktz = hc.out(K_TZ, (l + d) * nwn),
-              o_ks = hc.out(K_SFC, 3 * v);
-    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
-        return monortm_hip_rtm_jac_dev(s, n, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], quantity, dv[i_T], dv[i_TZ],
-                                       dv[i_O], dv[i_ts], dv[i_em], dv[i_rf], dv[o_rad], dv[o_tb], dv[o_ko], dv[o_kt], dv[o_ktz], dv[o_ks], s->hs);
-    });
-}
-
-int monortm_hip_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                         const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                         double sclcpl, double sclhw, double y0res, int ibrd,
-                         int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
-                         const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD, void *TB,
-                         void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
-    if (int rc = need_real8(c, "monortm_hip_jacobian")) return rc;
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !O || !RAD ||
-        !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    DeviceGuard guard;
-    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
-    const size_t d = 8, l = (size_t)nlay_max * d, v = (size_t)nwn * d, w = l * nwn;
-    HostCall hc(8);
-    hc.flag = true;
-    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
-              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l),
-              i_XA = hc.in(ixsect == 1 ? XAMNT : nullptr, l * ctx_nxs(c)), i_TZ = hc.in(TZ, l + d),
-              i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, v), i_rf = hc.in(reflc, v);
-    const int o_O = hc.out(O, w), o_rad = hc.out(RAD, v), o_tb = hc.out(TB, v), o_kt = hc.out(K_T, w), o_ktz = hc.out(K_TZ, (l + d) * nwn),
-              o_kw = hc.out(njac ? K_W : nullptr, w * njac), o_kc = hc.out(K_CLW, w), o_ko = hc.out(K_O, w), o_ks = hc.out(K_SFC, 3 * v);
-    // every share's states are checked on its own device's context, before anything of it is staged
-    auto pre = [&](Ctx *s, int p0, int n) -> int {
-        if (nmol < 1) { s->err = "bad nmol"; return MONORTM_EARG; }
-        return jac_check_states(s, n, nwn, wn, nlay + p0, nlay_max, hc.host(i_T, p0));
-    };
-    return hc.run(c, nprof, pre, [&](Ctx *s, int, int n, char *const *dv) {
-        const double ends[2] = {wn[0], wn[nwn - 1]};
-        return monortm_hip_jacobian_xs_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C], dv[i_W],
-                                        dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, dv[i_XA],
-                                        (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em], dv[i_rf],
-                                        quantity, njac, jac_mol, dv[o_O], dv[o_rad], dv[o_tb], dv[o_kt], dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ko],
-                                        dv[o_ks], ends, s->hs);
-    });
-}
-
-int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                         const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                         double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
-                         const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD, void *TB,
-                         void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC) {
-    return monortm_hip_jacobian_xs(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, 0,
-                                   nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, O, RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O, K_SFC);
-}
-
-// ---- Jacobians of path scans (DESIGN.md section 3.8) ----------------------------------------------------------------------
-int monortm_hip_rtm_scan_jac_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
-                                 int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc,
-                                 int sfc_per_path, const void *emiss, const void *reflc, void *RAD, void *TB, void *K_O, void *K_PATH,
-                                 void *K_T, void *K_TZ, void *K_SFC, void *stream) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
-    if (!c->shards.empty()) return multi_only_host(c);
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !RAD || !TB || !K_T || !K_TZ || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    if (int rcq = check_quantity(c, quantity)) return rcq;
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
-    if (int rcd = check_device(c)) return rcd;
-    RtmScanJacArgs a{};
-    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = c->real_kind;
-    a.sfc_per_path = sfc_per_path;
-    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_PATH = K_PATH; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
-    a.errflag = c->errflag;
-    launch_rtm_scan_jac(a, false, (hipStream_t)stream);
-    HIPCHK(c, hipGetLastError());
-    return MONORTM_OK;
-}
-
-// MODM of the base and the 2 (1 + njac) perturbed states ONCE (jac_states: what monortm_hip_jacobian_dev runs), then one launch of the
-// adjoint along every path, chained with the states' differences.
-int monortm_hip_scan_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                                  const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL,
-                                  const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd,
-                                  int ixsect, const void *XAMNT, const int *irt,
-                                  const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
-                                  const int *jac_mol, int npath, const void *path, int sfc_per_path, void *O, void *RAD, void *TB, void *K_T,
-                                  void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_PATH, void *K_SFC, const double *wn_ends,
-                                  void *stream) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
-    hipStream_t s = (hipStream_t)stream;
-    const bool any_null = !wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path ||
-                          !O || !RAD || !TB || !K_T || !K_TZ || !K_CLW || !K_SFC;
-    if (int rc = jac_full_check(c, "monortm_hip_scan_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    if (int rcd = check_device(c)) return rcd;
-    double *xO = nullptr;
-    size_t st = 0;
-    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, XAMNT, njac,
-                            jac_mol, O, wn_ends, s, &xO, &st))
-        return rc;
-    RtmScanJacArgs a{};
-    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity;
-    a.sfc_per_path = sfc_per_path;
-    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.RAD = RAD; a.TB = TB; a.K_O = K_O; a.K_PATH = K_PATH; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
-    jac_chain_args(a, c, njac, K_W, K_CLW, xO, st);
-    a.errflag = c->errflag;
-    launch_rtm_scan_jac(a, true, s);
-    HIPCHK(c, hipGetLastError());
-    return MONORTM_OK;
-}
-
-int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                                  const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL,
-                                  const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd, const int *irt,
-                                  const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
-                                  const int *jac_mol, int npath, const void *path, int sfc_per_path, void *O, void *RAD, void *TB, void *K_T,
-                                  void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_PATH, void *K_SFC, const double *wn_ends,
-                                  void *stream) {
-    return monortm_hip_scan_jacobian_xs_dev(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
-                                            ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, O,
-                                            RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O, K_PATH, K_SFC, wn_ends, stream);
-}
-
-int monortm_hip_rtm_scan_jac(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
-                             int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc,
-                             int sfc_per_path, const void *emiss, const void *reflc, void *RAD, void *TB, void *K_O, void *K_PATH, void *K_T,
-                             void *K_TZ, void *K_SFC) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
-    DeviceGuard guard;
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !RAD || !TB || !K_T || !K_TZ || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    if (int rc = check_quantity(c, quantity)) return rc;
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
-    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vo = (size_t)nwn * npath * d, vs = sfc_per_path ? vo : (size_t)nwn * d,
-                 wo = l * nwn * npath;
-    HostCall hc(8);
-    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
-              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, l * nwn), i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs),
-              i_rf = hc.in(reflc, vs);
-    const int o_rad = hc.out(RAD, vo), o_tb = hc.out(TB, vo), o_ko = hc.out(K_O, wo), o_kp = hc.out(K_PATH, wo), o_kt = hc.out(K_T, wo),
-              o_ktz = hc.out(K_TZ, (l + d) * nwn * npath), o_ks = hc.out(K_SFC, 3 * vo);
-    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
-        return monortm_hip_rtm_scan_jac_dev(s, n, npath, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], quantity, dv[i_T],
-                                            dv[i_TZ], dv[i_O], dv[i_f], dv[i_ts], sfc_per_path, dv[i_em], dv[i_rf], dv[o_rad], dv[o_tb], dv[o_ko],
-                                            dv[o_kp], dv[o_kt], dv[o_ktz], dv[o_ks], s->hs);
-    });
-}
-
-int monortm_hip_scan_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                              const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                              double sclcpl, double sclhw, double y0res, int ibrd,
-                              int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
-                              const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
-                              int sfc_per_path, void *O, void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O,
-                              void *K_PATH, void *K_SFC) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return null_ctx();
-    if (int rc = need_real8(c, "monortm_hip_scan_jacobian")) return rc;
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !RAD ||
-        !TB || !K_T || !K_TZ || !K_CLW || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    DeviceGuard guard;
-    // the whole call is checked before the first device is touched: a refusal launches nothing anywhere
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
-    if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
-    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
-    if (int rc = jac_check_states(c, nprof, nwn, wn, nlay, nlay_max, T)) return rc;
-    const size_t d = 8, l = (size_t)nlay_max * d, w = l * nwn, vo = (size_t)nwn * npath * d, vs = sfc_per_path ? vo : (size_t)nwn * d, wo = w * npath;
-    HostCall hc(8);
-    hc.flag = true;
-    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
-              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l),
-              i_XA = hc.in(ixsect == 1 ? XAMNT : nullptr, l * ctx_nxs(c)), i_TZ = hc.in(TZ, l + d),
-              i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs), i_rf = hc.in(reflc, vs);
-    const int o_O = hc.out(O, w), o_rad = hc.out(RAD, vo), o_tb = hc.out(TB, vo), o_kt = hc.out(K_T, wo), o_ktz = hc.out(K_TZ, (l + d) * nwn * npath),
-              o_kw = hc.out(njac ? K_W : nullptr, wo * njac), o_kc = hc.out(K_CLW, wo), o_ko = hc.out(K_O, wo), o_kp = hc.out(K_PATH, wo),
-              o_ks = hc.out(K_SFC, 3 * vo);
-    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
-        const double ends[2] = {wn[0], wn[nwn - 1]};
-        return monortm_hip_scan_jacobian_xs_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C],
-                                             dv[i_W], dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, dv[i_XA],
-                                        (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em],
-                                             dv[i_rf], quantity, njac, jac_mol, npath, dv[i_f], sfc_per_path, dv[o_O], dv[o_rad], dv[o_tb], dv[o_kt],
-                                             dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ko], dv[o_kp], dv[o_ks], ends, s->hs);
-    });
-}
-
-int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                              const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                              double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
-                              const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
-                              int sfc_per_path, void *O, void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O,
-                              void *K_PATH, void *K_SFC) {
-    return monortm_hip_scan_jacobian_xs(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
-                                        ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, O, RAD,
-                                        TB, K_T, K_TZ, K_W, K_CLW, K_O, K_PATH, K_SFC);
-}
-
-
-// ---- channel- and beam-averaged Jacobians of path scans (DESIGN.md section 3.9) ---------------------------------------------
 }  // extern "C"
 
+// ---- measurement operators: their checks and device tables ------------------------------------------------
 namespace {
 constexpr int kObsMaxViews = 65535, kObsMaxChan = 65536;
 constexpr size_t kObsMaxTable = size_t(1) << 26;   // entries of the per-block membership table (256 MB of int)
@@ -2206,38 +1982,238 @@ int obs_upload(Ctx *c, Ctx::Obs &ob, const int *view_start, const double *wpath,
     return MONORTM_OK;
 }
 
-void obs_args(RtmObsJacArgs &a, const Ctx::Obs &ob) {
+template <class Args>   // RtmObsJacArgs, RtmObsArgs
+void obs_args(Args &a, const Ctx::Obs &ob) {
     a.nview = ob.nview; a.nchan = ob.nchan;
     a.view_start = ob.view_start; a.wpath = ob.wpath; a.mstart = ob.mstart; a.mlane = ob.mlane; a.mw = ob.mw;
 }
 
-// monortm_hip_rtm_obs_jac_dev with the element size of the outputs as an argument: the host entry of a real_kind = 4 context has the
-// kernel accumulate in double and rounds once, when it unpacks
-int rtm_obs_jac_dev_impl(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
-                         const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path,
-                         const void *emiss, const void *reflc, int obs, void *Y, void *K_T, void *K_TZ, void *K_SFC, int out_kind,
-                         void *stream) {
+// ---- the inputs of the Jacobian and measurement host entries, declared in ONE place ------------------------------------------------
+// The index of every input among the call's arrays (HostCall), -1: none (the entry has no such argument, or it is null where it may be).
+struct HostIn {
+    int wn, nlay, irt, P, T, CLW, WKL, WBRODL, XAMNT, TZ, O, path, tmpsfc, emiss, reflc;
+};
+// O: the optical depths an entry is handed (null: it runs MODM itself, and O is among the outputs it declares)
+HostIn declare_inputs(HostCall &hc, const Ctx *c, const AtmIn &atm, const SfcIn &sfc, const ScanIn &scan, const void *O) {
+    const size_t d = (size_t)c->real_kind, l = (size_t)atm.nlay_max * d, vs = (size_t)atm.nwn * (scan.sfc_per_path ? scan.npath : 1) * d;
+    auto in = [&](const void *p, size_t per_profile) { return p ? hc.in(p, per_profile) : -1; };
+    HostIn ix;
+    ix.wn = hc.in_shared(atm.wn, atm.nwn * sizeof(double)); ix.nlay = in(atm.nlay, sizeof(int)); ix.irt = in(sfc.irt, sizeof(int));
+    ix.P = in(atm.P, l); ix.T = in(atm.T, l); ix.CLW = in(atm.CLW, l); ix.WKL = in(atm.WKL, l * atm.nmol); ix.WBRODL = in(atm.WBRODL, l);
+    ix.XAMNT = in(atm.ixsect == 1 ? atm.XAMNT : nullptr, l * ctx_nxs(c));
+    ix.TZ = in(sfc.TZ, l + d); ix.O = in(O, l * atm.nwn); ix.path = in(scan.path, l * scan.npath);
+    ix.tmpsfc = in(sfc.tmpsfc, d); ix.emiss = in(sfc.emiss, vs); ix.reflc = in(sfc.reflc, vs);
+    return ix;
+}
+// The groups of one share on its device: n profiles at the device addresses of the declared arrays, the grid's ends from the host's wn
+struct Share {
+    AtmIn atm;
+    SfcIn sfc;
+    ScanIn scan;
+    const void *O = nullptr;
+    double ends[2] = {0., 0.};
+    Share(const HostIn &ix, char *const *dv, int n, const AtmIn &h_atm, const SfcIn &h_sfc, const ScanIn &h_scan)
+        : atm(h_atm), sfc(h_sfc), scan(h_scan) {
+        auto at = [&](int i) -> const void * { return i < 0 ? nullptr : dv[i]; };
+        atm.nprof = n;
+        atm.wn = static_cast<const double *>(at(ix.wn)); atm.nlay = static_cast<const int *>(at(ix.nlay));
+        atm.P = at(ix.P); atm.T = at(ix.T); atm.CLW = at(ix.CLW); atm.WKL = at(ix.WKL); atm.WBRODL = at(ix.WBRODL); atm.XAMNT = at(ix.XAMNT);
+        ends[0] = h_atm.wn[0]; ends[1] = h_atm.wn[h_atm.nwn - 1];
+        atm.wn_ends = ends;
+        sfc.irt = static_cast<const int *>(at(ix.irt)); sfc.TZ = at(ix.TZ); sfc.tmpsfc = at(ix.tmpsfc); sfc.emiss = at(ix.emiss); sfc.reflc = at(ix.reflc);
+        scan.path = at(ix.path);
+        O = at(ix.O);
+    }
+    Share(const Share &) = delete;   // (atm.wn_ends points into the object)
+    Share &operator=(const Share &) = delete;
+};
+
+// ---- the adjoints of RTM on given optical depths O (monortm_hip_rtm_jac_dev, _rtm_scan_jac_dev, _rtm_obs_jac_dev) ---------------------
+int rtm_jac_dev_impl(Ctx *c, const AtmIn &atm, const SfcIn &sfc, const void *O, const JacOut &out, hipStream_t s) {
     if (!c->shards.empty()) return multi_only_host(c);
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !Y || !K_T || !K_TZ || !K_SFC) {
+    if (any_null({atm.wn, atm.nlay, sfc.irt, atm.T, sfc.TZ, O, sfc.tmpsfc, sfc.emiss, sfc.reflc, out.RAD, out.TB, out.K_O, out.K_T, out.K_TZ, out.K_SFC})) {
         c->err = "null array argument";
         return MONORTM_EARG;
     }
-    if (int rcq = check_quantity(c, quantity)) return rcq;
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
-    Ctx::Obs *ob = nullptr;
-    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
+    if (int rcq = check_quantity(c, sfc.quantity)) return rcq;
+    if (atm.nprof < 1 || atm.nprof > 65535 || atm.nwn < 1 || atm.nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
-    RtmObsJacArgs a{};
-    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = c->real_kind;
-    a.sfc_per_path = sfc_per_path;
-    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.Y = Y; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
-    a.errflag = c->errflag;
-    obs_args(a, *ob);
-    launch_rtm_obs_jac(a, false, out_kind, (hipStream_t)stream);
+    RtmJacArgs a{};
+    adjoint_args(a, atm, sfc, O, out);
+    a.real_kind = c->real_kind;
+    a.RAD = out.RAD; a.TB = out.TB; a.K_O = out.K_O;
+    launch_rtm_jac(a, false, s);
     HIPCHK(c, hipGetLastError());
     return MONORTM_OK;
+}
+
+int rtm_scan_jac_dev_impl(Ctx *c, const AtmIn &atm, const SfcIn &sfc, const ScanIn &scan, const void *O, const JacOut &out, hipStream_t s) {
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (any_null({atm.wn, atm.nlay, sfc.irt, atm.T, sfc.TZ, O, scan.path, sfc.tmpsfc, sfc.emiss, sfc.reflc, out.RAD, out.TB, out.K_T, out.K_TZ, out.K_SFC})) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (int rcq = check_quantity(c, sfc.quantity)) return rcq;
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
+    if (atm.nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (int rcd = check_device(c)) return rcd;
+    RtmScanJacArgs a{};
+    adjoint_args(a, atm, sfc, O, out);
+    scan_args(a, scan);
+    a.real_kind = c->real_kind;
+    a.RAD = out.RAD; a.TB = out.TB; a.K_O = out.K_O; a.K_PATH = out.K_PATH;
+    a.errflag = c->errflag;
+    launch_rtm_scan_jac(a, false, s);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+// out_kind: the element size of the outputs - the host entry of a real_kind = 4 context has the kernel accumulate in double and rounds
+// once, when it unpacks
+int rtm_obs_jac_dev_impl(Ctx *c, const AtmIn &atm, const SfcIn &sfc, const ScanIn &scan, const void *O, int obs, const JacOut &out, int out_kind,
+                         hipStream_t s) {
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (any_null({atm.wn, atm.nlay, sfc.irt, atm.T, sfc.TZ, O, scan.path, sfc.tmpsfc, sfc.emiss, sfc.reflc, out.Y, out.K_T, out.K_TZ, out.K_SFC})) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (int rcq = check_quantity(c, sfc.quantity)) return rcq;
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
+    if (atm.nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, scan.npath, atm.nwn, &ob)) return rc;
+    if (int rcd = check_device(c)) return rcd;
+    RtmObsJacArgs a{};
+    adjoint_args(a, atm, sfc, O, out);
+    scan_args(a, scan);
+    obs_args(a, *ob);
+    a.real_kind = c->real_kind;
+    a.Y = out.Y;
+    a.errflag = c->errflag;
+    launch_rtm_obs_jac(a, false, out_kind, s);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+// ---- the full Jacobians (monortm_hip_jacobian_xs_dev, _scan_jacobian_xs_dev, _obs_jacobian_xs_dev), written once ------------------------
+// MODM of the base and the 2 (1 + njac) perturbed states ONCE (jac_states), then ONE launch of the family's adjoint, chained with the
+// states' differences: along the profile's own path, along every path of a scan, or contracted per measurement.
+enum JacFamily { JAC_PLAIN, JAC_SCAN, JAC_OBS };
+const char *const kJacEntry[3] = {"monortm_hip_jacobian", "monortm_hip_scan_jacobian", "monortm_hip_obs_jacobian"};
+// the pointers a family requires (K_O and K_PATH are optional; K_W may be null with njac = 0: jac_check_mol)
+bool jac_full_null(JacFamily fam, const AtmIn &atm, const SfcIn &sfc, const ScanIn &scan, const JacOut &out) {
+    if (any_null({atm.wn, atm.nlay, atm.P, atm.T, atm.CLW, atm.WKL, atm.WBRODL, atm.cntnm_fac, sfc.irt, sfc.TZ, sfc.tmpsfc, sfc.emiss, sfc.reflc,
+                  out.O, out.K_T, out.K_TZ, out.K_CLW, out.K_SFC}))
+        return true;
+    if (fam != JAC_PLAIN && !scan.path) return true;
+    return fam == JAC_OBS ? !out.Y : any_null({out.RAD, out.TB});
+}
+int jac_full(Ctx *c, JacFamily fam, const AtmIn &atm, const SfcIn &sfc, const JacReq &jq, const ScanIn &scan, int obs, const JacOut &out,
+             hipStream_t s) {
+    if (int rc = jac_full_check(c, kJacEntry[fam], jac_full_null(fam, atm, sfc, scan, out), atm, sfc.quantity, jq, out.K_W)) return rc;
+    if (fam != JAC_PLAIN)
+        if (int rc = scan_check_args(c, atm, scan)) return rc;
+    Ctx::Obs *ob = nullptr;
+    if (fam == JAC_OBS)
+        if (int rc = obs_for_call(c, obs, scan.npath, atm.nwn, &ob)) return rc;
+    if (int rcd = check_device(c)) return rcd;
+    double *xO = nullptr;
+    size_t st = 0;
+    if (int rc = jac_states(c, atm, jq, out.O, s, &xO, &st)) return rc;
+    if (fam == JAC_PLAIN) {
+        RtmJacArgs a{};
+        adjoint_args(a, atm, sfc, out.O, out);
+        jac_chain_args(a, c, jq.njac, out.K_W, out.K_CLW, xO, st);
+        a.RAD = out.RAD; a.TB = out.TB; a.K_O = out.K_O;
+        launch_rtm_jac(a, true, s);
+    } else if (fam == JAC_SCAN) {
+        RtmScanJacArgs a{};
+        adjoint_args(a, atm, sfc, out.O, out);
+        scan_args(a, scan);
+        jac_chain_args(a, c, jq.njac, out.K_W, out.K_CLW, xO, st);
+        a.RAD = out.RAD; a.TB = out.TB; a.K_O = out.K_O; a.K_PATH = out.K_PATH;
+        a.errflag = c->errflag;
+        launch_rtm_scan_jac(a, true, s);
+    } else {
+        RtmObsJacArgs a{};
+        adjoint_args(a, atm, sfc, out.O, out);
+        scan_args(a, scan);
+        obs_args(a, *ob);
+        jac_chain_args(a, c, jq.njac, out.K_W, out.K_CLW, xO, st);
+        a.Y = out.Y;
+        a.errflag = c->errflag;
+        launch_rtm_obs_jac(a, true, 8, s);
+    }
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+// ---- the forward measurement operator: channel- and beam-averaged scans (DESIGN.md section 3.10) ------------------------------
+int obs_check_quantity(Ctx *c, int quantity) {
+    if (quantity < 0 || quantity > 2) { c->err = "quantity must be 0 (RAD), 1 (TB) or 2 (band TB)"; return MONORTM_EARG; }
+    return MONORTM_OK;
+}
+// the channels' nominal wavenumbers of a host call (quantity 2 only): all of them, before anything is staged
+int obs_check_vcen(Ctx *c, int quantity, const double *vcen, int nchan) {
+    if (quantity != 2) return MONORTM_OK;
+    if (!vcen) { c->err = "quantity 2 (band TB) needs vcen [nchan]"; return MONORTM_EARG; }
+    for (int i = 0; i < nchan; i++)
+        if (!(vcen[i] > 0. && std::isfinite(vcen[i]))) { c->err = "vcen[" + std::to_string(i) + "] is not a finite wavenumber > 0"; return MONORTM_EARG; }
+    return MONORTM_OK;
+}
+
+// monortm_hip_rtm_obs_dev with the element size of Y as an argument: the host entry of a real_kind = 4 context has the kernel accumulate
+// (and convert to the band temperature) in double and rounds once, when it unpacks
+int rtm_obs_dev_impl(Ctx *c, const AtmIn &atm, const SfcIn &sfc, const ScanIn &scan, const void *O, int obs, const double *vcen, void *Y,
+                     int out_kind, hipStream_t s) {
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (any_null({atm.wn, atm.nlay, sfc.irt, atm.T, sfc.TZ, O, scan.path, sfc.tmpsfc, sfc.emiss, sfc.reflc, Y})) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (int rcq = obs_check_quantity(c, sfc.quantity)) return rcq;
+    if (sfc.quantity == 2 && !vcen) { c->err = "quantity 2 (band TB) needs vcen [nchan]"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
+    if (atm.nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, scan.npath, atm.nwn, &ob)) return rc;
+    if (int rcd = check_device(c)) return rcd;
+    RtmObsArgs a{};
+    rtm_args(a, atm, sfc, O);
+    scan_args(a, scan);
+    obs_args(a, *ob);
+    a.quantity = sfc.quantity; a.real_kind = c->real_kind; a.tmpsfc = sfc.tmpsfc;
+    a.vcen = sfc.quantity == 2 ? vcen : nullptr;
+    a.Y = Y;
+    a.errflag = c->errflag;
+    launch_rtm_obs(a, out_kind, s);
+    HIPCHK(c, hipGetLastError());
+    return MONORTM_OK;
+}
+
+// monortm_hip_obs_dev likewise: ONE MODM pass into the caller's O (the MODM outputs the operator does not use go to the context's
+// workspace, grown on demand and kept), then ONE launch of the forward kernel
+int obs_dev_impl(Ctx *c, const AtmIn &atm, const SfcIn &sfc, const ScanIn &scan, int obs, const double *vcen, void *O, void *Y, int out_kind,
+                 hipStream_t s) {
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (any_null({atm.wn, atm.nlay, atm.P, atm.T, atm.CLW, atm.WKL, atm.WBRODL, atm.cntnm_fac, sfc.irt, sfc.TZ, sfc.tmpsfc, sfc.emiss, sfc.reflc,
+                  scan.path, O, Y})) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (int rcq = obs_check_quantity(c, sfc.quantity)) return rcq;
+    if (sfc.quantity == 2 && !vcen) { c->err = "quantity 2 (band TB) needs vcen [nchan]"; return MONORTM_EARG; }
+    if (atm.nmol < 7 || atm.nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
+    if (atm.nprof < 1 || atm.nprof > 65535 || atm.nwn < 1 || atm.nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
+    Ctx::Obs *ob = nullptr;
+    if (int rc = obs_for_call(c, obs, scan.npath, atm.nwn, &ob)) return rc;
+    if (int rcd = check_device(c)) return rcd;
+    const size_t st = (size_t)atm.nprof * atm.nlay_max * atm.nwn * (size_t)c->real_kind;   // bytes of one [nprof][nlay_max][nwn] array
+    Arena ws;
+    const size_t w_OM = ws.add(st * atm.nmol), w_OC = ws.add(st * MONORTM_NCONT), w_OL = ws.add(st);
+    if (int rc = jac_ws_reserve(c, ws.size)) return rc;
+    char *wb = static_cast<char *>(c->jac_ws);
+    const ModmOut mo{.O = O, .O_BY_MOL = wb + w_OM, .OC = wb + w_OC, .O_CLW = wb + w_OL};
+    if (int rc = modm_dev_impl(c, atm, false, mo, s)) return rc;   // (ixsect = 0: the entries have no cross-section arguments)
+    return rtm_obs_dev_impl(c, atm, sfc, scan, O, obs, vcen, Y, out_kind, s);
 }
 
 }  // namespace
@@ -2297,50 +2273,278 @@ int monortm_hip_obs_destroy(void *ctx, int handle) {
     return MONORTM_OK;
 }
 
+// ---- Jacobians (DESIGN.md section 3.6) ----------------------------------------------------------------------------------
+int monortm_hip_rtm_jac_dev(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
+                            const void *T, const void *TZ, const void *O, const void *tmpsfc, const void *emiss, const void *reflc,
+                            void *RAD, void *TB, void *K_O, void *K_T, void *K_TZ, void *K_SFC, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const JacOut out{.RAD = RAD, .TB = TB, .K_T = K_T, .K_TZ = K_TZ, .K_O = K_O, .K_SFC = K_SFC};
+    return rtm_jac_dev_impl(c, atm, sfc, O, out, (hipStream_t)stream);
+}
+
+int monortm_hip_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                                const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                                double sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const void *XAMNT, const int *irt,
+                                const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
+                                const int *jac_mol, void *O, void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O,
+                                void *K_SFC, const double *wn_ends, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .dvset = dvset, .nlay = nlay, .nlay_max = nlay_max, .nmol = nmol, .P = P, .T = T,
+                    .CLW = CLW, .WKL = WKL, .WBRODL = WBRODL, .cntnm_fac = cntnm_fac, .sclcpl = sclcpl, .sclhw = sclhw, .y0res = y0res,
+                    .ibrd = ibrd, .ixsect = ixsect, .XAMNT = XAMNT, .wn_ends = wn_ends};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const JacReq jq{.njac = njac, .jac_mol = jac_mol};
+    const JacOut out{.O = O, .RAD = RAD, .TB = TB, .K_T = K_T, .K_TZ = K_TZ, .K_W = K_W, .K_CLW = K_CLW, .K_O = K_O, .K_SFC = K_SFC};
+    return jac_full(c, JAC_PLAIN, atm, sfc, jq, ScanIn(), 0, out, (hipStream_t)stream);
+}
+
+int monortm_hip_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                             const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                             double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                             const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD,
+                             void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC, const double *wn_ends,
+                             void *stream) {
+    return monortm_hip_jacobian_xs_dev(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
+                                       ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, O, RAD, TB, K_T, K_TZ, K_W, K_CLW,
+                                       K_O, K_SFC, wn_ends, stream);
+}
+
+int monortm_hip_rtm_jac(void *ctx, int nprof, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
+                        const void *T, const void *TZ, const void *O, const void *tmpsfc, const void *emiss, const void *reflc, void *RAD,
+                        void *TB, void *K_O, void *K_T, void *K_TZ, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    if (any_null({wn, nlay, irt, T, TZ, O, tmpsfc, emiss, reflc, RAD, TB, K_O, K_T, K_TZ, K_SFC})) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    DeviceGuard guard;
+    if (int rc = jac_check_args(c, atm, quantity)) return rc;
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, v = (size_t)nwn * d, w = l * nwn;
+    HostCall hc(8);
+    const HostIn in = declare_inputs(hc, c, atm, sfc, ScanIn(), O);
+    const int o_rad = hc.out(RAD, v), o_tb = hc.out(TB, v), o_ko = hc.out(K_O, w), o_kt = hc.out(K_T, w), o_ktz = hc.out(K_TZ, (l + d) * nwn),
+              o_ks = hc.out(K_SFC, 3 * v);
+    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
+        const Share sh(in, dv, n, atm, sfc, ScanIn());
+        const JacOut out{.RAD = dv[o_rad], .TB = dv[o_tb], .K_T = dv[o_kt], .K_TZ = dv[o_ktz], .K_O = dv[o_ko], .K_SFC = dv[o_ks]};
+        return rtm_jac_dev_impl(s, sh.atm, sh.sfc, sh.O, out, s->hs);
+    });
+}
+
+int monortm_hip_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                            const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                            double sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const void *XAMNT, const int *irt, const void *TZ,
+                            const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O,
+                            void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .dvset = dvset, .nlay = nlay, .nlay_max = nlay_max, .nmol = nmol, .P = P, .T = T,
+                    .CLW = CLW, .WKL = WKL, .WBRODL = WBRODL, .cntnm_fac = cntnm_fac, .sclcpl = sclcpl, .sclhw = sclhw, .y0res = y0res,
+                    .ibrd = ibrd, .ixsect = ixsect, .XAMNT = XAMNT};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const JacReq jq{.njac = njac, .jac_mol = jac_mol};
+    const JacOut out{.O = O, .RAD = RAD, .TB = TB, .K_T = K_T, .K_TZ = K_TZ, .K_W = K_W, .K_CLW = K_CLW, .K_O = K_O, .K_SFC = K_SFC};
+    if (int rc = need_real8(c, kJacEntry[JAC_PLAIN])) return rc;
+    if (jac_full_null(JAC_PLAIN, atm, sfc, ScanIn(), out)) { c->err = "null array argument"; return MONORTM_EARG; }
+    DeviceGuard guard;
+    if (int rc = jac_check_args(c, atm, quantity)) return rc;
+    if (int rc = jac_check_mol(c, atm, jq, K_W)) return rc;
+    const size_t d = 8, l = (size_t)nlay_max * d, v = (size_t)nwn * d, w = l * nwn;
+    HostCall hc(8);
+    hc.flag = true;
+    const HostIn in = declare_inputs(hc, c, atm, sfc, ScanIn(), nullptr);
+    const int o_O = hc.out(O, w), o_rad = hc.out(RAD, v), o_tb = hc.out(TB, v), o_kt = hc.out(K_T, w), o_ktz = hc.out(K_TZ, (l + d) * nwn),
+              o_kw = hc.out(njac ? K_W : nullptr, w * njac), o_kc = hc.out(K_CLW, w), o_ko = hc.out(K_O, w), o_ks = hc.out(K_SFC, 3 * v);
+    // every share's states are checked on its own device's context, before anything of it is staged
+    auto pre = [&](Ctx *s, int p0, int n) -> int {
+        if (nmol < 1) { s->err = "bad nmol"; return MONORTM_EARG; }
+        AtmIn share = atm;
+        share.nprof = n; share.nlay = nlay + p0; share.T = hc.host(in.T, p0);
+        return jac_check_states(s, share);
+    };
+    return hc.run(c, nprof, pre, [&](Ctx *s, int, int n, char *const *dv) {
+        const Share sh(in, dv, n, atm, sfc, ScanIn());
+        const JacOut od{.O = dv[o_O], .RAD = dv[o_rad], .TB = dv[o_tb], .K_T = dv[o_kt], .K_TZ = dv[o_ktz], .K_W = dv[o_kw], .K_CLW = dv[o_kc],
+                        .K_O = dv[o_ko], .K_SFC = dv[o_ks]};
+        return jac_full(s, JAC_PLAIN, sh.atm, sh.sfc, jq, sh.scan, 0, od, s->hs);
+    });
+}
+
+int monortm_hip_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                         const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                         double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                         const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, void *O, void *RAD, void *TB,
+                         void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_SFC) {
+    return monortm_hip_jacobian_xs(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, 0,
+                                   nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, O, RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O, K_SFC);
+}
+
+// ---- Jacobians of path scans (DESIGN.md section 3.8) ----------------------------------------------------------------------
+int monortm_hip_rtm_scan_jac_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                                 int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc,
+                                 int sfc_per_path, const void *emiss, const void *reflc, void *RAD, void *TB, void *K_O, void *K_PATH,
+                                 void *K_T, void *K_TZ, void *K_SFC, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    const JacOut out{.RAD = RAD, .TB = TB, .K_T = K_T, .K_TZ = K_TZ, .K_O = K_O, .K_PATH = K_PATH, .K_SFC = K_SFC};
+    return rtm_scan_jac_dev_impl(c, atm, sfc, scan, O, out, (hipStream_t)stream);
+}
+
+int monortm_hip_scan_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                                     const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL,
+                                     const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd, int ixsect,
+                                     const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc, const void *emiss,
+                                     const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
+                                     int sfc_per_path, void *O, void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O,
+                                     void *K_PATH, void *K_SFC, const double *wn_ends, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .dvset = dvset, .nlay = nlay, .nlay_max = nlay_max, .nmol = nmol, .P = P, .T = T,
+                    .CLW = CLW, .WKL = WKL, .WBRODL = WBRODL, .cntnm_fac = cntnm_fac, .sclcpl = sclcpl, .sclhw = sclhw, .y0res = y0res,
+                    .ibrd = ibrd, .ixsect = ixsect, .XAMNT = XAMNT, .wn_ends = wn_ends};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const JacReq jq{.njac = njac, .jac_mol = jac_mol};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    const JacOut out{.O = O, .RAD = RAD, .TB = TB, .K_T = K_T, .K_TZ = K_TZ, .K_W = K_W, .K_CLW = K_CLW, .K_O = K_O, .K_PATH = K_PATH,
+                     .K_SFC = K_SFC};
+    return jac_full(c, JAC_SCAN, atm, sfc, jq, scan, 0, out, (hipStream_t)stream);
+}
+
+int monortm_hip_scan_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                                  const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL,
+                                  const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd, const int *irt,
+                                  const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
+                                  const int *jac_mol, int npath, const void *path, int sfc_per_path, void *O, void *RAD, void *TB, void *K_T,
+                                  void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_PATH, void *K_SFC, const double *wn_ends,
+                                  void *stream) {
+    return monortm_hip_scan_jacobian_xs_dev(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
+                                            ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, O,
+                                            RAD, TB, K_T, K_TZ, K_W, K_CLW, K_O, K_PATH, K_SFC, wn_ends, stream);
+}
+
+int monortm_hip_rtm_scan_jac(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
+                             int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc,
+                             int sfc_per_path, const void *emiss, const void *reflc, void *RAD, void *TB, void *K_O, void *K_PATH, void *K_T,
+                             void *K_TZ, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    DeviceGuard guard;
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    if (any_null({wn, nlay, irt, T, TZ, O, path, tmpsfc, emiss, reflc, RAD, TB, K_T, K_TZ, K_SFC})) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    if (int rc = check_quantity(c, quantity)) return rc;
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
+    // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
+    if (int rc = scan_check_path(c, atm, scan)) return rc;
+    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vo = (size_t)nwn * npath * d, wo = l * nwn * npath;
+    HostCall hc(8);
+    const HostIn in = declare_inputs(hc, c, atm, sfc, scan, O);
+    const int o_rad = hc.out(RAD, vo), o_tb = hc.out(TB, vo), o_ko = hc.out(K_O, wo), o_kp = hc.out(K_PATH, wo), o_kt = hc.out(K_T, wo),
+              o_ktz = hc.out(K_TZ, (l + d) * nwn * npath), o_ks = hc.out(K_SFC, 3 * vo);
+    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
+        const Share sh(in, dv, n, atm, sfc, scan);
+        const JacOut out{.RAD = dv[o_rad], .TB = dv[o_tb], .K_T = dv[o_kt], .K_TZ = dv[o_ktz], .K_O = dv[o_ko], .K_PATH = dv[o_kp],
+                         .K_SFC = dv[o_ks]};
+        return rtm_scan_jac_dev_impl(s, sh.atm, sh.sfc, sh.scan, sh.O, out, s->hs);
+    });
+}
+
+int monortm_hip_scan_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                                 const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                                 double sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const void *XAMNT, const int *irt,
+                                 const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
+                                 const int *jac_mol, int npath, const void *path, int sfc_per_path, void *O, void *RAD, void *TB, void *K_T,
+                                 void *K_TZ, void *K_W, void *K_CLW, void *K_O, void *K_PATH, void *K_SFC) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .dvset = dvset, .nlay = nlay, .nlay_max = nlay_max, .nmol = nmol, .P = P, .T = T,
+                    .CLW = CLW, .WKL = WKL, .WBRODL = WBRODL, .cntnm_fac = cntnm_fac, .sclcpl = sclcpl, .sclhw = sclhw, .y0res = y0res,
+                    .ibrd = ibrd, .ixsect = ixsect, .XAMNT = XAMNT};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const JacReq jq{.njac = njac, .jac_mol = jac_mol};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    const JacOut out{.O = O, .RAD = RAD, .TB = TB, .K_T = K_T, .K_TZ = K_TZ, .K_W = K_W, .K_CLW = K_CLW, .K_O = K_O, .K_PATH = K_PATH,
+                     .K_SFC = K_SFC};
+    if (int rc = need_real8(c, kJacEntry[JAC_SCAN])) return rc;
+    if (jac_full_null(JAC_SCAN, atm, sfc, scan, out)) { c->err = "null array argument"; return MONORTM_EARG; }
+    DeviceGuard guard;
+    // the whole call is checked before the first device is touched: a refusal launches nothing anywhere
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
+    if (int rc = jac_check_args(c, atm, quantity)) return rc;
+    if (int rc = jac_check_mol(c, atm, jq, K_W)) return rc;
+    if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
+    if (int rc = scan_check_path(c, atm, scan)) return rc;
+    if (int rc = jac_check_states(c, atm)) return rc;
+    const size_t d = 8, l = (size_t)nlay_max * d, w = l * nwn, vo = (size_t)nwn * npath * d, wo = w * npath;
+    HostCall hc(8);
+    hc.flag = true;
+    const HostIn in = declare_inputs(hc, c, atm, sfc, scan, nullptr);
+    const int o_O = hc.out(O, w), o_rad = hc.out(RAD, vo), o_tb = hc.out(TB, vo), o_kt = hc.out(K_T, wo), o_ktz = hc.out(K_TZ, (l + d) * nwn * npath),
+              o_kw = hc.out(njac ? K_W : nullptr, wo * njac), o_kc = hc.out(K_CLW, wo), o_ko = hc.out(K_O, wo), o_kp = hc.out(K_PATH, wo),
+              o_ks = hc.out(K_SFC, 3 * vo);
+    return hc.run(c, nprof, [&](Ctx *s, int, int n, char *const *dv) {
+        const Share sh(in, dv, n, atm, sfc, scan);
+        const JacOut od{.O = dv[o_O], .RAD = dv[o_rad], .TB = dv[o_tb], .K_T = dv[o_kt], .K_TZ = dv[o_ktz], .K_W = dv[o_kw], .K_CLW = dv[o_kc],
+                        .K_O = dv[o_ko], .K_PATH = dv[o_kp], .K_SFC = dv[o_ks]};
+        return jac_full(s, JAC_SCAN, sh.atm, sh.sfc, jq, sh.scan, 0, od, s->hs);
+    });
+}
+
+int monortm_hip_scan_jacobian(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
+                              const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                              double sclcpl, double sclhw, double y0res, int ibrd, const int *irt, const void *TZ, const void *tmpsfc,
+                              const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
+                              int sfc_per_path, void *O, void *RAD, void *TB, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_O,
+                              void *K_PATH, void *K_SFC) {
+    return monortm_hip_scan_jacobian_xs(ctx, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
+                                        ibrd, 0, nullptr, irt, TZ, tmpsfc, emiss, reflc, quantity, njac, jac_mol, npath, path, sfc_per_path, O, RAD,
+                                        TB, K_T, K_TZ, K_W, K_CLW, K_O, K_PATH, K_SFC);
+}
+
+// ---- channel- and beam-averaged Jacobians of path scans (DESIGN.md section 3.9) ---------------------------------------------
 int monortm_hip_rtm_obs_jac_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
                                 int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc,
                                 int sfc_per_path, const void *emiss, const void *reflc, int obs, void *Y, void *K_T, void *K_TZ, void *K_SFC,
                                 void *stream) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    return rtm_obs_jac_dev_impl(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, obs,
-                                Y, K_T, K_TZ, K_SFC, c->real_kind, stream);
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    const JacOut out{.Y = Y, .K_T = K_T, .K_TZ = K_TZ, .K_SFC = K_SFC};
+    return rtm_obs_jac_dev_impl(c, atm, sfc, scan, O, obs, out, c->real_kind, (hipStream_t)stream);
 }
 
-// MODM of the base and the 2 (1 + njac) perturbed states ONCE (jac_states), then one launch of the contracting adjoint
 int monortm_hip_obs_jacobian_xs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                                 const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                                 double sclcpl, double sclhw, double y0res, int ibrd,
-                                 int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
-                                 const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
-                                 int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_SFC,
-                                 const double *wn_ends, void *stream) {
+                                    const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                                    double sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const void *XAMNT, const int *irt,
+                                    const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
+                                    const int *jac_mol, int npath, const void *path, int sfc_per_path, int obs, void *O, void *Y, void *K_T,
+                                    void *K_TZ, void *K_W, void *K_CLW, void *K_SFC, const double *wn_ends, void *stream) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    hipStream_t s = (hipStream_t)stream;
-    const bool any_null = !wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path ||
-                          !O || !Y || !K_T || !K_TZ || !K_CLW || !K_SFC;
-    if (int rc = jac_full_check(c, "monortm_hip_obs_jacobian", any_null, nprof, nwn, nlay_max, nmol, quantity, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    Ctx::Obs *ob = nullptr;
-    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
-    if (int rcd = check_device(c)) return rcd;
-    double *xO = nullptr;
-    size_t st = 0;
-    if (int rc = jac_states(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, XAMNT, njac,
-                            jac_mol, O, wn_ends, s, &xO, &st))
-        return rc;
-    RtmObsJacArgs a{};
-    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity;
-    a.sfc_per_path = sfc_per_path;
-    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.Y = Y; a.K_T = K_T; a.K_TZ = K_TZ; a.K_SFC = K_SFC;
-    jac_chain_args(a, c, njac, K_W, K_CLW, xO, st);
-    a.errflag = c->errflag;
-    obs_args(a, *ob);
-    launch_rtm_obs_jac(a, true, 8, s);
-    HIPCHK(c, hipGetLastError());
-    return MONORTM_OK;
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .dvset = dvset, .nlay = nlay, .nlay_max = nlay_max, .nmol = nmol, .P = P, .T = T,
+                    .CLW = CLW, .WKL = WKL, .WBRODL = WBRODL, .cntnm_fac = cntnm_fac, .sclcpl = sclcpl, .sclhw = sclhw, .y0res = y0res,
+                    .ibrd = ibrd, .ixsect = ixsect, .XAMNT = XAMNT, .wn_ends = wn_ends};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const JacReq jq{.njac = njac, .jac_mol = jac_mol};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    const JacOut out{.O = O, .Y = Y, .K_T = K_T, .K_TZ = K_TZ, .K_W = K_W, .K_CLW = K_CLW, .K_SFC = K_SFC};
+    return jac_full(c, JAC_OBS, atm, sfc, jq, scan, obs, out, (hipStream_t)stream);
 }
 
 int monortm_hip_obs_jacobian_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
@@ -2360,73 +2564,70 @@ int monortm_hip_rtm_obs_jac(void *ctx, int nprof, int npath, int nwn, const doub
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
     DeviceGuard guard;
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !Y || !K_T || !K_TZ || !K_SFC) {
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    if (any_null({wn, nlay, irt, T, TZ, O, path, tmpsfc, emiss, reflc, Y, K_T, K_TZ, K_SFC})) {
         c->err = "null array argument";
         return MONORTM_EARG;
     }
     if (int rc = check_quantity(c, quantity)) return rc;
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
     Ctx::Obs *ob = nullptr;
     if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
     // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
-    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vs = (size_t)nwn * (sfc_per_path ? npath : 1) * d;
+    if (int rc = scan_check_path(c, atm, scan)) return rc;
     const size_t y = (size_t)ob->nview * ob->nchan;   // measurements of a profile
     HostCall hc(8);
-    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
-              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, l * nwn), i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs),
-              i_rf = hc.in(reflc, vs);
+    const HostIn in = declare_inputs(hc, c, atm, sfc, scan, O);
     // the kernel accumulates into double outputs (out_kind 8) whatever the context's REAL kind: rounded once, when they are unpacked
     const int o_y = hc.out_widened(Y, y), o_kt = hc.out_widened(K_T, y * nlay_max), o_ktz = hc.out_widened(K_TZ, y * (nlay_max + 1)),
               o_ks = hc.out_widened(K_SFC, 3 * y);
     return hc.run(c, nprof, [&](Ctx *s, int g, int n, char *const *dv) {   // (every shard holds the operator under a handle of its own)
-        return rtm_obs_jac_dev_impl(s, n, npath, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], quantity, dv[i_T], dv[i_TZ],
-                                    dv[i_O], dv[i_f], dv[i_ts], sfc_per_path, dv[i_em], dv[i_rf], g < 0 ? obs : ob->shard[g], dv[o_y], dv[o_kt],
-                                    dv[o_ktz], dv[o_ks], 8, s->hs);
+        const Share sh(in, dv, n, atm, sfc, scan);
+        const JacOut out{.Y = dv[o_y], .K_T = dv[o_kt], .K_TZ = dv[o_ktz], .K_SFC = dv[o_ks]};
+        return rtm_obs_jac_dev_impl(s, sh.atm, sh.sfc, sh.scan, sh.O, g < 0 ? obs : ob->shard[g], out, 8, s->hs);
     });
 }
 
 int monortm_hip_obs_jacobian_xs(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol,
-                             const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
-                             double sclcpl, double sclhw, double y0res, int ibrd,
-                             int ixsect, const void *XAMNT, const int *irt, const void *TZ, const void *tmpsfc,
-                             const void *emiss, const void *reflc, int quantity, int njac, const int *jac_mol, int npath, const void *path,
-                             int sfc_per_path, int obs, void *O, void *Y, void *K_T, void *K_TZ, void *K_W, void *K_CLW, void *K_SFC) {
+                                const void *P, const void *T, const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac,
+                                double sclcpl, double sclhw, double y0res, int ibrd, int ixsect, const void *XAMNT, const int *irt,
+                                const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int njac,
+                                const int *jac_mol, int npath, const void *path, int sfc_per_path, int obs, void *O, void *Y, void *K_T,
+                                void *K_TZ, void *K_W, void *K_CLW, void *K_SFC) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    if (int rc = need_real8(c, "monortm_hip_obs_jacobian")) return rc;
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !Y ||
-        !K_T || !K_TZ || !K_CLW || !K_SFC) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .dvset = dvset, .nlay = nlay, .nlay_max = nlay_max, .nmol = nmol, .P = P, .T = T,
+                    .CLW = CLW, .WKL = WKL, .WBRODL = WBRODL, .cntnm_fac = cntnm_fac, .sclcpl = sclcpl, .sclhw = sclhw, .y0res = y0res,
+                    .ibrd = ibrd, .ixsect = ixsect, .XAMNT = XAMNT};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const JacReq jq{.njac = njac, .jac_mol = jac_mol};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    const JacOut out{.O = O, .Y = Y, .K_T = K_T, .K_TZ = K_TZ, .K_W = K_W, .K_CLW = K_CLW, .K_SFC = K_SFC};
+    if (int rc = need_real8(c, kJacEntry[JAC_OBS])) return rc;
+    if (jac_full_null(JAC_OBS, atm, sfc, scan, out)) { c->err = "null array argument"; return MONORTM_EARG; }
     DeviceGuard guard;
     // the whole call is checked before the first device is touched: a refusal launches nothing anywhere
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    if (int rc = jac_check_args(c, nprof, nwn, nlay, nlay_max, quantity)) return rc;
-    if (int rc = jac_check_mol(c, nmol, njac, jac_mol, K_W, ixsect, XAMNT)) return rc;
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
+    if (int rc = jac_check_args(c, atm, quantity)) return rc;
+    if (int rc = jac_check_mol(c, atm, jq, K_W)) return rc;
     if (nmol < 1) { c->err = "bad nmol"; return MONORTM_EARG; }
     Ctx::Obs *ob = nullptr;
     if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
-    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
-    if (int rc = jac_check_states(c, nprof, nwn, wn, nlay, nlay_max, T)) return rc;
-    const size_t d = 8, l = (size_t)nlay_max * d, vs = (size_t)nwn * (sfc_per_path ? npath : 1) * d;
+    if (int rc = scan_check_path(c, atm, scan)) return rc;
+    if (int rc = jac_check_states(c, atm)) return rc;
+    const size_t d = 8, l = (size_t)nlay_max * d;
     const size_t y = (size_t)ob->nview * ob->nchan * d, yk = y * nlay_max;   // bytes of a profile's measurements, of their layer derivatives
     HostCall hc(8);
     hc.flag = true;
-    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
-              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l),
-              i_XA = hc.in(ixsect == 1 ? XAMNT : nullptr, l * ctx_nxs(c)), i_TZ = hc.in(TZ, l + d),
-              i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs), i_rf = hc.in(reflc, vs);
+    const HostIn in = declare_inputs(hc, c, atm, sfc, scan, nullptr);
     const int o_O = hc.out(O, l * nwn), o_y = hc.out(Y, y), o_kt = hc.out(K_T, yk), o_ktz = hc.out(K_TZ, yk + y),
               o_kw = hc.out(njac ? K_W : nullptr, yk * njac), o_kc = hc.out(K_CLW, yk), o_ks = hc.out(K_SFC, 3 * y);
     return hc.run(c, nprof, [&](Ctx *s, int g, int n, char *const *dv) {   // (every shard holds the operator under a handle of its own)
-        const double ends[2] = {wn[0], wn[nwn - 1]};
-        return monortm_hip_obs_jacobian_xs_dev(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C],
-                                            dv[i_W], dv[i_B], cntnm_fac, sclcpl, sclhw, y0res, ibrd, ixsect, dv[i_XA],
-                                        (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em],
-                                            dv[i_rf], quantity, njac, jac_mol, npath, dv[i_f], sfc_per_path, g < 0 ? obs : ob->shard[g], dv[o_O],
-                                            dv[o_y], dv[o_kt], dv[o_ktz], dv[o_kw], dv[o_kc], dv[o_ks], ends, s->hs);
+        const Share sh(in, dv, n, atm, sfc, scan);
+        const JacOut od{.O = dv[o_O], .Y = dv[o_y], .K_T = dv[o_kt], .K_TZ = dv[o_ktz], .K_W = dv[o_kw], .K_CLW = dv[o_kc], .K_SFC = dv[o_ks]};
+        return jac_full(s, JAC_OBS, sh.atm, sh.sfc, jq, sh.scan, g < 0 ? obs : ob->shard[g], od, s->hs);
     });
 }
 
@@ -2440,100 +2641,16 @@ int monortm_hip_obs_jacobian(void *ctx, int nprof, int nwn, const double *wn, do
                                        K_T, K_TZ, K_W, K_CLW, K_SFC);
 }
 
-// ---- the forward measurement operator: channel- and beam-averaged scans (DESIGN.md section 3.10) ------------------------------
-}  // extern "C"
-
-namespace {
-int obs_check_quantity(Ctx *c, int quantity) {
-    if (quantity < 0 || quantity > 2) { c->err = "quantity must be 0 (RAD), 1 (TB) or 2 (band TB)"; return MONORTM_EARG; }
-    return MONORTM_OK;
-}
-// the channels' nominal wavenumbers of a host call (quantity 2 only): all of them, before anything is staged
-int obs_check_vcen(Ctx *c, int quantity, const double *vcen, int nchan) {
-    if (quantity != 2) return MONORTM_OK;
-    if (!vcen) { c->err = "quantity 2 (band TB) needs vcen [nchan]"; return MONORTM_EARG; }
-    for (int i = 0; i < nchan; i++)
-        if (!(vcen[i] > 0. && std::isfinite(vcen[i]))) { c->err = "vcen[" + std::to_string(i) + "] is not a finite wavenumber > 0"; return MONORTM_EARG; }
-    return MONORTM_OK;
-}
-
-// monortm_hip_rtm_obs_dev with the element size of Y as an argument: the host entry of a real_kind = 4 context has the kernel accumulate
-// (and convert to the band temperature) in double and rounds once, when it unpacks
-int rtm_obs_dev_impl(Ctx *c, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
-                     const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path, const void *emiss,
-                     const void *reflc, int obs, const double *vcen, void *Y, int out_kind, void *stream) {
-    if (!c->shards.empty()) return multi_only_host(c);
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !Y) { c->err = "null array argument"; return MONORTM_EARG; }
-    if (int rcq = obs_check_quantity(c, quantity)) return rcq;
-    if (quantity == 2 && !vcen) { c->err = "quantity 2 (band TB) needs vcen [nchan]"; return MONORTM_EARG; }
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    if (nprof > 65535) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
-    Ctx::Obs *ob = nullptr;
-    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
-    if (int rcd = check_device(c)) return rcd;
-    RtmObsArgs a{};
-    a.nprof = nprof; a.npath = npath; a.nwn = nwn; a.nlay_max = nlay_max; a.quantity = quantity; a.real_kind = c->real_kind;
-    a.sfc_per_path = sfc_per_path;
-    a.wn = wn; a.T = T; a.TZ = TZ; a.O = O; a.path = path; a.tmpsfc = tmpsfc; a.emiss = emiss; a.reflc = reflc; a.nlay = nlay; a.irt = irt;
-    a.nview = ob->nview; a.nchan = ob->nchan;
-    a.view_start = ob->view_start; a.wpath = ob->wpath; a.mstart = ob->mstart; a.mlane = ob->mlane; a.mw = ob->mw;
-    a.vcen = quantity == 2 ? vcen : nullptr;
-    a.Y = Y;
-    a.errflag = c->errflag;
-    launch_rtm_obs(a, out_kind, (hipStream_t)stream);
-    HIPCHK(c, hipGetLastError());
-    return MONORTM_OK;
-}
-
-// monortm_hip_obs_dev likewise: ONE MODM pass into the caller's O (the MODM outputs the operator does not use go to the context's
-// workspace, grown on demand and kept), then ONE launch of the forward kernel
-int obs_dev_impl(Ctx *c, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P, const void *T,
-                 const void *CLW, const void *WKL, const void *WBRODL, const double *cntnm_fac, double sclcpl, double sclhw, double y0res, int ibrd,
-                 const int *irt, const void *TZ, const void *tmpsfc, const void *emiss, const void *reflc, int quantity, int npath,
-                 const void *path, int sfc_per_path, int obs, const double *vcen, void *O, void *Y, int out_kind, const double *wn_ends,
-                 void *stream) {
-    if (!c->shards.empty()) return multi_only_host(c);
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !Y) {
-        c->err = "null array argument";
-        return MONORTM_EARG;
-    }
-    if (int rcq = obs_check_quantity(c, quantity)) return rcq;
-    if (quantity == 2 && !vcen) { c->err = "quantity 2 (band TB) needs vcen [nchan]"; return MONORTM_EARG; }
-    if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
-    if (nprof < 1 || nprof > 65535 || nwn < 1 || nlay_max < 1) { c->err = "bad nprof/nwn/nlay_max"; return MONORTM_EARG; }
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
-    Ctx::Obs *ob = nullptr;
-    if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
-    if (int rcd = check_device(c)) return rcd;
-    const size_t st = (size_t)nprof * nlay_max * nwn * (size_t)c->real_kind;   // bytes of one [nprof][nlay_max][nwn] array
-    Arena ws;
-    const size_t w_OM = ws.add(st * nmol), w_OC = ws.add(st * MONORTM_NCONT), w_OL = ws.add(st);
-    if (ws.size > c->jac_ws_bytes) {   // (the Jacobian entries' workspace: whichever call needs more grows it)
-        if (c->jac_ws) HIPCHK(c, hipFree(c->jac_ws));
-        c->jac_ws = nullptr;
-        c->jac_ws_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->jac_ws, ws.size));
-        c->jac_ws_bytes = ws.size;
-    }
-    char *wb = static_cast<char *>(c->jac_ws);
-    if (int rc = monortm_hip_modm_xs_dev(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res,
-                                         ibrd, 0, nullptr, nullptr, O, wb + w_OM, wb + w_OC, wb + w_OL, wn_ends, stream))
-        return rc;
-    return rtm_obs_dev_impl(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, obs, vcen,
-                            Y, out_kind, stream);
-}
-
-}  // namespace
-
-extern "C" {
-
+// ---- the forward measurement operator -----------------------------------------------------------------------
 int monortm_hip_rtm_obs_dev(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt,
                             int quantity, const void *T, const void *TZ, const void *O, const void *path, const void *tmpsfc, int sfc_per_path,
                             const void *emiss, const void *reflc, int obs, const double *vcen, void *Y, void *stream) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    return rtm_obs_dev_impl(c, nprof, npath, nwn, wn, nlay, nlay_max, irt, quantity, T, TZ, O, path, tmpsfc, sfc_per_path, emiss, reflc, obs, vcen,
-                            Y, c->real_kind, stream);
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    return rtm_obs_dev_impl(c, atm, sfc, scan, O, obs, vcen, Y, c->real_kind, (hipStream_t)stream);
 }
 
 int monortm_hip_obs_dev(void *ctx, int nprof, int nwn, const double *wn, double dvset, const int *nlay, int nlay_max, int nmol, const void *P,
@@ -2543,8 +2660,12 @@ int monortm_hip_obs_dev(void *ctx, int nprof, int nwn, const double *wn, double 
                         void *Y, const double *wn_ends, void *stream) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    return obs_dev_impl(c, nprof, nwn, wn, dvset, nlay, nlay_max, nmol, P, T, CLW, WKL, WBRODL, cntnm_fac, sclcpl, sclhw, y0res, ibrd, irt, TZ,
-                        tmpsfc, emiss, reflc, quantity, npath, path, sfc_per_path, obs, vcen, O, Y, c->real_kind, wn_ends, stream);
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .dvset = dvset, .nlay = nlay, .nlay_max = nlay_max, .nmol = nmol, .P = P, .T = T,
+                    .CLW = CLW, .WKL = WKL, .WBRODL = WBRODL, .cntnm_fac = cntnm_fac, .sclcpl = sclcpl, .sclhw = sclhw, .y0res = y0res,
+                    .ibrd = ibrd, .wn_ends = wn_ends};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    return obs_dev_impl(c, atm, sfc, scan, obs, vcen, O, Y, c->real_kind, (hipStream_t)stream);
 }
 
 int monortm_hip_rtm_obs(void *ctx, int nprof, int npath, int nwn, const double *wn, const int *nlay, int nlay_max, const int *irt, int quantity,
@@ -2553,25 +2674,25 @@ int monortm_hip_rtm_obs(void *ctx, int nprof, int npath, int nwn, const double *
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
     DeviceGuard guard;
-    if (!wn || !nlay || !irt || !T || !TZ || !O || !path || !tmpsfc || !emiss || !reflc || !Y) { c->err = "null array argument"; return MONORTM_EARG; }
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .nlay = nlay, .nlay_max = nlay_max, .T = T};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    if (any_null({wn, nlay, irt, T, TZ, O, path, tmpsfc, emiss, reflc, Y})) { c->err = "null array argument"; return MONORTM_EARG; }
     if (int rc = obs_check_quantity(c, quantity)) return rc;
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
     Ctx::Obs *ob = nullptr;
     if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
     if (int rc = obs_check_vcen(c, quantity, vcen, ob->nchan)) return rc;
     // the whole call's nlay and factors before the first device is touched: a refusal launches nothing anywhere
-    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vs = (size_t)nwn * (sfc_per_path ? npath : 1) * d;
+    if (int rc = scan_check_path(c, atm, scan)) return rc;
     HostCall hc(4);   // (the scan slots: lastO, which points into the MODM slots, stays valid)
-    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_T = hc.in(T, l),
-              i_TZ = hc.in(TZ, l + d), i_O = hc.in(O, l * nwn), i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs),
-              i_rf = hc.in(reflc, vs), i_vc = hc.in_shared(quantity == 2 ? vcen : nullptr, ob->nchan * sizeof(double));
+    const HostIn in = declare_inputs(hc, c, atm, sfc, scan, O);
+    const int i_vc = hc.in_shared(quantity == 2 ? vcen : nullptr, ob->nchan * sizeof(double));
     // the kernel accumulates into a double Y (out_kind 8) whatever the context's REAL kind: rounded once, when it is unpacked
     const int o_y = hc.out_widened(Y, (size_t)ob->nview * ob->nchan);
     return hc.run(c, nprof, [&](Ctx *s, int g, int n, char *const *dv) {   // (every shard holds the operator under a handle of its own)
-        return rtm_obs_dev_impl(s, n, npath, nwn, (double *)dv[i_wn], (int *)dv[i_nl], nlay_max, (int *)dv[i_irt], quantity, dv[i_T], dv[i_TZ],
-                                dv[i_O], dv[i_f], dv[i_ts], sfc_per_path, dv[i_em], dv[i_rf], g < 0 ? obs : ob->shard[g], (double *)dv[i_vc],
-                                dv[o_y], 8, s->hs);
+        const Share sh(in, dv, n, atm, sfc, scan);
+        return rtm_obs_dev_impl(s, sh.atm, sh.sfc, sh.scan, sh.O, g < 0 ? obs : ob->shard[g], (double *)dv[i_vc], dv[o_y], 8, s->hs);
     });
 }
 
@@ -2581,34 +2702,33 @@ int monortm_hip_obs(void *ctx, int nprof, int nwn, const double *wn, double dvse
                     int quantity, int npath, const void *path, int sfc_per_path, int obs, const double *vcen, void *O, void *Y) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return null_ctx();
-    if (!wn || !nlay || !P || !T || !CLW || !WKL || !WBRODL || !cntnm_fac || !irt || !TZ || !tmpsfc || !emiss || !reflc || !path || !O || !Y) {
+    const AtmIn atm{.nprof = nprof, .nwn = nwn, .wn = wn, .dvset = dvset, .nlay = nlay, .nlay_max = nlay_max, .nmol = nmol, .P = P, .T = T,
+                    .CLW = CLW, .WKL = WKL, .WBRODL = WBRODL, .cntnm_fac = cntnm_fac, .sclcpl = sclcpl, .sclhw = sclhw, .y0res = y0res,
+                    .ibrd = ibrd};
+    const SfcIn sfc{.irt = irt, .TZ = TZ, .tmpsfc = tmpsfc, .emiss = emiss, .reflc = reflc, .quantity = quantity};
+    const ScanIn scan{.npath = npath, .path = path, .sfc_per_path = sfc_per_path};
+    if (any_null({wn, nlay, P, T, CLW, WKL, WBRODL, cntnm_fac, irt, TZ, tmpsfc, emiss, reflc, path, O, Y})) {
         c->err = "null array argument";
         return MONORTM_EARG;
     }
     DeviceGuard guard;
     // the whole call is checked before the first device is touched: a refusal launches nothing anywhere
     if (int rc = obs_check_quantity(c, quantity)) return rc;
-    if (int rc = scan_check_args(c, nprof, npath, nwn, nlay_max, sfc_per_path)) return rc;
+    if (int rc = scan_check_args(c, atm, scan)) return rc;
     if (nmol < 7 || nmol > MXMOL) { c->err = "nmol must be 7..39 (LINES reads WK(1:7), modm.f90:313)"; return MONORTM_EARG; }
     Ctx::Obs *ob = nullptr;
     if (int rc = obs_for_call(c, obs, npath, nwn, &ob)) return rc;
     if (int rc = obs_check_vcen(c, quantity, vcen, ob->nchan)) return rc;
-    if (int rc = scan_check_path(c, nprof, npath, nlay, nlay_max, path)) return rc;
-    for (int i = 1; i < nwn; i++)
-        if (!(wn[i] >= wn[i - 1])) { c->err = "wavenumbers must be ascending (the reference takes v1 = wn(1), v2 = wn(nwn), modm.f90:180-181)"; return MONORTM_EARG; }
-    const size_t d = (size_t)c->real_kind, l = (size_t)nlay_max * d, vs = (size_t)nwn * (sfc_per_path ? npath : 1) * d;
+    if (int rc = scan_check_path(c, atm, scan)) return rc;
+    if (int rc = check_ascending(c, atm)) return rc;
     HostCall hc(8);   // (the Jacobian slots: a call between a MODM and an RTM call leaves lastO alone)
     hc.flag = true;
-    const int i_wn = hc.in_shared(wn, nwn * sizeof(double)), i_nl = hc.in(nlay, sizeof(int)), i_irt = hc.in(irt, sizeof(int)), i_P = hc.in(P, l),
-              i_T = hc.in(T, l), i_C = hc.in(CLW, l), i_W = hc.in(WKL, l * nmol), i_B = hc.in(WBRODL, l), i_TZ = hc.in(TZ, l + d),
-              i_f = hc.in(path, l * npath), i_ts = hc.in(tmpsfc, d), i_em = hc.in(emiss, vs), i_rf = hc.in(reflc, vs),
-              i_vc = hc.in_shared(quantity == 2 ? vcen : nullptr, ob->nchan * sizeof(double));
-    const int o_O = hc.out(O, l * nwn), o_y = hc.out_widened(Y, (size_t)ob->nview * ob->nchan);
+    const HostIn in = declare_inputs(hc, c, atm, sfc, scan, nullptr);
+    const int i_vc = hc.in_shared(quantity == 2 ? vcen : nullptr, ob->nchan * sizeof(double));
+    const int o_O = hc.out(O, (size_t)nlay_max * c->real_kind * nwn), o_y = hc.out_widened(Y, (size_t)ob->nview * ob->nchan);
     return hc.run(c, nprof, [&](Ctx *s, int g, int n, char *const *dv) {   // (every shard holds the operator under a handle of its own)
-        const double ends[2] = {wn[0], wn[nwn - 1]};
-        return obs_dev_impl(s, n, nwn, (double *)dv[i_wn], dvset, (int *)dv[i_nl], nlay_max, nmol, dv[i_P], dv[i_T], dv[i_C], dv[i_W], dv[i_B],
-                            cntnm_fac, sclcpl, sclhw, y0res, ibrd, (int *)dv[i_irt], dv[i_TZ], dv[i_ts], dv[i_em], dv[i_rf], quantity, npath,
-                            dv[i_f], sfc_per_path, g < 0 ? obs : ob->shard[g], (double *)dv[i_vc], dv[o_O], dv[o_y], 8, ends, s->hs);
+        const Share sh(in, dv, n, atm, sfc, scan);
+        return obs_dev_impl(s, sh.atm, sh.sfc, sh.scan, g < 0 ? obs : ob->shard[g], (double *)dv[i_vc], dv[o_O], dv[o_y], 8, s->hs);
     });
 }
 

@@ -70,10 +70,7 @@ def inputs(r, prs):
     rng = np.random.default_rng(21)
 
     def pack(get, width=None):   # zero padding up to LM, whatever the batch's own deepest profile
-        out = np.zeros((n, LM) if width is None else (n, LM, width), dt)
-        for i, p in enumerate(prs):
-            out[i, : p.nlay] = get(p)
-        return out
+        return api.pack_layers(prs, LM, get, width, dt)
 
     a = dict(nlay=nlay, irt=irt, ts=ts, em=em, rf=rf, T=pack(lambda p: p.t), P=pack(lambda p: p.p), CLW=pack(lambda p: p.clw),
              WB=pack(lambda p: p.wbrodl), WKL=pack(lambda p: p.wkl, NMOL))
@@ -193,9 +190,27 @@ def obs_jacobian(c, pr, wn, v):
                                             c.o("k_w", (NVIEW, LM, 1, NCHAN)), c.o("k_clw", YK), c.o("k_sfc", (NVIEW, 3, NCHAN)))
 
 
+def vcen(c, wn, v):
+    """The channels' nominal wavenumbers of quantity 2 (shared by the profiles), null otherwise."""
+    if v["q"] != 2:
+        return None
+    c.keep.append(np.ascontiguousarray(np.linspace(wn[0], wn[-1], NCHAN)))
+    return _p(c.keep[-1])
+
+
+def rtm_obs(c, pr, wn, v):
+    return c.r.lib.monortm_hip_rtm_obs(c.r.ctx, c.n, NPATH, NWN, _p(wn), c.i("nlay"), LM, c.i("irt"), v["q"], c.i("T"), c.i("TZ"), c.i("O"),
+                                       c.i("path"), c.i("ts"), v["sfc"], *sfc(c, v), v["obs"], vcen(c, wn, v), c.o("y", Y))
+
+
+def obs(c, pr, wn, v):
+    return c.r.lib.monortm_hip_obs(c.r.ctx, c.n, NWN, *modm_in(c, pr, wn), *sfc(c, v), v["q"], NPATH, c.i("path"), v["sfc"], v["obs"],
+                                   vcen(c, wn, v), c.o("o", W), c.o("y", Y))
+
+
 def case(entry, rk=8, drop=(), **v):
     v = dict(dict(sfc=0, iout=1, njac=1), **v)
-    name = "-".join([entry.__name__, f"r{rk}"] + [f"{k}{x}" for k, x in v.items() if k in ("sfc", "iout", "njac")] + ["no_" + k for k in drop])
+    name = "-".join([entry.__name__, f"r{rk}"] + [f"{k}{x}" for k, x in v.items() if k in ("sfc", "iout", "njac", "q")] + ["no_" + k for k in drop])
     return pytest.param(entry, rk, tuple(drop), v, id=name)
 
 
@@ -210,6 +225,8 @@ CASES = [
     case(scan_jacobian), case(scan_jacobian, sfc=1, njac=0, drop=NO_W),
     case(rtm_obs_jac), case(rtm_obs_jac, sfc=1), case(rtm_obs_jac, rk=4),
     case(obs_jacobian), case(obs_jacobian, sfc=1, njac=0, drop=("k_w",)),
+    case(rtm_obs, q=1), case(rtm_obs, sfc=1, q=2), case(rtm_obs, rk=4, q=0), case(rtm_obs, rk=4, sfc=1, q=1),
+    case(obs, q=1), case(obs, sfc=1, q=2), case(obs, rk=4, q=1),
 ]
 
 
