@@ -19,8 +19,11 @@
 // the shared reciprocals (1e-15 of a term; 1e-12 of a cell's optical depth); tests/test_ms_kernel.py holds the two kernels
 // together and both to the oracle.  A profile's last bits depend on the profiles that share its waves.
 // Memory besides the outputs: 10 KB of LDS and 21 KB of scratch in global memory per wave (records of rare shapes, radiation terms,
-// the sums of the run in progress - L2-resident), two bytes per table line (ms_reach_kernel), 96 bytes per possible chunk of CL lines
-// (the launch-wide chunk plan that the same launch writes: ms_plan_wave).
+// the parked sums of a run that spans chunks, the sum over the molecules), two bytes per table line (ms_reach_kernel), 96 bytes per
+// possible chunk of CL lines (the launch-wide chunk plan that the same launch writes: ms_plan_wave).  The scratch of the resident waves
+// is larger than the L2 (4096 waves x 21 KB), its hot part - the three [WPS][64] blocks, 7.5 KB a wave - about fills it.  A walk that
+// continues a run loads its five sums and, if the run goes on, stores five; a walk that ends a run stores nothing, and the completion
+// loads five radiation terms and five sums over the molecules in ONE round trip and stores ten values (O_BY_MOL, the sum).
 #define MONORTM_EXP_SGPR_CONSTANTS 1   // (exp_prep of lines_device.hpp: see there)
 #include "lines_device.hpp"
 #include "lines_ms_asm.hpp"
@@ -154,15 +157,16 @@ __device__ __attribute__((noinline)) void ms_voigt_scan(unsigned long long cand,
 }
 
 // the lines [j0, j1) of a molecule run in the chunk: sub-runs of ordinary lines through the assembly loops, lines with Y factors
-// one by one (general_term: every per-lane condition explicit), Voigt candidates corrected afterwards
+// one by one (general_term: every per-lane condition explicit), Voigt candidates corrected afterwards.  The sums of the run are
+// handed back in S (a run that began in an earlier chunk reloads them from sS first); the caller finishes or parks them
 // NT: the 25 cm-1 test can fail for some (state, channel); M2: negative resonance within reach of some; V / Y: rare shapes
 template <int KIND>
 __device__ __forceinline__ void ms_eval_run(const MsState &st, const MsSpec &sp, const HotA *sA, const HotB *gB, const ColdLine *gC, const MsArgs &ms,
                                             unsigned long long NT, unsigned long long M2, unsigned long long V, unsigned long long Y,
-                                            const unsigned long long (&RS)[WPS], const unsigned long long (&QS)[WPS], int j0, int j1, const double *sWn, int ce, unsigned kvalid, int mol, double *sS, bool fresh, int *errflag, unsigned short *vq) {
+                                            const unsigned long long (&RS)[WPS], const unsigned long long (&QS)[WPS], int j0, int j1, const double *sWn, int ce, unsigned kvalid, int mol, const double *sS, bool fresh, double (&S)[WPS], int *errflag, unsigned short *vq) {
     // the lane's wavenumbers and the sums of the run, read here and not held across the chunk loop (ten LDS reads per run against
     // twenty registers that would be live across the prepare stage)
-    double W[WPS], S[WPS];
+    double W[WPS];
     {
         int c = ce, ln = (int)__lane_id();
         asm volatile("" : "+v"(c), "+v"(ln));
@@ -229,12 +233,6 @@ __device__ __forceinline__ void ms_eval_run(const MsState &st, const MsSpec &sp,
 #pragma unroll
         for (int k = 0; k < WPS; k++) S[k] = St[k];
     }
-    {
-        int ln = (int)__lane_id();
-        asm volatile("" : "+v"(ln));
-#pragma unroll
-        for (int k = 0; k < WPS; k++) sS[k * 64 + ln] = S[k];
-    }
 }
 
 // per workgroup: HotB[G CL] (16-byte aligned), ColdLine[G CL], then three blocks of [WPS][64] doubles - radiation terms, the sums of the run
@@ -259,14 +257,15 @@ struct MsLds {
     unsigned char *sFlag;  // [nsteps * 64] class flags per item (state * CL + line): bits 0-3 NT, M2, V, Y
     int *sRole;            // [64] the lane in the evaluate stage: se | ce << 8 | kvalid << 16 | profile exists << 24 | state active << 25 |
                            // prepare pass of the state << 26 | its place in that pass (sub) << 28
-    double *sS;            // [WPS][64] the sums of the molecule run in progress (a lane's own slots; global memory): in registers only inside a run's walk
+    double *sS;            // [WPS][64] the sums of a molecule run that goes on in the next chunk (a lane's own slots; global memory): a run that ends in the chunk of its walk never touches them
 };
 __device__ __forceinline__ MsLds ms_lds(double *dyn, int G, int sa_stride, int nmol, int nslot, double *gS = nullptr) {
     MsLds l;
     l.sA = reinterpret_cast<HotA *>(dyn);
     l.sWn = reinterpret_cast<double *>(l.sA + G * sa_stride);
-    // (the sums of the run in progress are parked in the workgroup's scratch, a lane's own slots: ten global accesses per walk of a
-    // run, served by the L2 - in LDS they took the 2.5 KB that a chunk of 32 lines instead of 21 needs: configs[3] 1.055 -> 1.02 ms)
+    // (the sums of a run that spans chunks are parked in the workgroup's scratch, a lane's own slots: five loads where such a run
+    // resumes, five stores where it is parked again - in LDS they took the 2.5 KB that a chunk of 32 lines instead of 21 needs:
+    // configs[3] 1.055 -> 1.02 ms)
     l.sS = gS;
     l.sLay = l.sWn + 64;
     l.sW = l.sLay + G * 20;
@@ -920,7 +919,7 @@ __global__ __launch_bounds__(64, 4) void lines_ms_kernel(ModmArgs a, DevLines L,
     if (total_m < 0) return;
     const int total = total_m & (MS_MATCH_BIT - 1);
     const bool match = (total_m & MS_MATCH_BIT) != 0;   // the wave takes its windows and its plain chunks' words from the chunk plan
-#ifdef MONORTM_EXPERIMENT
+#if defined(MONORTM_EXPERIMENT) && !defined(MONORTM_NO_PLAN_STATS)   // (the counters' atomics contend on one line: a timing run of an experiment build leaves them out)
     unsigned long long *plan_cnt = ms.plan + MS_PLAN_CNT;   // (waves, waves that match, chunks, chunks on the fast path)
     if (ms.plan_on && threadIdx.x == 0) { atomicAdd(plan_cnt, 1ull); if (match) atomicAdd(plan_cnt + 1, 1ull); }
 #endif
@@ -965,7 +964,7 @@ __global__ __launch_bounds__(64, 4) void lines_ms_kernel(ModmArgs a, DevLines L,
 #ifdef MONORTM_EXPERIMENT
         if (mc.ablate == 2 || mc.ablate == 6) continue;
 #endif
-#ifdef MONORTM_EXPERIMENT
+#if defined(MONORTM_EXPERIMENT) && !defined(MONORTM_NO_PLAN_STATS)
         if (mc.plan_on && threadIdx.x == 0) { atomicAdd(mc.plan + MS_PLAN_CNT + 2, 1ull); if (fast) atomicAdd(mc.plan + MS_PLAN_CNT + 3, 1ull); }
 #endif
         MsSpec sp;
@@ -999,35 +998,83 @@ __global__ __launch_bounds__(64, 4) void lines_ms_kernel(ModmArgs a, DevLines L,
             if (o0 >= base + CL) break;
             const int j0 = max(o0, base) - base, j1 = min(o1, base + CL) - base;
             const int mol = m + 1;
+            const bool done = o1 <= base + CL;   // the run ends in this chunk (wave-uniform)
+            double S[WPS];                       // its sums as the walk leaves them (ms_eval_run)
             {
                 const MsLane ln = ms_lane(mc, pg, ld.sRole);
                 const MsState st{ld.sA + ln.se * mc.sa_stride, gB + ln.se * CL, gC + ln.se * CL, ln.item0};
 #ifdef MONORTM_EXPERIMENT
                 if ((mc.ablate == 3 && (mol == 7 || mol == 2)) || (mc.ablate == 5 && mol != 7 && mol != 2)) continue;
 #endif
-                if (mol == 7) ms_eval_run<1>(st, sp, ld.sA, gB, gC, mc, NT, M2, V, Y, RS, QS, j0, j1, ld.sWn, ln.ce, ln.kvalid, mol, ld.sS, o0 >= base, ac.errflag, sVq);
-                else if (mol == 2) ms_eval_run<2>(st, sp, ld.sA, gB, gC, mc, NT, M2, V, Y, RS, QS, j0, j1, ld.sWn, ln.ce, ln.kvalid, mol, ld.sS, o0 >= base, ac.errflag, sVq);
-                else ms_eval_run<0>(st, sp, ld.sA, gB, gC, mc, NT, M2, V, Y, RS, QS, j0, j1, ld.sWn, ln.ce, ln.kvalid, mol, ld.sS, o0 >= base, ac.errflag, sVq);
+                if (mol == 7) ms_eval_run<1>(st, sp, ld.sA, gB, gC, mc, NT, M2, V, Y, RS, QS, j0, j1, ld.sWn, ln.ce, ln.kvalid, mol, ld.sS, o0 >= base, S, ac.errflag, sVq);
+                else if (mol == 2) ms_eval_run<2>(st, sp, ld.sA, gB, gC, mc, NT, M2, V, Y, RS, QS, j0, j1, ld.sWn, ln.ce, ln.kvalid, mol, ld.sS, o0 >= base, S, ac.errflag, sVq);
+                else ms_eval_run<0>(st, sp, ld.sA, gB, gC, mc, NT, M2, V, Y, RS, QS, j0, j1, ld.sWn, ln.ce, ln.kvalid, mol, ld.sS, o0 >= base, S, ac.errflag, sVq);
             }
-            if (o1 <= base + CL) {   // run complete: O_BY_MOL = RFT * (W * SF)   (modm.f90:436-438)
+            if (done) {   // run complete: O_BY_MOL = RFT * (W * SF)   (modm.f90:436-438)
+                // One memory round trip.  What the block needs of the arguments and of the lane's role is read first; then the five
+                // radiation terms (formed once, in the prologue) and - from the second completion on - the five sums over the molecules
+                // (as stored, in molecule order, modm.f90:264-269; a lane's own slots of the workgroup's scratch, stored to OSUM once at
+                // the end of the wave) are loaded back to back: every lane owns its [WPS][64] slots, so the loads need no predicate.
+                // The arithmetic is selects, not divergent regions; only the stores are predicated (a lane without channel k writes
+                // nothing).  The sums of the run come from the walk in registers.
                 const MsLane ln = ms_lane(mc, pg, ld.sRole);
+                const bool has_os = ac.osum != nullptr;
+                const int nlay_max = ac.nlay_max;
+                double *const obm0 = static_cast<double *>(ac.O_BY_MOL);
                 const double wm = ld.sW[ln.se * nmol + m];
-                const size_t pl_e = (size_t)ln.prof * ac.nlay_max + lay;
-                double *obm = static_cast<double *>(ac.O_BY_MOL) + (pl_e * nmol + m) * (size_t)nwn;
-                // sum over the molecules as stored, in molecule order (modm.f90:264-269), accumulated in the workgroup's scratch (a lane's
-                // own slots, L2-resident) and stored once at the end of the wave
-                double *os = const_cast<double *>(gR) + 2 * WPS * 64;
+                const double *pr = gR + ln.lane;
+                double *po = const_cast<double *>(gR) + 2 * WPS * 64 + ln.lane;
+#ifdef MONORTM_EXPERIMENT
+                const bool bare = mc.ablate == 7;   // the ceiling of this block: no load, no sum over the molecules (wrong results)
+#else
+                constexpr bool bare = false;
+#endif
+                const bool add = has_os && !osum_first && !bare;
+                double rft[WPS], ov[WPS];
+#pragma unroll
+                for (int k = 0; k < WPS; k++) { rft[k] = 1.; ov[k] = 0.; }
+                if (!bare) {
+#pragma unroll
+                    for (int k = 0; k < WPS; k++) rft[k] = pr[k * 64];
+                }
+                if (add) {
+#pragma unroll
+                    for (int k = 0; k < WPS; k++) ov[k] = po[k * 64];
+                }
+                double *ob = obm0 + (((size_t)ln.prof * nlay_max + lay) * nmol + m) * (size_t)nwn + ln.ce;
+                // (a state without a column of this molecule: the reference does not walk the lines at all, modm.f90:318-321)
+                const bool nocol = wm == 0.;
+                double od[WPS], on[WPS];
+                {
+#pragma clang fp contract(off)   // (two products and a sum, as ever: no FMA)
+#pragma unroll
+                    for (int k = 0; k < WPS; k++) {
+                        const double p = rft[k] * (wm * S[k]);
+                        od[k] = nocol ? 0. : p;
+                        const double t = ov[k] + od[k];
+                        on[k] = add ? t : od[k];
+                    }
+                }
+                // (all ten values exist before the first store: sunk into the predicated regions, the waits for the later loads would stand
+                // behind the earlier stores - the counter is one, in order - and wait for those too)
+#pragma unroll
+                for (int k = 0; k < WPS; k++) asm volatile("" : "+v"(od[k]), "+v"(on[k]));
 #pragma unroll
                 for (int k = 0; k < WPS; k++)
                     if (ln.act && ((ln.kvalid >> k) & 1u)) {
-                        const int iw = ln.ce + LPS * k;
-                        const double rft = gR[k * 64 + ln.lane];   // radiation term of (state, channel): formed once, in the prologue
-                        // (a state without a column of this molecule: the reference does not walk the lines at all, modm.f90:318-321)
-                        const double od = (wm == 0.) ? 0. : rft * (wm * ld.sS[k * 64 + ln.lane]);
-                        obm[iw] = od;
-                        if (ac.osum) os[k * 64 + ln.lane] = osum_first ? od : os[k * 64 + ln.lane] + od;
+                        ob[LPS * k] = od[k];
+                        if (has_os && !bare) po[k * 64] = on[k];
                     }
+                // (the two arms must not share a tail: merged, the last store of this one would wait for the other's pending loads -
+                // vmcnt(0) behind nine stores)
+                asm volatile("; run finished");
                 osum_first = false;
+            } else {   // the run goes on in the next chunk: park its sums (the only store to sS; ms_eval_run reloads them there)
+                int ln = (int)__lane_id();
+                asm volatile("" : "+v"(ln));
+#pragma unroll
+                for (int k = 0; k < WPS; k++) ld.sS[k * 64 + ln] = S[k];
+                asm volatile("; run parked");
             }
         }
         ms_sync();

@@ -2,6 +2,9 @@
 # One A/B variant of the HIP library for lines_ms_kernel: lines_ms_kernel.hip and api.hip recompiled with extra flags (experiment
 # switches allowed), the other objects from the shipped build (monortm_amd/lib/obj/).
 #   tools/build_variant_ms.sh NAME [-DFLAG ...]   -> build_dbg/libmonortm_hip_NAME.so   (git-ignored, travels with gpurun)
+# For TIMING an experiment build add -DMONORTM_NO_PLAN_STATS: the chunk-plan counters (MONORTM_MS_PLAN_STATS) are two atomicAdd on one
+# line per chunk and take the kernel from 0.85 to 4.2 ms on configs[3].  MONORTM_MS_ABLATE values: device_common.hpp (MsArgs::ablate);
+# 7 = the completion of a molecule run without its loads and without the sum over the molecules (lines_ms_kernel.hip).
 set -e
 NAME=$1; shift
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
