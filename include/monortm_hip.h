@@ -121,8 +121,9 @@ int monortm_hip_kat(void *ctx, int which, int n, const double *args, const doubl
  * (a Jacobian call makes several): 2 finish_mw_kernel (last wavenumber < 820 cm-1 and an ABSRB grid of <= 1000 points), 3
  * finish_kernel<HIGH> (last wavenumber > 1340 cm-1), 4 finish_kernel<PAR> (fewer than 16 x compute units (profile, layer) workgroups),
  * 5 finish_kernel<Q4> (four layers per wave: ABSRB grid <= 64 points, <= 128 wavenumbers), 6 finish_kernel with 64 threads (ABSRB
- * grid <= 256 points, <= 128 wavenumbers), 7 finish_kernel with 256 threads.  which = 16 .. 19 -> launches of far_kernel (the far field
- * of dense grids, one launch per level of intervals and MODM evaluation) with 1, 2, 4, 8 waves per workgroup; 8 .. 15 are unknown.
+ * grid <= 256 points, <= 128 wavenumbers), 7 finish_kernel with 256 threads.  which = 9 -> those launches of variant 2 that took the
+ * column layout (finish_mw_kernel_col, option "finish_mw").  which = 16 .. 19 -> launches of far_kernel (the far field
+ * of dense grids, one launch per level of intervals and MODM evaluation) with 1, 2, 4, 8 waves per workgroup; 8 and 10 .. 15 are unknown.
  * Counted on the host next to the launch; tests use them to know which variant served a call.  A multi-device context returns the
  * sum over its devices.  -1 for an unknown selector / NULL. */
 long long monortm_hip_counter(void *ctx, int which);
@@ -691,6 +692,9 @@ int monortm_hip_profile(void *ctx, int enable);
  *   "finish" = "auto" | "generic": generic = finish_kernel forms the continuum, cloud and total optical depths also where
  *       finish_mw_kernel would (last wavenumber < 820 cm-1): the A/B switch between the two; MONORTM_FINISH_GENERIC (set to anything)
  *       makes generic the default at monortm_hip_init.
+ *   "finish_mw" = "auto" | "layer" | "column" (MONORTM_FINISH_MW): the layout of finish_mw_kernel - a workgroup per (profile, layer), or
+ *       per (profile, block of 64 layers) wherever that layout can run (not with line slices summed in the finish kernel, not beyond
+ *       40 KB of LDS); auto chooses by batch size.  The outputs are bitwise the same.
  * Values are parsed strictly (whole string, in range).  Unknown names / values: MONORTM_EARG. */
 int monortm_hip_set_option(void *ctx, const char *name, const char *value);
 int monortm_hip_kernel_time(void *ctx, int kernel, double *total_ms, long long *launches);

@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libmonortm_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FC = os.environ.get("MONORTM_FC", "/opt/rocm/bin/amdflang")
 HIP_SOURCES = ["api.hip", "lines_kernel.hip", "lines_ms_kernel.hip", "far_kernel.hip", "continuum_kernel.hip", "xsec_kernel.hip", "xsec_jac_kernel.hip", "rtm_kernel.hip", "rtm_scan_kernel.hip", "jacobian_kernel.hip", "rtm_scan_jac_kernel.hip", "rtm_obs_jac_kernel.hip", "rtm_obs_kernel.hip", "oe_kernel.hip", "line_table.cpp"]
-HIP_DEPS = HIP_SOURCES + ["device_common.hpp", "lineshape.hpp", "cloud_tkc.hpp", "obs_exchange.hpp", "rtm_tile.hpp", "modm_plan.hpp", "ms_reach.hpp", "lines_device.hpp", "xsec_walk.hpp", "lines_asm.hpp", "lines_ms_asm.hpp", "line_table.hpp", "tables/monortm_tables.h",
+HIP_DEPS = HIP_SOURCES + ["device_common.hpp", "lineshape.hpp", "cloud_tkc.hpp", "obs_exchange.hpp", "rtm_tile.hpp", "modm_plan.hpp", "finish_mw_layout.hpp", "ms_reach.hpp", "lines_device.hpp", "xsec_walk.hpp", "lines_asm.hpp", "lines_ms_asm.hpp", "line_table.hpp", "tables/monortm_tables.h",
                            "../../include/monortm_hip.h"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value", "-Wno-pass-failed",
              "-Wno-unused-const-variable"]

@@ -663,7 +663,8 @@ class MonoRTM:
     def counter(self, which: int = 0) -> int:
         """monortm_hip_counter: 0 = rtm calls, 1 = rtm_scan calls that found O resident on the device; 2 .. 7 = launches of the
         continuum / cloud / total kernel by variant (FINISH_VARIANTS: finish_mw_kernel, finish_kernel<HIGH>, <PAR>, <Q4>, plain with
-        64 threads, plain with 256), one per MODM evaluation; 16 .. 19 = launches of far_kernel with 1, 2, 4, 8 waves per workgroup
+        64 threads, plain with 256), one per MODM evaluation; 9 = those of variant 0 that took the column layout
+        (finish_mw_kernel_col); 16 .. 19 = launches of far_kernel with 1, 2, 4, 8 waves per workgroup
         (FAR_WAVES), one per level of intervals and MODM evaluation."""
         return int(self.lib.monortm_hip_counter(self.ctx, which))
 
@@ -1013,7 +1014,7 @@ class MonoRTM:
 
     def set_option(self, name: str, value) -> None:
         """Measurement switches of the context (monortm_hip_set_option): nslice, fair, tile_waves, far_levels, lines_kernel = auto | wn |
-        ms, ms_items, ms_prepare = auto | fused | passes, ms_plan = auto | on | off, jac_dt, jac_dlnw, and finish = auto | generic (generic: finish_kernel also below 820 cm-1, where finish_mw_kernel
+        ms, ms_items, ms_prepare = auto | fused | passes, ms_plan = auto | on | off, finish_mw = auto | layer | column, jac_dt, jac_dlnw, and finish = auto | generic (generic: finish_kernel also below 820 cm-1, where finish_mw_kernel
         serves by default; the environment variable MONORTM_FINISH_GENERIC makes it the default of a new context)."""
         self._chk(self.lib.monortm_hip_set_option(self.ctx, name.encode(), str(value).encode()))
 

@@ -16,6 +16,7 @@
 #include "device_common.hpp"
 #include "line_table.hpp"
 #include "modm_plan.hpp"
+#include "finish_mw_layout.hpp"
 #include "lineshape.hpp"
 #include "tables/monortm_tables.h"
 
@@ -41,6 +42,7 @@ struct Ctx {
         int ms_ablate = 0;        // timing experiments: lines_ms_kernel without its later stages (wrong results)
         int ms_prepare = MS_PREPARE_FUSED;   // lines_ms_kernel's prepare stage: the fused trip where it applies / the pass loop always
         int ms_plan = 1;          // lines_ms_kernel: the launch-wide chunk plan for the waves that match it / every wave on its own
+        int finish_mw = monortm_dev::FINISH_MW_AUTO;   // layout of the microwave finish kernel (finish_mw_layout.hpp)
         double jac_dt = MONORTM_JAC_DT, jac_dlnw = MONORTM_JAC_DLNW;   // half-steps of the Jacobian's central differences
     } opt;
     void *comm = nullptr;     // RCCL communicator of a multi-process job (monortm_hip_comm_init), one rank per context
@@ -130,6 +132,8 @@ struct Ctx {
     // launches of the continuum / cloud / total kernel by variant (monortm_hip_counter 2 .. 7): finish_mw_kernel, finish_kernel<HIGH>,
     // <PAR>, <Q4>, plain with 64 threads, plain with 256
     long long finish_launches[6] = {0, 0, 0, 0, 0, 0};
+    // ... of which finish_mw_kernel_col, the column layout of variant 0 (monortm_hip_counter 9)
+    long long finish_mw_col_launches = 0;
     // launches of far_kernel by waves per workgroup (monortm_hip_counter 16 .. 19): 1, 2, 4, 8 - one per level and MODM evaluation
     long long far_launches[4] = {0, 0, 0, 0};
     // MONORTM_HOST_TIMING=1: wall time of the host-buffer calls by phase (pack, enqueue, wait, unpack), printed at finalize
@@ -194,6 +198,7 @@ int set_option(Ctx *c, const char *name, const char *value) {
     const std::string n = name ? name : "", v = value ? value : "";
     const bool autov = v.empty() || v == "auto";
     long iv = 0;
+    int iopt = 0;
     double dv = 0.;
     bool isint = false, isdbl = false;
     if (!autov) {
@@ -222,6 +227,9 @@ int set_option(Ctx *c, const char *name, const char *value) {
 #endif
     // continuum / cloud / total kernel: auto = finish_mw_kernel below 820 cm-1, finish_kernel elsewhere; generic = finish_kernel always
     else if (n == "finish" && (autov || v == "generic")) c->opt.finish_generic = autov ? 0 : 1;
+    // finish_mw_kernel's layout: auto = by batch size (finish_mw_col_waves); layer = a workgroup per (profile, layer) always; column = a
+    // workgroup per (profile, block of 64 layers) wherever that layout can run (A/B measurements, tests of the two: identical bits)
+    else if (n == "finish_mw" && monortm_dev::finish_mw_parse(v.c_str(), &iopt)) c->opt.finish_mw = iopt;
     else if (n == "ms_items" && (autov || (isint && (iv == 64 || iv == 128 || iv == 192 || iv == 256)))) c->opt.ms_items = autov ? 0 : (int)iv;
     // half-steps of the Jacobian: a finite positive double (jac_dlnw below 1: WKL (1 - eps) stays positive)
     else if ((n == "jac_dt" || n == "jac_dlnw") && (autov || (isdbl && std::isfinite(dv) && dv > 0. && (n == "jac_dt" || dv < 1.)))) {
@@ -1159,7 +1167,7 @@ int monortm_hip_init(const char *tape3_path, double v1, double v2, int icp, int 
     }
     if (const char *e = getenv("MONORTM_HOST_TIMING")) c->host_timing = e[0] == '1';
     if (getenv("MONORTM_FINISH_GENERIC")) c->opt.finish_generic = 1;  // (set, whatever its value: the default of option "finish")
-    for (const char *k : {"lines_kernel", "nslice", "fair", "tile_waves", "far_levels", "ms_items", "ms_prepare", "ms_plan",
+    for (const char *k : {"lines_kernel", "nslice", "fair", "tile_waves", "far_levels", "ms_items", "ms_prepare", "ms_plan", "finish_mw",
 #ifdef MONORTM_EXPERIMENT
                           "ms_ablate",
 #endif
@@ -1448,6 +1456,7 @@ long long monortm_hip_counter(void *ctx, int which) {
     if (which == 0) return c->o_reused;
     if (which == 1) return c->o_reused_scan;
     if (which >= 2 && which <= 7) return c->finish_launches[which - 2];
+    if (which == 9) return c->finish_mw_col_launches;
     if (which >= 16 && which <= 19) return c->far_launches[which - 16];
     return -1;
 }
@@ -1671,14 +1680,16 @@ int modm_dev_impl(Ctx *c, const AtmIn &atm, bool odx_given, const ModmOut &out, 
     if (ixsect == 1 && !odx_given) launch_xsec(a, c->xs, s);   // MONORTM_XSEC_SUB comes first (modm.f90:197); the finish kernel adds its sum into O
     a.slices_reduced = pl.slices_reduced;
     if (pl.slices_reduced) launch_reduce_slices(a, s);
+    bool column = false;   // finish_mw_kernel_col served the call (launch_finish_mw chooses the layout)
     if (pl.mw) {
-        const hipError_t e = launch_finish_mw(a, c->tables, vends[0], vends[1], pl.V1ABS, pl.V2ABS, pl.NPTABS, c->mw_cache, s);
+        const hipError_t e = launch_finish_mw(a, c->tables, vends[0], vends[1], pl.V1ABS, pl.V2ABS, pl.NPTABS, c->mw_cache, c->opt.finish_mw, c->cus, &column, s);
         if (e != hipSuccess) {
             c->err = std::string("launch_finish_mw: ") + (c->mw_cache.why ? c->mw_cache.why : hipGetErrorString(e));
             return c->mw_cache.why ? MONORTM_EUNSUPPORTED : MONORTM_EHIP;
         }
     } else HIPCHK(c, launch_finish(a, c->tables, pl.V1ABS, pl.V2ABS, pl.NPTABS, pl.csize, pl.high, pl.par, pl.fin_threads, pl.fin_lds, pl.lds_sets, s));
     c->finish_launches[pl.finish_variant]++;
+    if (column) c->finish_mw_col_launches++;
     prof_end(c, s, ev);
     HIPCHK(c, hipGetLastError());
     return MONORTM_OK;

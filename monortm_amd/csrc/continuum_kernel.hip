@@ -5,6 +5,7 @@
 #include <cstring>
 #include "cloud_tkc.hpp"
 #include "tables/monortm_tables.h"
+#include "finish_mw_layout.hpp"
 
 namespace {
 using namespace monortm_dev;
@@ -592,6 +593,155 @@ __global__ void mw_items_kernel(DevTables tb, MwSetup q, double V1ABS, int NPTAB
     }
 }
 
+// ---- the per-value expressions of the microwave finish, shared by its two layouts (finish_mw_kernel: lane = item / channel for one
+// layer; finish_mw_kernel_col: lane = layer in the set-up and stage A).  A value has ONE expression, written once: the layouts differ
+// in which index the lanes hold, not in the arithmetic, and their outputs are bitwise the same (tests/test_finish_mw_column.py).
+struct MwLayer {  // the scalars of one layer that stages A, C and D read
+    double TAVE, rTAVE, WK1, x_vmr_h2o, x_vmr_o2, x_vmr_n2;
+    double Rself, TFAC, Rfrgn, WCO2, tau_fac, tfac;
+};
+// (round 4: the layer scalars through reciprocals - v_rcp_f64 + two Newton steps, within an ulp of the IEEE quotients that
+// finish_kernel forms - and the exponentials through exp_cw: 1250 -> ~1050 instructions per wave)
+__device__ __forceinline__ MwLayer mw_layer(double PAVE, double TAVE, double WTOT, double WK1, double WK2, double WK7, double xself,
+                                            double xfrgn, double xco2c, double xn2cn) {
+    const double P0c = 1013., T0c = 296., XLOSMT = 2.68675E+19;
+    MwLayer L;
+    const double rTAVE = rcp2(TAVE), rWTOT = rcp2(WTOT), pr = PAVE * (1. / P0c);
+    const double RHOAVE = pr * (T0c * rTAVE);
+    const double amagat = pr * (273. * rTAVE);
+    const double x_vmr_h2o = WK1 * rWTOT, x_vmr_o2 = WK7 * rWTOT, x_vmr_n2 = 1. - x_vmr_h2o - x_vmr_o2;
+    const double wn2 = x_vmr_n2 * WTOT;
+    const double h2o_fac = x_vmr_h2o;
+    L.TAVE = TAVE, L.rTAVE = rTAVE, L.WK1 = WK1, L.x_vmr_h2o = x_vmr_h2o, L.x_vmr_o2 = x_vmr_o2, L.x_vmr_n2 = x_vmr_n2;
+    L.Rself = h2o_fac * RHOAVE * 1.e-20 * xself;            // contnm.f90:325-371
+    L.TFAC = (TAVE - T0c) * (1. / (260. - T0c));
+    L.Rfrgn = (1. - h2o_fac) * RHOAVE * 1.e-20 * xfrgn;     // contnm.f90:380-474
+    L.WCO2 = WK2 * RHOAVE * 1.0E-20 * xco2c;                // contnm.f90:484-528 + FRNCO2 :2958
+    L.tau_fac = xn2cn * (wn2 / XLOSMT) * amagat;            // contnm.f90:906-943
+    L.tfac = (TAVE - 296.) * (1. / (220. - 296.));
+    return L;
+}
+// the four stage-A formulas: the coarse coefficient of a live item of the branch; pw1 / pw2 are the temperature interpolations
+// powpos(x, y) = exp(y log x) with the tabulated log x: self (260 K / 296 K: exp_cw(TFAC tc)), N2 (220 K / 296 K: exp_cw(tfac tc))
+// and its scale factor (exp_cw(tfac tf))
+__device__ __forceinline__ double mw_a_self(const MwLayer &L, double ta, double pw1, bool intab) {
+    double v = 0.;
+    if (intab) {
+        double SH2O = 0.;
+        if (ta > 0.) SH2O = ta * pw1;
+        v = L.WK1 * (SH2O * L.Rself);
+    }
+    return v;
+}
+__device__ __forceinline__ double mw_a_frgn(const MwLayer &L, double ta, double tc, bool intab) {
+    double FH2O = intab ? ta : 0.;
+    const double FSCAL = tc;  // xfac_rhu below 600 cm-1, the closed form above (mw_items_kernel)
+    FH2O = FH2O * FSCAL;
+    return (L.WK1 * FH2O) * L.Rfrgn;
+}
+__device__ __forceinline__ double mw_a_co2(const MwLayer &L, double ta, bool intab) {
+    return intab ? ta * L.WCO2 : 0.;  // (band-head temperature factor and chi factor are 1 below 2000 cm-1)
+}
+__device__ __forceinline__ double mw_a_n2(const MwLayer &L, double ta, double te, double pw1, double pw2, bool intab) {
+    double c0 = 0., c1 = 0.;
+    if (intab) {
+        c0 = ta * pw1;
+        const double sf_T = te * pw2;
+        c1 = (sf_T - 1.) * (0.79) / (0.21);
+    }
+    return L.tau_fac * c0 * (L.x_vmr_n2 + c1 * L.x_vmr_o2 + 1. * L.x_vmr_h2o);
+}
+// the stage-B point: XINT of four neighbouring coarse values onto one ABSRB point
+__device__ __forceinline__ double mw_b_point(double a0, double a1, double a2, double a3, const MwItemB &r) {
+    return (-a0 * r.B1 + a1 * r.c1 + a2 * r.c2 - a3 * r.B2) * 1.0;
+}
+// everything of stage C that depends on the channel alone
+struct MwChan {
+    double wnv, B1, w1, w2, B2;  // wavenumber; the 4-point weights of XINT on the 1 cm-1 grid (the same for the three passes)
+    int J;
+    bool inside;
+};
+__device__ __forceinline__ MwChan mw_chan(const ModmArgs &a, double V1, double V1ABS, double V2ABS, int iw) {
+    const double DVABS = 1.0;
+    const int nwn = a.nwn;
+    MwChan c;
+    const double wnv = a.wn[iw];
+    double vint;
+    if (a.dvset != 0.) {
+        const int I = iw + 1;
+        int ilo = (int)((V1ABS + DVABS - V1) / a.dvset + 1. + K_ONEMI);
+        if (ilo < 1) ilo = 1;
+        int ihi = (int)((V2ABS - DVABS - V1) / a.dvset + K_ONEMI);
+        if (ihi > nwn) ihi = nwn;
+        c.inside = I >= ilo && I <= ihi;
+        vint = V1 + a.dvset * (double)(I - 1);
+    } else {
+        int ilo = (int)((V1ABS + DVABS - wnv) / 1.0 + 1. + K_ONEMI);
+        if (ilo < 1) ilo = 1;
+        int ihi = (int)((V2ABS - DVABS - wnv) / 1.0 + K_ONEMI);
+        if (ihi > 1) ihi = 1;
+        c.inside = ilo <= 1 && ihi >= 1;
+        vint = wnv;
+    }
+    const double RECDVA = 1. / DVABS;
+    const int J = (int)((vint - V1ABS) * RECDVA + K_ONEPL);
+    const double VJ = V1ABS + DVABS * (double)(J - 1);
+    const double P = RECDVA * (vint - VJ);
+    const double tP = (3. - 2. * P) * P;  // C = tP P
+    const double B = 0.5 * P * (1. - P);
+    const double B1 = B * (1. - P), B2 = B * P;
+    // 1 - C + B2 and C + B1 with the products C and B P fused into the additions, written out: these are the contractions
+    // finish_mw_kernel has always had (its resource census of round 4 on), and a sum of two products left to the compiler is fused
+    // into one or the other by what surrounds it - the two layouts came out one ulp apart in C + B1
+    c.wnv = wnv, c.J = J, c.B1 = B1, c.w1 = fma(B, P, fma(-tP, P, 1.)), c.w2 = fma(tP, P, B1), c.B2 = B2;
+    return c;
+}
+// RADFN (src/lblrtm_sub.f90:36-97) with XKT > 0
+__device__ __forceinline__ double mw_radfn(double wnv, double rTAVE) {
+    double rad = wnv;
+    const double x = (wnv * K_RADCN2) * rTAVE;
+    if (x <= 0.01) rad = 0.5 * x * wnv;
+    else if (x <= 10.0) {
+        const double e = exp_cw(-x);
+        rad = wnv * (1. - e) * rcp2(1. + e);
+    }
+    return rad;
+}
+// the XINT sums of the three passes: xint_point on the sum of self and foreign needs ABSRB = (0 + self) + foreign per point, as
+// CONTNM accumulates it
+__device__ __forceinline__ void mw_xint3(const double *sAbs, int NA, const MwChan &c, double val[3]) {
+    val[0] = val[1] = val[2] = 0.;
+    if (c.inside) {
+        const int J = c.J;
+        const double *A0 = sAbs, *A1 = sAbs + NA, *A2 = sAbs + 2 * NA, *A3 = sAbs + 3 * NA;
+        const double h0 = A0[J - 1] + A1[J - 1], h1 = A0[J] + A1[J], h2 = A0[J + 1] + A1[J + 1], h3 = A0[J + 2] + A1[J + 2];
+        val[0] = -h0 * c.B1 + h1 * c.w1 + h2 * c.w2 - h3 * c.B2;
+        val[1] = -A2[J - 1] * c.B1 + A2[J] * c.w1 + A2[J + 1] * c.w2 - A2[J + 2] * c.B2;
+        val[2] = -A3[J - 1] * c.B1 + A3[J] * c.w1 + A3[J + 1] * c.w2 - A3[J + 2] * c.B2;
+    }
+}
+// the continuum slots of one (layer, channel) as stored, and their sum in slot order (rounded to R first)
+template <typename R>
+__device__ __forceinline__ double mw_store_oc(R *OC, size_t nwn, int iw, const double val[3], double rad, bool on01, bool on2, bool on3) {
+    const R s0 = on01 ? (R)(val[0] * rad) : (R)0;
+    const R s1 = on2 ? (R)(val[1] * rad) : (R)0;
+    const R s4 = on3 ? (R)(val[2] * rad) : (R)0;
+    OC[iw] = s0;
+    OC[nwn + iw] = s1;
+    OC[2 * nwn + iw] = (R)0;
+    OC[3 * nwn + iw] = (R)0;
+    OC[4 * nwn + iw] = s4;
+    double soc = 0.;
+    soc += (double)s0;
+    soc += (double)s1;
+    soc += 0.;
+    soc += 0.;
+    soc += (double)s4;
+    return soc;
+}
+// the totals of modm.f90:264-269 (the Rayleigh term of modm.f90:243-245 is zero below 820 cm-1)
+__device__ __forceinline__ double mw_total(double o_lines, double odx, double soc, double oclw) { return o_lines + odx + 0. + soc + oclw; }
+
 template <typename R>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void finish_mw_kernel(ModmArgs a, MwSetup q, const MwItemA *__restrict__ ia, const MwItemB *__restrict__ ib,
                                                        double V1ABS, double V2ABS, int NPTABS) {
@@ -645,19 +795,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void f
             obm[at] = (R)acc;  // read back in stage D, two barriers later
         }
     }
-    const double DVABS = 1.0;
-    const double V1 = q.V1, V2 = q.V2;
-    const double P0c = 1013., T0c = 296., XLOSMT = 2.68675E+19;
-    // (round 4: the layer scalars through reciprocals - v_rcp_f64 + two Newton steps, within an ulp of the IEEE quotients that
-    // finish_kernel forms - and the exponentials through exp_cw: 1250 -> ~1050 instructions per wave)
-    const double rTAVE = rcp2(TAVE), rWTOT = rcp2(WTOT), pr = PAVE * (1. / P0c);
-    const double RHOAVE = pr * (T0c * rTAVE);
-    const double XKT = TAVE * (1. / K_RADCN2);
-    const double amagat = pr * (273. * rTAVE);
-    const double x_vmr_h2o = WK1 * rWTOT, x_vmr_o2 = WK7 * rWTOT, x_vmr_n2 = 1. - x_vmr_h2o - x_vmr_o2;
-    const double wn2 = x_vmr_n2 * WTOT;
-    const double h2o_fac = x_vmr_h2o;
+    const double V1 = q.V1;
     const double xself = a.cntnm[0], xfrgn = a.cntnm[1], xco2c = a.cntnm[2], xn2cn = a.cntnm[5];
+    const MwLayer L = mw_layer(PAVE, TAVE, WTOT, WK1, WK2, WK7, xself, xfrgn, xco2c, xn2cn);
     const bool on0 = q.alive[0] && xself > 0., on1 = q.alive[1] && xfrgn > 0., on2 = q.alive[2] && xco2c > 0.,
                on3 = q.alive[3] && xn2cn > 0.;
     // LDS: coarse arrays of the four branches (q.off), then their four ABSRB grids [NPTABS + 4], 1-based
@@ -668,46 +808,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void f
     MW_T();
     // ---- stage A: coarse coefficients ------------------------------------------------------------
     {
-        const double Rself = h2o_fac * RHOAVE * 1.e-20 * xself;            // contnm.f90:325-371
-        const double TFAC = (TAVE - T0c) * (1. / (260. - T0c));
-        const double Rfrgn = (1. - h2o_fac) * RHOAVE * 1.e-20 * xfrgn;     // contnm.f90:380-474
-        const double WCO2 = WK2 * RHOAVE * 1.0E-20 * xco2c;                // contnm.f90:484-528 + FRNCO2 :2958
-        const double tau_fac = xn2cn * (wn2 / XLOSMT) * amagat;            // contnm.f90:906-943
-        const double tfac = (TAVE - 296.) * (1. / (220. - 296.));
         const int onmask = (on0 ? 1 : 0) | (on1 ? 2 : 0) | (on2 ? 4 : 0) | (on3 ? 8 : 0);
         for (int it = tid; it < q.off[4]; it += nt) {
             const MwItemA r = ia[it];
             const int b = r.flags & 3;
             const bool live = ((r.flags >> 2) & 1) && ((onmask >> b) & 1), intab = (r.flags >> 3) & 1;
             const double ta = r.ta, tc = r.tc, te = r.te, tf = r.tf;
-            // the temperature interpolations powpos(x, y) = exp(y log x) with the tabulated log x: self (260 K / 296 K), N2
-            // (220 K / 296 K) and its scale factor
-            const double pw1 = exp_cw((b == 0 ? TFAC : tfac) * ((b == 0 || b == 3) ? tc : 0.));
-            const double pw2 = exp_cw(tfac * (b == 3 ? tf : 0.));
+            // a lane picks its formula by selects: both exponentials on every item
+            const double pw1 = exp_cw((b == 0 ? L.TFAC : L.tfac) * ((b == 0 || b == 3) ? tc : 0.));
+            const double pw2 = exp_cw(L.tfac * (b == 3 ? tf : 0.));
             double v = 0.;
             if (live) {
-                if (b == 0) {
-                    if (intab) {
-                        double SH2O = 0.;
-                        if (ta > 0.) SH2O = ta * pw1;
-                        v = WK1 * (SH2O * Rself);
-                    }
-                } else if (b == 1) {
-                    double FH2O = intab ? ta : 0.;
-                    const double FSCAL = tc;  // xfac_rhu below 600 cm-1, the closed form above (mw_items_kernel)
-                    FH2O = FH2O * FSCAL;
-                    v = (WK1 * FH2O) * Rfrgn;
-                } else if (b == 2) {
-                    if (intab) v = ta * WCO2;  // (band-head temperature factor and chi factor are 1 below 2000 cm-1)
-                } else {
-                    double c0 = 0., c1 = 0.;
-                    if (intab) {
-                        c0 = ta * pw1;
-                        const double sf_T = te * pw2;
-                        c1 = (sf_T - 1.) * (0.79) / (0.21);
-                    }
-                    v = tau_fac * c0 * (x_vmr_n2 + c1 * x_vmr_o2 + 1. * x_vmr_h2o);
-                }
+                if (b == 0) v = mw_a_self(L, ta, pw1, intab);
+                else if (b == 1) v = mw_a_frgn(L, ta, tc, intab);
+                else if (b == 2) v = mw_a_co2(L, ta, intab);
+                else v = mw_a_n2(L, ta, te, pw1, pw2, intab);
             }
             sC[it] = v;
         }
@@ -723,7 +838,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void f
         double v = 0.;
         if (inside) {
             const double *A = sC + r.j;
-            v = (-A[0] * r.B1 + A[1] * r.c1 + A[2] * r.c2 - A[3] * r.B2) * 1.0;
+            v = mw_b_point(A[0], A[1], A[2], A[3], r);
         }
         sAbs[it] = v;
     }
@@ -733,64 +848,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void f
     // ---- stage C: second interpolation ABSRB -> wavenumbers (modm.f90:216-246) x RADFN -> OC -------------------
     double soc = 0.;  // sum of the continuum slots as stored (rounded to R)
     if (iw < nwn) {
-        const double wnv = a.wn[iw];
-        bool inside;
-        double vint;
-        if (a.dvset != 0.) {
-            const int I = iw + 1;
-            int ilo = (int)((V1ABS + DVABS - V1) / a.dvset + 1. + K_ONEMI);
-            if (ilo < 1) ilo = 1;
-            int ihi = (int)((V2ABS - DVABS - V1) / a.dvset + K_ONEMI);
-            if (ihi > nwn) ihi = nwn;
-            inside = I >= ilo && I <= ihi;
-            vint = V1 + a.dvset * (double)(I - 1);
-        } else {
-            int ilo = (int)((V1ABS + DVABS - wnv) / 1.0 + 1. + K_ONEMI);
-            if (ilo < 1) ilo = 1;
-            int ihi = (int)((V2ABS - DVABS - wnv) / 1.0 + K_ONEMI);
-            if (ihi > 1) ihi = 1;
-            inside = ilo <= 1 && ihi >= 1;
-            vint = wnv;
-        }
-        double rad = wnv;  // RADFN (src/lblrtm_sub.f90:36-97) with XKT > 0
-        {
-            const double x = (wnv * K_RADCN2) * rTAVE;
-            if (x <= 0.01) rad = 0.5 * x * wnv;
-            else if (x <= 10.0) {
-                const double e = exp_cw(-x);
-                rad = wnv * (1. - e) * rcp2(1. + e);
-            }
-        }
-        // the 4-point weights of XINT are the same for the three passes (same grid): xint_point on the sum of self and
-        // foreign needs ABSRB = (0 + self) + foreign per point, as CONTNM accumulates it
-        const double RECDVA = 1. / DVABS;
-        const int J = (int)((vint - V1ABS) * RECDVA + K_ONEPL);
-        const double VJ = V1ABS + DVABS * (double)(J - 1);
-        const double P = RECDVA * (vint - VJ);
-        const double C = (3. - 2. * P) * P * P;
-        const double B = 0.5 * P * (1. - P);
-        const double B1 = B * (1. - P), B2 = B * P;
-        double val[3] = {0., 0., 0.};
-        if (inside) {
-            const double *A0 = sAbs, *A1 = sAbs + NA, *A2 = sAbs + 2 * NA, *A3 = sAbs + 3 * NA;
-            const double h0 = A0[J - 1] + A1[J - 1], h1 = A0[J] + A1[J], h2 = A0[J + 1] + A1[J + 1], h3 = A0[J + 2] + A1[J + 2];
-            val[0] = -h0 * B1 + h1 * (1. - C + B2) + h2 * (C + B1) - h3 * B2;
-            val[1] = -A2[J - 1] * B1 + A2[J] * (1. - C + B2) + A2[J + 1] * (C + B1) - A2[J + 2] * B2;
-            val[2] = -A3[J - 1] * B1 + A3[J] * (1. - C + B2) + A3[J + 1] * (C + B1) - A3[J + 2] * B2;
-        }
-        const R s0 = (on0 || on1) ? (R)(val[0] * rad) : (R)0;
-        const R s1 = on2 ? (R)(val[1] * rad) : (R)0;
-        const R s4 = on3 ? (R)(val[2] * rad) : (R)0;
-        OC[iw] = s0;
-        OC[(size_t)nwn + iw] = s1;
-        OC[(size_t)2 * nwn + iw] = (R)0;
-        OC[(size_t)3 * nwn + iw] = (R)0;
-        OC[(size_t)4 * nwn + iw] = s4;
-        soc += (double)s0;
-        soc += (double)s1;
-        soc += 0.;
-        soc += 0.;
-        soc += (double)s4;
+        const MwChan c = mw_chan(a, V1, V1ABS, V2ABS, iw);
+        const double rad = mw_radfn(c.wnv, L.rTAVE);
+        double val[3];
+        mw_xint3(sAbs, NA, c, val);
+        soc = mw_store_oc<R>(OC, (size_t)nwn, iw, val, rad, on0 || on1, on2, on3);
     }
 
     MW_T();
@@ -801,8 +863,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void f
         const double oclw = (CLW == 0.) ? 0. : odclw_tkc(a.wn[iw], TAVE, CLW);
         OCLW[iw] = (R)oclw;
         const double odx = a.ODXSEC ? (double)rp<R>(a.ODXSEC)[pl * (size_t)nwn + iw] : 0.;  // cross-section molecules (modm.f90:197, :268)
-        const double o = o_lines + odx + 0. + soc + oclw;  // (the Rayleigh term of modm.f90:243-245 is zero below 820 cm-1)
-        O[iw] = (R)o;
+        O[iw] = (R)mw_total(o_lines, odx, soc, oclw);
     }
 #ifdef LINES_TIMING
     if (a.osum && tid < 12 && blockIdx.z == 0) OCLW[8 + tid] = (R)a.osum[pl * (size_t)nwn + tid];
@@ -812,6 +873,195 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void f
     if (tid == 0) for (int i = 1; i < ntq; i++) OCLW[i - 1] = (R)(double)(tq[i] - tq[i - 1]);
     if (tid == 0) OCLW[ntq - 1] = (R)(double)(tq[ntq - 1] - tq[0]);
 #endif
+}
+
+// ------------------------------------------------------------------------------------------------
+// finish_mw_kernel_col: the column layout of finish_mw_kernel.  finish_mw_kernel gives every (profile, layer) a workgroup, and nearly
+// all a wave of it executes is either the same for every layer of the profile (the item records, the per-channel values of stage C,
+// the kernel arguments and addresses) or the work of ONE layer done on 64 lanes (the reciprocals and the ten derived scalars; in
+// stage A two exp_cw on every item where the self branch needs one, the N2 branch two and the others none).  Here a workgroup of NW
+// waves serves one profile's block of up to 64 layers:
+//   phase 1, lane = layer: the layer scalars once per layer, in a lane; stage A with the ITEM wave-uniform - its record comes by scalar
+//            loads, its branch is a branch and only the exponentials that branch needs are evaluated - into sC[item][layer].  The
+//            waves split the items and repeat the cheap set-up.  One barrier.
+//   phase 2, lane = channel (ABSRB item in stage B), one layer after the other: each wave takes a contiguous share of the layers,
+//            keeps its stage-B records and everything that depends on the channel alone in registers, reads the layer's scalars out
+//            of the registers of phase 1 (v_readlane: every wave holds all 64 layers) and runs stages B, C and D as finish_mw_kernel
+//            does.  The ABSRB grids are private to the wave, and a wave's LDS instructions execute in order: no barrier here.
+// The values keep their expressions (the mw_* helpers above), so the outputs are bitwise finish_mw_kernel's.  Global loads and
+// stores are the same coalesced rows; the next layer's osum / ODXSEC rows are requested before this layer's stage C.
+// MULTI: more than 64 channels - a loop over blocks of 64 inside the layer, the per-channel values recomputed per block.
+// Line slices summed inside the finish kernel stay with finish_mw_kernel (finish_mw_layout.hpp).
+// grid = (blocks of 64 layers, profiles); dynamic LDS = finish_mw_col_lds().
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double mw_readlane(double x, int l) {  // x of lane l (wave-uniform l), as a scalar
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l), hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
+    return __hiloint2double(hi, lo);
+}
+// what the compiler knows about x ends here: nothing computed from it leaves the layer loop, so that an expression which holds both
+// the channel and the layer contracts as it does in finish_mw_kernel, where they sit in one basic block
+__device__ __forceinline__ double mw_opaque(double x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+// stages C and D of one (layer, channel)
+template <typename R>
+__device__ __forceinline__ void mw_col_point(const ModmArgs &a, const MwChan &c, const double *sAbs, int NA, double rTAVE, double TAVE,
+                                             double CLW, bool on01, bool on2, bool on3, double o_lines, double odx, size_t pl, int iw) {
+    const size_t nwn = (size_t)a.nwn;
+    const double wnv = mw_opaque(c.wnv);
+    const double rad = mw_radfn(wnv, rTAVE);
+    double val[3];
+    mw_xint3(sAbs, NA, c, val);
+    const double soc = mw_store_oc<R>(wp<R>(a.OC) + pl * MONORTM_NCONT * nwn, nwn, iw, val, rad, on01, on2, on3);
+    const double oclw = (CLW == 0.) ? 0. : odclw_tkc(wnv, TAVE, CLW);
+    wp<R>(a.O_CLW)[pl * nwn + iw] = (R)oclw;
+    wp<R>(a.O)[pl * nwn + iw] = (R)mw_total(o_lines, odx, soc, oclw);
+}
+template <typename R>
+__device__ __forceinline__ double mw_col_lines(const ModmArgs &a, size_t pl, int iw) {  // the line sum of (layer, channel), as finish_mw_kernel forms it
+    const size_t nwn = (size_t)a.nwn;
+    if (a.osum) return a.osum[pl * nwn + iw];
+    double o_lines = 0.;
+    const R *obm = rp<R>(a.O_BY_MOL) + pl * a.nmol * nwn;
+    for (int m = 0; m < a.nmol; m++) o_lines = o_lines + (double)obm[(size_t)m * nwn + iw];
+    return o_lines;
+}
+template <typename R>
+__device__ __forceinline__ double mw_col_odx(const ModmArgs &a, size_t pl, int iw) {
+    return a.ODXSEC ? (double)rp<R>(a.ODXSEC)[pl * (size_t)a.nwn + iw] : 0.;  // cross-section molecules (modm.f90:197, :268)
+}
+
+template <typename R, int NW, bool MULTI>
+__global__ __launch_bounds__(NW * 64) void finish_mw_kernel_col(ModmArgs a, MwSetup q, const MwItemA *__restrict__ ia, const MwItemB *__restrict__ ib,
+                                                                double V1ABS, double V2ABS, int NPTABS) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int KB = 3;  // stage-B records a lane keeps in registers (4 NA <= 192: every microwave sounder's range); the rest are re-read
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int prof = blockIdx.y, lay0 = blockIdx.x * 64;
+    const int nwn = a.nwn, nmol = a.nmol;
+    const int nblk = min(64, a.nlay_max - lay0);                     // layers of this block ...
+    const int nact = max(0, min(nblk, a.nlay[prof] - lay0));         // ... of which the profile has the first nact
+    const size_t pl0 = (size_t)prof * a.nlay_max + lay0;
+    const int nA = q.off[4], NA = NPTABS + 4, nB = 4 * NA;
+    double *sC = smem;                                               // [nA][MW_COL_STRIDE]: coarse value of (item, layer)
+    double *sAbs = smem + (size_t)nA * MW_COL_STRIDE + (size_t)wave * nB;  // this wave's four ABSRB grids [NPTABS + 4], 1-based
+
+    // ---- zero fill of the layers the profile does not have: the waves share them ----------------------------------------
+    {
+        const int per = (nblk - nact + NW - 1) / NW;
+        const int z0 = min(nblk, nact + wave * per), z1 = min(nblk, z0 + per);
+        for (int l = z0; l < z1; l++) {
+            const size_t pl = pl0 + l;
+            R *O = wp<R>(a.O) + pl * (size_t)nwn, *OCLW = wp<R>(a.O_CLW) + pl * (size_t)nwn;
+            R *OC = wp<R>(a.OC) + pl * MONORTM_NCONT * (size_t)nwn, *obm = wp<R>(a.O_BY_MOL) + pl * nmol * (size_t)nwn;
+            for (int iw = lane; iw < nwn; iw += 64) {
+                O[iw] = (R)0;
+                OCLW[iw] = (R)0;
+                for (int sl = 0; sl < MONORTM_NCONT; sl++) OC[(size_t)sl * nwn + iw] = (R)0;
+                for (int m = 0; m < nmol; m++) obm[(size_t)m * nwn + iw] = (R)0;
+            }
+        }
+    }
+    if (nact == 0) return;  // (the whole workgroup)
+
+    // ---- phase 1, lane = layer: the layer scalars, then stage A item by item ----------------------------------------------
+    const double xself = a.cntnm[0], xfrgn = a.cntnm[1], xco2c = a.cntnm[2], xn2cn = a.cntnm[5];
+    const bool on0 = q.alive[0] && xself > 0., on1 = q.alive[1] && xfrgn > 0., on2 = q.alive[2] && xco2c > 0.,
+               on3 = q.alive[3] && xn2cn > 0.;
+    const int onmask = (on0 ? 1 : 0) | (on1 ? 2 : 0) | (on2 ? 4 : 0) | (on3 ? 8 : 0);
+    double TAVE, CLW, rTAVE;
+    {
+        // (lanes beyond the profile's layers repeat its last one: their column of sC is never read)
+        const size_t pl = pl0 + min(lane, nact - 1);
+        const double PAVE = rp<R>(a.P)[pl], WBROAD = rp<R>(a.WBRODL)[pl];
+        TAVE = rp<R>(a.T)[pl], CLW = rp<R>(a.CLW)[pl];
+        const R *wk = rp<R>(a.WKL) + pl * nmol;
+        double WTOT = WBROAD;
+        for (int m = 0; m < nmol; m++) WTOT = WTOT + wk[m];
+        const double WK1 = wk[0], WK2 = wk[1], WK7 = wk[6];
+        const MwLayer L = mw_layer(PAVE, TAVE, WTOT, WK1, WK2, WK7, xself, xfrgn, xco2c, xn2cn);
+        rTAVE = L.rTAVE;
+        for (int it = wave; it < nA; it += NW) {
+            const MwItemA r = ia[it];  // wave-uniform: scalar loads
+            const int b = r.flags & 3;
+            const bool live = ((r.flags >> 2) & 1) && ((onmask >> b) & 1), intab = (r.flags >> 3) & 1;
+            double v = 0.;
+            if (live) {
+                if (b == 0) v = mw_a_self(L, r.ta, exp_cw(L.TFAC * r.tc), intab);
+                else if (b == 1) v = mw_a_frgn(L, r.ta, r.tc, intab);
+                else if (b == 2) v = mw_a_co2(L, r.ta, intab);
+                else v = mw_a_n2(L, r.ta, r.te, exp_cw(L.tfac * r.tc), exp_cw(L.tfac * r.tf), intab);
+            }
+            sC[it * MW_COL_STRIDE + lane] = v;
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2, lane = channel / ABSRB item: this wave's share of the layers, one after the other ------------------------
+    const int per = (nact + NW - 1) / NW;
+    const int la0 = min(nact, wave * per), la1 = min(nact, la0 + per);
+    if (la0 >= la1) return;  // (a wave without a layer; no barrier follows)
+    MwItemB rb[KB];
+    bool inB[KB];
+#pragma unroll
+    for (int k = 0; k < KB; k++) {
+        const int it = lane + 64 * k;
+        rb[k] = MwItemB{0., 0., 0., 0., 0, 0};
+        if (it < nB) rb[k] = ib[it];
+        inB[k] = ((rb[k].flags >> 2) & 1) && ((onmask >> (rb[k].flags & 3)) & 1);
+    }
+    const double V1 = q.V1;
+    const int ncb = MULTI ? (nwn + 63) / 64 : 1;
+    MwChan c0{};
+    double pre_o = 0., pre_x = 0.;
+    if (!MULTI && lane < nwn) {
+        c0 = mw_chan(a, V1, V1ABS, V2ABS, lane);
+        pre_o = mw_col_lines<R>(a, pl0 + la0, lane), pre_x = mw_col_odx<R>(a, pl0 + la0, lane);
+    }
+    for (int l = la0; l < la1; l++) {
+        const size_t pl = pl0 + l;
+        const double rT = mw_readlane(rTAVE, l), T = mw_readlane(TAVE, l), W = mw_readlane(CLW, l);
+        const double cur_o = pre_o, cur_x = pre_x;
+        if (!MULTI && lane < nwn && l + 1 < la1) pre_o = mw_col_lines<R>(a, pl + 1, lane), pre_x = mw_col_odx<R>(a, pl + 1, lane);
+        // stage B: XINT of every branch onto its ABSRB grid
+        const double *col = sC + l;
+#pragma unroll
+        for (int k = 0; k < KB; k++) {
+            const int it = lane + 64 * k;
+            if (it < nB) {
+                double v = 0.;
+                if (inB[k]) {
+                    const double *A = col + rb[k].j * MW_COL_STRIDE;
+                    v = mw_b_point(A[0], A[MW_COL_STRIDE], A[2 * MW_COL_STRIDE], A[3 * MW_COL_STRIDE], rb[k]);
+                }
+                sAbs[it] = v;
+            }
+        }
+        for (int it = lane + 64 * KB; it < nB; it += 64) {
+            const MwItemB r = ib[it];
+            double v = 0.;
+            if (((r.flags >> 2) & 1) && ((onmask >> (r.flags & 3)) & 1)) {
+                const double *A = col + r.j * MW_COL_STRIDE;
+                v = mw_b_point(A[0], A[MW_COL_STRIDE], A[2 * MW_COL_STRIDE], A[3 * MW_COL_STRIDE], r);
+            }
+            sAbs[it] = v;
+        }
+        team_sync<false>();
+        // stages C and D
+        if (!MULTI) {
+            if (lane < nwn) mw_col_point<R>(a, c0, sAbs, NA, rT, T, W, on0 || on1, on2, on3, cur_o, cur_x, pl, lane);
+        } else {
+            for (int cb = 0; cb < ncb; cb++) {
+                const int iw = cb * 64 + lane;
+                if (iw < nwn) {
+                    const MwChan c = mw_chan(a, V1, V1ABS, V2ABS, iw);
+                    mw_col_point<R>(a, c, sAbs, NA, rT, T, W, on0 || on1, on2, on3, mw_col_lines<R>(a, pl, iw), mw_col_odx<R>(a, pl, iw), pl, iw);
+                }
+            }
+        }
+        team_sync<false>();  // the next layer's stage B overwrites the grids
+    }
 }
 
 // Wide grids (nmol x nwn large): the slice sums as a bandwidth-bound kernel of their own, ahead of finish_kernel
@@ -868,8 +1118,15 @@ void launch_kat(int which, int n, const double *in, const double *tab, double *o
 void launch_logratio(const double *t296, const double *tlow, double *out, int n, hipStream_t s) {
     hipLaunchKernelGGL(logratio_kernel, dim3((n + 255) / 256), dim3(256), 0, s, t296, tlow, out, n);
 }
+template <typename R, int NW>
+static void launch_finish_mw_col(bool multi, dim3 grid, size_t lds, hipStream_t s, const ModmArgs &a, const MwSetup &q, const MwItemA *ia,
+                                 const MwItemB *ib, double V1ABS, double V2ABS, int NPTABS) {
+    if (multi) hipLaunchKernelGGL((finish_mw_kernel_col<R, NW, true>), grid, dim3(NW * 64), lds, s, a, q, ia, ib, V1ABS, V2ABS, NPTABS);
+    else hipLaunchKernelGGL((finish_mw_kernel_col<R, NW, false>), grid, dim3(NW * 64), lds, s, a, q, ia, ib, V1ABS, V2ABS, NPTABS);
+}
+// layout_opt: option "finish_mw" (FINISH_MW_*); cus: compute units of the device; *column: whether the column layout served the call
 hipError_t launch_finish_mw(const ModmArgs &a, const DevTables &tb, double V1, double V2, double V1ABS, double V2ABS, int NPTABS,
-                            MwCache &cache, hipStream_t s) {
+                            MwCache &cache, int layout_opt, int cus, bool *column, hipStream_t s) {
     MwSetup q;
     const double v1s[4] = {MT_SELF296_V1, MT_FRGN296_V1, MT_FCO2_V1, MT_N2RT296_V1};
     const double v2s[4] = {MT_SELF296_V2, MT_FRGN296_V2, MT_FCO2_V2, MT_N2RT296_V2};
@@ -963,6 +1220,20 @@ hipError_t launch_finish_mw(const ModmArgs &a, const DevTables &tb, double V1, d
     en->last_use = ++cache.clock;
     const MwItemA *ia = static_cast<const MwItemA *>(en->items);
     const MwItemB *ib = reinterpret_cast<const MwItemB *>(ia + nA);
+    // The layout (finish_mw_layout.hpp).  `auto` takes the column layout where it was measured to win - configs[3] whole, 0.948 -> 0.923
+    // ms per step; the rule and its numbers stand beside finish_mw_col_waves().  Both layouts are variant 0 of the launch counters.
+    int col_nw = finish_mw_col_waves(MwLayoutIn{a.nprof, a.nlay_max, a.nwn, cus, nA, NPTABS, sliced, layout_opt});
+#if defined(LINES_TIMING) || defined(MW_TIMING)
+    col_nw = 0;  // the timing probes live in finish_mw_kernel
+#endif
+    if (column) *column = col_nw != 0;
+    if (col_nw) {
+        const dim3 cgrid((a.nlay_max + 63) / 64, a.nprof);
+        const size_t clds = finish_mw_col_lds(nA, NPTABS, col_nw);
+        if (a.real_kind == 4) launch_finish_mw_col<float, 4>(a.nwn > 64, cgrid, clds, s, a, q, ia, ib, V1ABS, V2ABS, NPTABS);
+        else launch_finish_mw_col<double, 4>(a.nwn > 64, cgrid, clds, s, a, q, ia, ib, V1ABS, V2ABS, NPTABS);
+        return hipGetLastError();
+    }
     if (a.real_kind == 4) hipLaunchKernelGGL(finish_mw_kernel<float>, grid, dim3(threads), lds, s, a, q, ia, ib, V1ABS, V2ABS, NPTABS);
     else hipLaunchKernelGGL(finish_mw_kernel<double>, grid, dim3(threads), lds, s, a, q, ia, ib, V1ABS, V2ABS, NPTABS);
     return hipGetLastError();

@@ -521,8 +521,9 @@ struct MwCache {
     const char *why = nullptr;  // reason of the last failure, where hipGetErrorString would not say it
     void release();             // frees every entry (context teardown; the device is idle)
 };
+// layout_opt: option "finish_mw" (finish_mw_layout.hpp); cus: compute units; *column: the column layout served the call
 hipError_t launch_finish_mw(const ModmArgs &a, const DevTables &tb, double V1, double V2, double V1ABS, double V2ABS, int NPTABS, MwCache &cache,
-                            hipStream_t s);
+                            int layout_opt, int cus, bool *column, hipStream_t s);
 // known-answer hook: device versions of W4, SD_Humlicek, SDVOIGT, RADFN, AtoB, ODCLW_TKC, TIPS scor (continuum_kernel.hip)
 void launch_kat(int which, int n, const double *in, const double *tab, double *out, int *errflag, const DevTables &tb, hipStream_t s);
 // xsec_kernel.hip: MONORTM_XSEC_SUB + convolve (src/monortm_sub.F90:1540-1834) -> a.ODXSEC
