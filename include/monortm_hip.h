@@ -668,6 +668,85 @@ int monortm_hip_oe_step_full_dev(void *ctx, int nprof, int nview, int nchan, int
                                  monortm_real *chi2, int *status, monortm_real *gain_t, monortm_real *avk, monortm_real *post_cov,
                                  monortm_real *dofs, void *stream);
 
+/* ---- The adaptive retrieval loop: Levenberg-Marquardt step acceptance per profile, on the device.  DESIGN.md section 3.15.
+ * The cost J(x) = (y_obs - F(x))^T Se^-1 (y_obs - F(x)) + (x - xa)^T Sa^-1 (x - xa) needs Sa^-1, which never appears here: the iterate
+ * carries its dual vector c = Sa^-1 (x - xa) instead.  monortm_hip_oe_step_lm is monortm_hip_oe_step_full with three more arrays:
+ *   c               [nprof][nstate], or NULL: 0 (exact at x = xa)
+ *   c_new           [nprof][nstate], may be NULL; not c itself.  c_new = (gamma c + K^T M^-1 r) / (1 + gamma) = Sa^-1 (x_new - xa), by
+ *                   the step's own algebra; K^T M^-1 r is one more dot product (L^-1 K_:,i) . (L^-1 r) per state, in the order of the others
+ *   cost            [nprof], may be NULL: chi2 + sum_i c_i (x_i - xa_i), the cost at x, summed in ascending i
+ * A failed profile (status 1) has c_new = c (0 where c is NULL) and cost = 0.  Every other output is what monortm_hip_oe_step_full gives
+ * on the same inputs, bit for bit; with c, c_new and cost all NULL the call launches what that entry launches.  c = NULL and c = 0 give
+ * the same bits.  Refusals, sharding, workspace and state map as monortm_hip_oe_step_full[_dev]; c_new == c is refused (MONORTM_EARG). */
+int monortm_hip_oe_step_lm(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                           const int *state_row, const monortm_real *K_T, const monortm_real *K_TZ, const monortm_real *K_W,
+                           const monortm_real *K_CLW, const monortm_real *K_SFC, const monortm_real *Y, const monortm_real *y_obs,
+                           const monortm_real *x, const monortm_real *xa, const monortm_real *Sa, int sa_per_profile,
+                           const monortm_real *Se, int se_kind, int se_per_profile, const monortm_real *gamma, monortm_real *x_new,
+                           monortm_real *post_var, monortm_real *avk_diag, monortm_real *chi2, int *status, monortm_real *gain_t,
+                           monortm_real *avk, monortm_real *post_cov, monortm_real *dofs, const monortm_real *c, monortm_real *c_new,
+                           monortm_real *cost);
+int monortm_hip_oe_step_lm_dev(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate,
+                               const int *state_kind /*host*/, const int *state_row /*host*/, const monortm_real *K_T,
+                               const monortm_real *K_TZ, const monortm_real *K_W, const monortm_real *K_CLW, const monortm_real *K_SFC,
+                               const monortm_real *Y, const monortm_real *y_obs, const monortm_real *x, const monortm_real *xa,
+                               const monortm_real *Sa, int sa_per_profile, const monortm_real *Se, int se_kind, int se_per_profile,
+                               const monortm_real *gamma, monortm_real *x_new, monortm_real *post_var, monortm_real *avk_diag,
+                               monortm_real *chi2, int *status, monortm_real *gain_t, monortm_real *avk, monortm_real *post_cov,
+                               monortm_real *dofs, const monortm_real *c, monortm_real *c_new, monortm_real *cost, void *stream);
+
+/* A state vector written into the resident inputs of a batch, checked against a box first.  Device pointers only, asynchronous on
+ * `stream`, one launch, one workgroup per profile.  The write map (host int [nstate] each) names the target of every state column:
+ *   map_kind        0: T[p][index]   1: TZ[p][index]   2: WKL[p][index][map_mol] = exp(x)   3: CLW[p][index]   4: TMPSFC[p]
+ *                   -1: checked against the box but not written (a variable that a later column names again)
+ *   map_index       layer (kinds 0, 2, 3) or level (kind 1).  A column is LIVE for profile p where index < nlay[p] (kind 1: index <=
+ *                   nlay[p]; kind 4: always).  For kind -1 live means index < nlay[p]: give level - 1 for a level, -1 for TMPSFC.
+ *   map_mol         0-based molecule of a kind-2 column
+ *   x_src           [nprof][nstate]
+ *   x_fallback      [nprof][nstate] or NULL;  done  int [nprof] or NULL
+ *   lo, hi          [nstate], or [nprof][nstate] with box_per_profile = 1; each may be NULL (no bound on that side)
+ *   nlay            int [nprof]
+ *   T, TZ, WKL, CLW with the elements per profile of each (WKL is [..][nmol] within a profile); an array no column writes may be NULL
+ *   tmpsfc_a, _b    [nprof] each: both are written by a kind-4 column (one may be NULL)
+ *   trial_ok        int [nprof], may be NULL
+ * trial_ok[p] = every live element of x_src[p] is finite and inside [lo, hi].  Then the live columns of kind >= 0 are written from
+ * x_fallback[p] where that is given and (trial_ok[p] == 0 or done[p] != 0), from x_src[p] otherwise.  Nothing else in the arrays changes.
+ * Refused before the launch (MONORTM_EARG): a kind outside -1..4, an index or molecule outside its array or the stride, a written array
+ * that is NULL, two written columns with one target, nstate outside 1..2048; real_kind 4 (MONORTM_EUNSUPPORTED).  The device copy of
+ * the map is kept like the state map of monortm_hip_oe_step_dev: after one call, a second of the same map allocates and copies nothing.
+ * ONE MAP PER CONTEXT, like the state map: a call with another map waits for `stream` (only), replaces the device copy with a blocking
+ * copy and may reallocate it.  A captured graph holds the pointer and reads whatever map is there when it replays: while a capture of
+ * this entry (or of monortm_hip_oe_step*_dev) is alive, call it on that context with the captured map only.  Callers that alternate
+ * between state vectors use one context per state vector. */
+int monortm_hip_oe_scatter_dev(void *ctx, int nprof, int nstate, const int *map_kind /*host*/, const int *map_index /*host*/,
+                               const int *map_mol /*host*/, const monortm_real *x_src, const monortm_real *x_fallback, const int *done,
+                               const monortm_real *lo, const monortm_real *hi, int box_per_profile, const int *nlay, int nlay_max,
+                               int nmol, monortm_real *T, long long t_stride, monortm_real *TZ, long long tz_stride, monortm_real *WKL,
+                               long long wkl_stride, monortm_real *CLW, long long clw_stride, monortm_real *tmpsfc_a,
+                               monortm_real *tmpsfc_b, int *trial_ok, void *stream);
+
+/* The decision on a trial step, per profile: device pointers only, asynchronous on `stream`, one launch, one workgroup per profile, no
+ * atomics.  Y_trial [nprof][nmeas] is the forward model at the state the scatter wrote; Se, se_kind, se_per_profile as in
+ * monortm_hip_oe_step_full; x_trial, c_trial (the step's x_new, c_new), xa [nprof][nstate]; step_status, trial_ok int [nprof].
+ * Loop state, updated in place: x_cur, c_cur [nprof][nstate]; J_cur, gamma [nprof]; done, n_acc, n_rej int [nprof].  Per profile:
+ *   done != 0                nothing of the profile changes, bit for bit
+ *   step_status == 1         done = 2
+ *   otherwise  J_trial = chi2(Y_trial) + sum_i c_trial_i (x_trial_i - xa_i); chi2 as the step forms it (se_kind 1: a bad pivot of Se
+ *              gives done = 2); accept = trial_ok && isfinite(J_trial) && J_trial <= J_cur
+ *   accept     x_cur = x_trial, c_cur = c_trial, J_cur = J_trial, gamma = gamma down (0 where that is below gamma_floor), n_acc + 1,
+ *              done = 1 where the decrease of J is <= conv nmeas
+ *   reject     gamma = max(gamma up, gamma_first), n_rej + 1, done = 4 where gamma > gamma_max
+ *   last != 0 and done still 0: done = 3
+ * done: 0 running, 1 converged, 2 failed step, 3 out of iterations, 4 stalled at gamma_max.  No error of monortm_hip_check.
+ * Refused (MONORTM_EARG): nmeas outside 1..128, nstate outside 1..2048, se_kind outside 0..1, a NULL array, up < 1, down outside 0..1,
+ * gamma_first <= 0, a negative gamma_floor, gamma_max or conv, a NaN among them; real_kind 4 (MONORTM_EUNSUPPORTED). */
+int monortm_hip_oe_accept_dev(void *ctx, int nprof, int nmeas, int nstate, const monortm_real *Y_trial, const monortm_real *y_obs,
+                              const monortm_real *Se, int se_kind, int se_per_profile, const monortm_real *x_trial,
+                              const monortm_real *c_trial, const monortm_real *xa, const int *step_status, const int *trial_ok, double up,
+                              double down, double gamma_first, double gamma_floor, double gamma_max, double conv, int last,
+                              monortm_real *x_cur, monortm_real *c_cur, monortm_real *J_cur, monortm_real *gamma, int *done, int *n_acc,
+                              int *n_rej, void *stream);
+
 /* Device-side failure flags raised by the kernels of earlier *_dev calls (temperature range, SD-Voigt
  * sign): synchronises `stream`, returns MONORTM_OK or the first error and clears the flags. */
 int monortm_hip_check(void *ctx, void *stream);

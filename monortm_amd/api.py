@@ -130,6 +130,10 @@ SYMBOLS = {
     "monortm_hip_oe_step_dev": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int] + [_vp] * 7),
     "monortm_hip_oe_step_full": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 10),
     "monortm_hip_oe_step_full_dev": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 11),
+    "monortm_hip_oe_step_lm": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 13),
+    "monortm_hip_oe_step_lm_dev": (C.c_int, [_vp] + [C.c_int] * 6 + [_vp] * 12 + [C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 14),
+    "monortm_hip_oe_scatter_dev": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 8 + [C.c_int, _vp, C.c_int, C.c_int] + [_vp, C.c_longlong] * 4 + [_vp] * 4),
+    "monortm_hip_oe_accept_dev": (C.c_int, [_vp] + [C.c_int] * 3 + [_vp] * 3 + [C.c_int] * 2 + [_vp] * 5 + [C.c_double] * 6 + [C.c_int] + [_vp] * 8),
     "monortm_hip_check": (C.c_int, [_vp, _vp]),
     "monortm_hip_profile": (C.c_int, [_vp, C.c_int]),
     "monortm_hip_kernel_time": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_longlong)]),
@@ -270,6 +274,43 @@ def _oe_map_of(state, nlay_max: int, vars):
             raise ValueError("state map: state_kind and state_row must be two int arrays of one length >= 1")
         return kind, row
     return oe_state_map(state, nlay_max, vars)
+
+
+def _lm_check(se, Se, x0, c0):
+    """What retrieve_lm and lm_start refuse before they touch the batch."""
+    if (se is None) == (Se is None):
+        raise ValueError("retrieve_lm: give se (variances) or Se (any shape of oe_step_full), not both")
+    if x0 is not None and c0 is None:
+        raise ValueError("retrieve_lm: x0 needs c0, the caller's own Sa^-1 (x0 - xa) (the loop never forms Sa^-1)")
+    if x0 is None and c0 is not None:
+        raise ValueError("retrieve_lm: c0 without x0")
+
+
+OE_WRITE_KINDS = {"t": 0, "tz": 1, "w": 2, "clw": 3, "tmpsfc": 4}
+OE_DONE = {0: "running", 1: "converged", 2: "failed step", 3: "out of iterations", 4: "stalled at gamma_max"}
+
+
+def oe_write_map(spec, nlay_max: int, nmol: int):
+    """(map_kind, map_index, map_mol) of monortm_hip_oe_scatter_dev, int32 [nstate], from a state spec over ("t", layers), ("tz",
+    levels), ("w", molecule, layers), ("clw", layers) and ("tmpsfc",).  A variable named twice is written from its last column: the
+    earlier ones get kind -1 (checked against the box, not written) and an index under which `index < nlay` says whether they are
+    live - the layer, level - 1, or -1 for TMPSFC.  ValueError for what has no resident input ("emiss", "reflc", a Jacobian variable
+    that is no molecule of the batch)."""
+    items = _oe_items(spec, nlay_max)
+    kind, index, mol = (np.zeros(len(items), np.int32) for _ in range(3))
+    last = {}
+    for col, (name, code, k) in enumerate(items):
+        if name not in OE_WRITE_KINDS:
+            raise ValueError(f"a state element {name!r} has no resident scalar to write back (oe_step itself takes it)")
+        if name == "w" and not 1 <= code <= nmol:
+            raise ValueError(f"Jacobian variable {code} is not a molecule of the batch (oe_step itself takes it)")
+        last[(name, code, k)] = col
+    for col, (name, code, k) in enumerate(items):
+        if last[(name, code, k)] == col:
+            kind[col], index[col], mol[col] = OE_WRITE_KINDS[name], 0 if k is None else k, code - 1 if name == "w" else 0
+        else:
+            kind[col], index[col] = -1, -1 if k is None else k - 1 if name == "tz" else k
+    return kind, index, mol
 
 
 JAC_FIELDS = ("o", "rad", "tb", "k_t", "k_tz", "k_w", "k_clw", "k_o", "k_sfc")
@@ -952,6 +993,39 @@ class MonoRTM:
                                                     *[_ptr(out[w]) if w in want else None for w in OE_FULL_WANT]))
         return out
 
+    # ---- the step that carries the dual vector of the adaptive loop (monortm_hip_oe_step_lm) -------------------------
+    def oe_step_lm(self, jac: dict, state, y_obs, x, xa, Sa, Se, gamma=None, c=None, want=(), se_kind=None) -> dict:
+        """oe_step_full plus the dual vector of the iterate: c [nprof, nstate] = Sa^-1 (x - xa), None for 0 (x = xa).  The dict of
+        oe_step_full and c_new [nprof, nstate] = Sa^-1 (x_new - xa) and cost [nprof] = chi2 + c . (x - xa), the cost at x; a failed
+        profile has c_new = c and cost = 0."""
+        want = _oe_want(want)
+        kt = jac["k_t"]
+        nprof, nv, lm, nc = kt.shape
+        kw = jac.get("k_w")
+        nj = 0 if kw is None else kw.shape[3]
+        kind, row = _oe_map_of(state, lm, jac.get("vars", ()))
+        n, m = len(kind), nv * nc
+        f = lambda a: None if a is None else _np(a)  # noqa: E731
+        K = [f(jac.get(k)) for k in ("k_t", "k_tz", "k_w", "k_clw", "k_sfc")]
+        if nj == 0:
+            K[2] = None
+        Y, yo, x, xa, Sa, Se, gamma, c = (f(a) for a in (jac["y"], y_obs, x, xa, Sa, Se, gamma, c))
+        se_kind, se_pp = oe_se_kind(Se.shape, nprof, m, se_kind)
+        for name, a, shapes in (("y_obs", yo, [(nprof, nv, nc)]), ("x", x, [(nprof, n)]), ("xa", xa, [(nprof, n)]), ("Sa", Sa, [(n, n), (nprof, n, n)]),
+                                ("gamma", gamma, [(nprof,)]), ("c", c, [(nprof, n)])):
+            if a is not None and a.shape not in shapes:
+                raise ValueError(f"{name} must be {' or '.join(str(list(s)) for s in shapes)}, got {list(a.shape)}")
+        out = dict(x_new=np.zeros((nprof, n)), post_var=np.zeros((nprof, n)), avk_diag=np.zeros((nprof, n)), chi2=np.zeros(nprof),
+                   status=np.zeros(nprof, np.int32), c_new=np.zeros((nprof, n)), cost=np.zeros(nprof))
+        shapes = dict(gain_t=(nprof, m, n), avk=(nprof, n, n), post_cov=(nprof, n, n), dofs=(nprof,))
+        out.update({w: np.zeros(shapes[w]) for w in want})
+        self._chk(self.lib.monortm_hip_oe_step_lm(self.ctx, nprof, nv, nc, lm, nj, n, _ptr(kind), _ptr(row), *[_ptr(k) for k in K], _ptr(Y),
+                                                  _ptr(yo), _ptr(x), _ptr(xa), _ptr(Sa), int(Sa.ndim == 3), _ptr(Se), se_kind, se_pp, _ptr(gamma),
+                                                  *[_ptr(out[k]) for k in ("x_new", "post_var", "avk_diag", "chi2", "status")],
+                                                  *[_ptr(out[w]) if w in want else None for w in OE_FULL_WANT], _ptr(c), _ptr(out["c_new"]),
+                                                  _ptr(out["cost"])))
+        return out
+
     # ---- the forward measurement operator (monortm_hip_rtm_obs / monortm_hip_obs; DESIGN.md section 3.10) ------------------------------
     def rtm_obs(self, profiles: list[Profile], O: np.ndarray, path, obs: int, quantity="tb", emiss=None, reflc=None, vcen=None) -> dict:
         """y = F(x) per measurement from one O [nprof, nlay_max, nwn]: the radiances of rtm_scan contracted with the operator `obs`
@@ -1360,6 +1434,16 @@ class DeviceBatch:
         The outputs - x_new, post_var, avk_diag, chi2, status and the diagnostics in `want` ("gain_t", "avk", "post_cov", "dofs") - are
         allocated at the first call for (nprof, nview, nchan, nstate, want) and overwritten by every later one: a graph capture of the
         call (after one warm call) replays into the same tensors."""
+        return self._oe_step_dev(jac, state, y_obs, x, xa, Sa, Se, gamma, want, stream, se_kind)
+
+    def oe_step_lm(self, jac: dict, state, y_obs, x, xa, Sa, Se, gamma=None, c=None, want=(), stream=None, se_kind=None) -> dict:
+        """MonoRTM.oe_step_lm on torch tensors, asynchronously, under the rules of oe_step_full: c [nprof, nstate] or None (0).  The
+        outputs of oe_step_full plus c_new [nprof, nstate] and cost [nprof], tensors of this entry's own, allocated at the first call for
+        (nprof, nview, nchan, nstate, want) and overwritten by every later one."""
+        return self._oe_step_dev(jac, state, y_obs, x, xa, Sa, Se, gamma, want, stream, se_kind, dual=True, c=c)
+
+    def _oe_step_dev(self, jac, state, y_obs, x, xa, Sa, Se, gamma, want, stream, se_kind, dual=False, c=None) -> dict:
+        """oe_step_full, or with dual oe_step_lm: one validation, one cache per entry, one call."""
         t = self.torch
         want = _oe_want(want)
         kt = jac["k_t"]
@@ -1373,30 +1457,33 @@ class DeviceBatch:
         if nj == 0:
             K[2] = None
         for name, a, shapes in [("y_obs", y_obs, [(nprof, nv, nc)]), ("x", x, [(nprof, n)]), ("xa", xa, [(nprof, n)]), ("Sa", Sa, [(n, n), (nprof, n, n)]),
-                                ("Se", Se, None), ("gamma", gamma, [(nprof,)]), ("y", jac["y"], [(nprof, nv, nc)])] + \
+                                ("Se", Se, None), ("gamma", gamma, [(nprof,)]), ("c", c, [(nprof, n)]), ("y", jac["y"], [(nprof, nv, nc)])] + \
                                [(f"K[{i}]", k, None) for i, k in enumerate(K)]:
-            if a is None and (name == "gamma" or name.startswith("K[")):
+            if a is None and (name in ("gamma", "c") or name.startswith("K[")):
                 continue
             if not isinstance(a, t.Tensor) or a.dtype != t.float64 or a.device != self.dev or not a.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous float64 tensor on {self.dev}")
             if shapes is not None and tuple(a.shape) not in shapes:
                 raise ValueError(f"{name} must be {' or '.join(str(list(s)) for s in shapes)}, got {list(a.shape)}")
         se_kind, se_pp = oe_se_kind(Se.shape, nprof, m, se_kind)
-        cache = self.__dict__.setdefault("_oe_full", {})
+        cache = self.__dict__.setdefault("_oe_lm" if dual else "_oe_full", {})
         key = (nprof, nv, nc, n, want)
         if key not in cache:
             z = lambda *s: t.zeros(*s, dtype=t.float64, device=self.dev)  # noqa: E731
             shapes = dict(gain_t=(nprof, m, n), avk=(nprof, n, n), post_cov=(nprof, n, n), dofs=(nprof,))
             cache[key] = dict(x_new=z(nprof, n), post_var=z(nprof, n), avk_diag=z(nprof, n), chi2=z(nprof),
                               status=t.zeros(nprof, dtype=t.int32, device=self.dev), **{w: z(*shapes[w]) for w in want})
+            if dual:
+                cache[key].update(c_new=z(nprof, n), cost=z(nprof))
         out = cache[key]
         s = stream if stream is not None else t.cuda.current_stream(self.dev)
         rt = self.rt
         d = lambda a: None if a is None else _vp(a.data_ptr())  # noqa: E731
-        rt._chk(rt.lib.monortm_hip_oe_step_full_dev(rt.ctx, nprof, nv, nc, lm, nj, n, _ptr(kind), _ptr(row), *[d(k) for k in K], d(jac["y"]),
-                                                    d(y_obs), d(x), d(xa), d(Sa), int(Sa.dim() == 3), d(Se), se_kind, se_pp, d(gamma),
-                                                    *[d(out[k]) for k in ("x_new", "post_var", "avk_diag", "chi2", "status")],
-                                                    *[d(out.get(w)) for w in OE_FULL_WANT], _vp(s.cuda_stream)))
+        entry = rt.lib.monortm_hip_oe_step_lm_dev if dual else rt.lib.monortm_hip_oe_step_full_dev
+        rt._chk(entry(rt.ctx, nprof, nv, nc, lm, nj, n, _ptr(kind), _ptr(row), *[d(k) for k in K], d(jac["y"]),
+                      d(y_obs), d(x), d(xa), d(Sa), int(Sa.dim() == 3), d(Se), se_kind, se_pp, d(gamma),
+                      *[d(out[k]) for k in ("x_new", "post_var", "avk_diag", "chi2", "status")],
+                      *[d(out.get(w)) for w in OE_FULL_WANT], *([d(c), d(out["c_new"]), d(out["cost"])] if dual else []), _vp(s.cuda_stream)))
         return dict(out)
 
     def _oe_resident(self, items):
@@ -1484,6 +1571,170 @@ class DeviceBatch:
                 if it + 1 < len(gammas):
                     x.copy_(xn)
         out = dict(step, x=x, chi2_history=t.stack(hist))
+        if keep:
+            out["kept"] = kept
+        return out
+
+    # ---- the adaptive retrieval loop: LM step acceptance per profile, on the device -------------------------------
+    def oe_scatter(self, wmap, x_src, x_fallback=None, done=None, lo=None, hi=None, trial_ok=None, stream=None) -> None:
+        """monortm_hip_oe_scatter_dev on the batch's resident T, TZ, WKL, CLW and both TMPSFC copies, asynchronously: wmap is the
+        triple of oe_write_map; x_src, x_fallback [nprof, nstate] float64, done, trial_ok [nprof] int32, lo, hi [nstate] or [nprof, nstate],
+        all contiguous tensors on the batch's device (ValueError otherwise)."""
+        t = self.torch
+        kind, index, mol = (np.ascontiguousarray(a, np.int32) for a in wmap)
+        n = len(kind)
+        for name, a, dt, shapes in (("x_src", x_src, t.float64, [(self.nprof, n)]), ("x_fallback", x_fallback, t.float64, [(self.nprof, n)]),
+                                    ("done", done, t.int32, [(self.nprof,)]), ("trial_ok", trial_ok, t.int32, [(self.nprof,)]),
+                                    ("lo", lo, t.float64, [(n,), (self.nprof, n)]), ("hi", hi, t.float64, [(n,), (self.nprof, n)])):
+            if a is None and name != "x_src":
+                continue
+            if not isinstance(a, t.Tensor) or a.dtype != dt or a.device != self.dev or not a.is_contiguous() or tuple(a.shape) not in shapes:
+                raise ValueError(f"{name} must be a contiguous {dt} tensor {' or '.join(str(list(s)) for s in shapes)} on {self.dev}")
+        per = [a.dim() == 2 for a in (lo, hi) if a is not None]
+        if len(set(per)) > 1:
+            raise ValueError("lo and hi must both be [nstate] or both [nprof, nstate]")
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        rt = self.rt
+        d = lambda a: None if a is None else _vp(a.data_ptr())  # noqa: E731
+        rt._chk(rt.lib.monortm_hip_oe_scatter_dev(rt.ctx, self.nprof, n, _ptr(kind), _ptr(index), _ptr(mol), d(x_src), d(x_fallback), d(done), d(lo),
+                                                  d(hi), int(bool(per) and per[0]), d(self.nlay), self.lm, self.nmol, d(self.T), self.lm, d(self.TZ),
+                                                  self.lm + 1, d(self.WKL), self.lm * self.nmol, d(self.CLW), self.lm, d(self.tmpsfc0),
+                                                  d(self.tmpsfc), d(trial_ok), _vp(s.cuda_stream)))
+
+    def oe_accept(self, y_trial, y_obs, Se, x_trial, c_trial, xa, step_status, trial_ok, loop: dict, up=10.0, down=0.5, gamma_first=1.0,
+                  gamma_floor=1e-3, gamma_max=1e8, conv=0.01, last=False, stream=None, se_kind=None) -> None:
+        """monortm_hip_oe_accept_dev, asynchronously: the decision on a trial step.  loop holds the state it updates in place - x_cur,
+        c_cur [nprof, nstate], J_cur, gamma [nprof] float64 and done, n_acc, n_rej [nprof] int32.  Every array a contiguous tensor on the
+        batch's device; Se in any shape of oe_step_full."""
+        t = self.torch
+        nprof, n = (int(v) for v in x_trial.shape)
+        m = int(y_obs.numel()) // nprof
+        se_kind, se_pp = oe_se_kind(Se.shape, nprof, m, se_kind)
+        f64 = [("y_trial", y_trial, m), ("y_obs", y_obs, m), ("Se", Se, None), ("x_trial", x_trial, n), ("c_trial", c_trial, n), ("xa", xa, n),
+               ("x_cur", loop["x_cur"], n), ("c_cur", loop["c_cur"], n), ("J_cur", loop["J_cur"], 1), ("gamma", loop["gamma"], 1)]
+        i32 = [(k, v, 1) for k, v in (("step_status", step_status), ("trial_ok", trial_ok), ("done", loop["done"]), ("n_acc", loop["n_acc"]),
+                                      ("n_rej", loop["n_rej"]))]
+        for dt, group in ((t.float64, f64), (t.int32, i32)):
+            for name, a, per in group:
+                if not isinstance(a, t.Tensor) or a.dtype != dt or a.device != self.dev or not a.is_contiguous() or \
+                        (per is not None and a.numel() != nprof * per):
+                    raise ValueError(f"{name} must be a contiguous {dt} tensor of {nprof} x {per} elements on {self.dev}")
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        rt = self.rt
+        d = lambda a: _vp(a.data_ptr())  # noqa: E731
+        rt._chk(rt.lib.monortm_hip_oe_accept_dev(rt.ctx, nprof, m, n, d(y_trial), d(y_obs), d(Se), se_kind, se_pp, d(x_trial), d(c_trial), d(xa),
+                                                 d(step_status), d(trial_ok), float(up), float(down), float(gamma_first), float(gamma_floor),
+                                                 float(gamma_max), float(conv), int(bool(last)),
+                                                 *[d(loop[k]) for k in ("x_cur", "c_cur", "J_cur", "gamma", "done", "n_acc", "n_rej")], _vp(s.cuda_stream)))
+
+    def lm_start(self, y_obs, path, obs: int, state, xa, Sa, se=None, Se=None, gamma0=0.0, up=10.0, down=0.5, gamma_first=1.0, gamma_floor=1e-3,
+                 gamma_max=1e8, conv=0.01, lo=None, hi=None, x0=None, c0=None, mols=None, quantity="tb", stream=None) -> dict:
+        """The loop state of retrieve_lm, with the first iterate (xa, or x0 with its dual vector c0) written into the batch: the dict that
+        lm_iterate advances.  Its tensors are cached per (nstate, nmeas): a second loop of the same shape allocates nothing."""
+        _lm_check(se, Se, x0, c0)
+        t = self.torch
+        items = _oe_items(state, self.lm)
+        wmap = oe_write_map(state, self.lm, self.nmol)
+        if mols is None:
+            mols = tuple(dict.fromkeys(code for name, code, _ in items if name == "w"))
+        n = len(items)
+        if not isinstance(xa, t.Tensor) or tuple(xa.shape) != (self.nprof, n):
+            raise ValueError(f"xa must be a tensor [{self.nprof}, {n}]")
+        nv, nc = self.rt._obs_shape(obs)
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        cache = self.__dict__.setdefault("_lm", {})
+        key = (n, nv, nc)
+        if key not in cache:
+            z = lambda *sh: t.zeros(*sh, dtype=t.float64, device=self.dev)  # noqa: E731
+            zi = lambda: t.zeros(self.nprof, dtype=t.int32, device=self.dev)  # noqa: E731
+            cache[key] = dict(x_cur=z(self.nprof, n), c_cur=z(self.nprof, n), J_cur=z(self.nprof), gamma=z(self.nprof), done=zi(), n_acc=zi(),
+                              n_rej=zi(), trial_ok=zi())
+        L = dict(cache[key], y_obs=y_obs, path=path, obs=obs, state=state, wmap=wmap, xa=xa, Sa=Sa, Se=se if Se is None else Se, lo=lo, hi=hi,
+                 mols=mols, quantity=quantity, stream=stream,
+                 knobs=dict(up=up, down=down, gamma_first=gamma_first, gamma_floor=gamma_floor, gamma_max=gamma_max, conv=conv))
+        with t.cuda.stream(s):
+            L["x_cur"].copy_(xa if x0 is None else x0)
+            if c0 is None:
+                L["c_cur"].zero_()
+            else:
+                L["c_cur"].copy_(c0)
+            L["gamma"].copy_(t.as_tensor(gamma0, dtype=t.float64).expand(self.nprof))
+            for k in ("J_cur", "done", "n_acc", "n_rej"):
+                L[k].zero_()
+        self.oe_scatter(wmap, L["x_cur"], stream=s)
+        return L
+
+    def lm_iterate(self, L: dict, first=False, last=False) -> dict:
+        """One iteration of retrieve_lm on the loop state of lm_start, six steps on one stream with no host branch on device data:
+        obs_jacobian; oe_step_lm (first: its cost becomes J_cur); the trial x_new scattered into the batch - x_cur instead where it
+        leaves the box or the profile is done; obs; the decision; x_cur scattered.  After one warm call a second allocates nothing on
+        the device, and a graph capture of the call replays into the same tensors.  Returns the tensors of this iteration (jac, step, y)."""
+        t = self.torch
+        s = L["stream"] if L["stream"] is not None else t.cuda.current_stream(self.dev)   # (None: the stream current at this call)
+        jac = self.obs_jacobian(L["path"], L["obs"], mols=L["mols"], quantity=L["quantity"], stream=s)
+        if "map" not in L:
+            L["map"] = _oe_map_of(L["state"], self.lm, jac["vars"].numpy())
+        step = self.oe_step_lm(jac, L["map"], L["y_obs"], L["x_cur"], L["xa"], L["Sa"], L["Se"], gamma=L["gamma"], c=L["c_cur"], stream=s)
+        if first:
+            with t.cuda.stream(s):
+                L["J_cur"].copy_(step["cost"])
+        self.oe_scatter(L["wmap"], step["x_new"], x_fallback=L["x_cur"], done=L["done"], lo=L["lo"], hi=L["hi"], trial_ok=L["trial_ok"], stream=s)
+        y = self.obs(L["path"], L["obs"], quantity=L["quantity"], stream=s)
+        self.oe_accept(y, L["y_obs"], L["Se"], step["x_new"], step["c_new"], L["xa"], step["status"], L["trial_ok"], L, last=last, stream=s,
+                       **L["knobs"])
+        self.oe_scatter(L["wmap"], L["x_cur"], stream=s)
+        return dict(jac=jac, step=step, y=y)
+
+    def retrieve_lm(self, y_obs, path, obs: int, state, xa, Sa, se=None, Se=None, maxit=10, gamma0=0.0, up=10.0, down=0.5, gamma_first=1.0,
+                    gamma_floor=1e-3, gamma_max=1e8, conv=0.01, lo=None, hi=None, x0=None, c0=None, mols=None, quantity="tb", diagnostics=(),
+                    keep=False, stream=None) -> dict:
+        """An adaptive optimal-estimation retrieval on the resident batch: up to maxit Levenberg-Marquardt iterations in which every
+        profile accepts or rejects its own trial step, adapts its own gamma and stops on its own, all on the device (lm_iterate).  The
+        cost J = chi2 + (x - xa)^T Sa^-1 (x - xa) is evaluated through the dual vector c = Sa^-1 (x - xa) that the iterate carries.
+        state, y_obs, xa, Sa, se / Se, mols, quantity as retrieve (the same refusals).  The loop starts at xa (c = 0), or at x0 with the
+        caller's c0 = Sa^-1 (x0 - xa); gamma0 a scalar or [nprof].  A step is accepted where the trial lies inside [lo, hi] ([nstate]
+        or [nprof, nstate] tensors, either may be None), J at the trial is finite and J does not rise: gamma <- gamma down (0 below
+        gamma_floor), and the profile has converged (done 1) where J fell by no more than conv x nmeas.  Otherwise gamma <- max(gamma up,
+        gamma_first), and the profile stalls (done 4) beyond gamma_max.  done 2: the step itself failed; 3: out of iterations.
+        Returns x (the last accepted iterate - what the batch holds), J, gamma, done, n_acc, n_rej [nprof], J_history [maxit + 1, nprof],
+        (x, J, gamma, done, n_acc and n_rej ARE the loop's cached buffers: the next retrieve_lm or lm_start of the same shape on this batch
+        overwrites them - clone what you keep)
+        and from one undamped oe_step_full at x: post_var, avk_diag, chi2, status and the diagnostics asked for (names of oe_step_full's
+        `want`).  keep=True: kept, per iteration the clones retrieve keeps plus c, c_new, cost, y_trial, status, the loop state before
+        (gamma, J, done) and after (gamma_after, J_after, done_after, n_acc, n_rej, x_after, trial_ok) and the batch's T, TZ, WKL, CLW and
+        tmpsfc after the iteration."""
+        diagnostics = _oe_want(diagnostics)
+        _lm_check(se, Se, x0, c0)
+        if int(maxit) < 1:
+            raise ValueError("retrieve_lm: maxit must be >= 1")
+        t = self.torch
+        L = self.lm_start(y_obs, path, obs, state, xa, Sa, se=se, Se=Se, gamma0=gamma0, up=up, down=down, gamma_first=gamma_first,
+                          gamma_floor=gamma_floor, gamma_max=gamma_max, conv=conv, lo=lo, hi=hi, x0=x0, c0=c0, mols=mols, quantity=quantity,
+                          stream=stream)
+        s = stream if stream is not None else t.cuda.current_stream(self.dev)
+        with t.cuda.stream(s):
+            hist = t.zeros(int(maxit) + 1, self.nprof, dtype=t.float64, device=self.dev)
+            kept = []
+            for it in range(int(maxit)):
+                before = {k: L[k].clone() for k in ("gamma", "J_cur", "done", "x_cur", "c_cur")} if keep else None
+                r = self.lm_iterate(L, first=it == 0, last=it + 1 == int(maxit))
+                if it == 0:
+                    hist[0].copy_(r["step"]["cost"])
+                    if keep:
+                        before["J_cur"] = r["step"]["cost"].clone()
+                hist[it + 1].copy_(L["J_cur"])
+                if keep:
+                    kept.append(dict({k: r["jac"][k].clone() for k in ("y", "k_t", "k_tz", "k_w", "k_clw", "k_sfc")}, x=before["x_cur"], c=before["c_cur"],
+                                     gamma=before["gamma"], J=before["J_cur"], done=before["done"],
+                                     **{k: r["step"][k].clone() for k in ("x_new", "c_new", "cost", "status")}, y_trial=r["y"].clone(),
+                                     **{k + "_after": L[k].clone() for k in ("gamma", "done")}, J_after=L["J_cur"].clone(), x_after=L["x_cur"].clone(),
+                                     **{k: L[k].clone() for k in ("n_acc", "n_rej", "trial_ok")},
+                                     **{k: getattr(self, k).clone() for k in ("T", "TZ", "WKL", "CLW", "tmpsfc")}))
+            # the posterior belongs to the undamped problem at the final iterate: that call's x_new is discarded
+            jac = self.obs_jacobian(L["path"], obs, mols=L["mols"], quantity=quantity, stream=s)
+            fin = self.oe_step_full(jac, L["map"], y_obs, L["x_cur"], xa, Sa, L["Se"], gamma=None, want=diagnostics, stream=s)
+        out = dict({k: fin[k] for k in ("post_var", "avk_diag", "chi2", "status") + diagnostics}, x=L["x_cur"], J=L["J_cur"], gamma=L["gamma"],
+                   done=L["done"], n_acc=L["n_acc"], n_rej=L["n_rej"], J_history=hist)
         if keep:
             out["kept"] = kept
         return out

@@ -103,6 +103,10 @@ struct Ctx {
     // monortm_hip_oe_step_full_dev asked for dofs without avk_diag: the diagonal that the kernel sums, [nprof][nstate]
     void *oe_diag = nullptr;
     size_t oe_diag_elems = 0;
+    // monortm_hip_oe_scatter_dev (section 3.15): the write map on the device and the host copy it was uploaded from, kept like the state map
+    void *oe_wmap = nullptr;
+    size_t oe_wmap_ints = 0;
+    std::vector<int> oe_wmap_host;
     // measurement operators (monortm_hip_obs_create): the device tables of up to kMaxObs operators, checked on
     // the host when they were created - the kernel never sees an unchecked index, and a call that takes a handle copies nothing
     struct Obs {
@@ -1227,6 +1231,7 @@ void monortm_hip_finalize(void *ctx) {
     if (c->oe_ws) hipFree(c->oe_ws);
     if (c->oe_map) hipFree(c->oe_map);
     if (c->oe_diag) hipFree(c->oe_diag);
+    if (c->oe_wmap) hipFree(c->oe_wmap);
     for (auto &ob : c->obs)
         if (ob.dev) hipFree(ob.dev);
     for (int i = 0; i < 12; i++)
@@ -2783,15 +2788,18 @@ int oe_check_kind(Ctx *c, int se_kind) {
     return MONORTM_OK;
 }
 
-// both device entries: se is [nmeas] (se_kind 0) or Se [nmeas][nmeas] (1); gain_t, avk, post_cov, dofs null for monortm_hip_oe_step_dev
+// the device entries: se is [nmeas] (se_kind 0) or Se [nmeas][nmeas] (1); gain_t, avk, post_cov, dofs null for monortm_hip_oe_step_dev;
+// cdual, c_new, cost null for it and for monortm_hip_oe_step_full_dev
 int oe_step_dev_impl(Ctx *c, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind, const int *state_row,
                      const void *const K[5], const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa, int sa_per_profile,
                      const void *se, int se_kind, int se_per_profile, const void *gamma, void *x_new, void *post_var, void *avk_diag,
-                     void *chi2, int *status, void *gain_t, void *avk, void *post_cov, void *dofs, void *stream) {
+                     void *chi2, int *status, void *gain_t, void *avk, void *post_cov, void *dofs, const void *cdual, void *c_new, void *cost,
+                     void *stream) {
     if (!c->shards.empty()) return multi_only_host(c);
     if (int rc = oe_check(c, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, sa_per_profile, se_per_profile)) return rc;
     if (int rc = oe_check_kind(c, se_kind)) return rc;
     if (!Y || !y_obs || !x || !xa || !Sa || !se || !x_new || !status) { c->err = "null array argument"; return MONORTM_EARG; }
+    if (cdual && cdual == c_new) { c->err = "c_new must not be c itself (the cost reads c behind the stores to c_new)"; return MONORTM_EARG; }
     if (int rcd = check_device(c)) return rcd;
     hipStream_t s = (hipStream_t)stream;
     const int nmeas = nview * nchan;
@@ -2827,6 +2835,7 @@ int oe_step_dev_impl(Ctx *c, int nprof, int nview, int nchan, int nlay_max, int 
     a.x_new = (double *)x_new; a.post_var = (double *)post_var; a.avk_diag = (double *)avk_diag; a.chi2 = (double *)chi2; a.status = status;
     a.ws = static_cast<double *>(c->oe_ws);
     a.se_kind = se_kind; a.gain_t = (double *)gain_t; a.dofs = (double *)dofs;
+    a.c = (const double *)cdual; a.c_new = (double *)c_new; a.cost = (double *)cost;
     HIPCHK(c, launch_oe_step(a, s));
     OeCovArgs v{};
     v.nprof = nprof; v.nmeas = nmeas; v.nstate = nstate; v.sa_per_profile = sa_per_profile;
@@ -2848,7 +2857,8 @@ int monortm_hip_oe_step_dev(void *ctx, int nprof, int nview, int nchan, int nlay
     if (!c) return null_ctx();
     const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
     return oe_step_dev_impl(c, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, Y, y_obs, x, xa, Sa, sa_per_profile, se, 0,
-                            se_per_profile, gamma, x_new, post_var, avk_diag, chi2, status, nullptr, nullptr, nullptr, nullptr, stream);
+                            se_per_profile, gamma, x_new, post_var, avk_diag, chi2, status, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            stream);
 }
 
 int monortm_hip_oe_step_full_dev(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
@@ -2861,7 +2871,8 @@ int monortm_hip_oe_step_full_dev(void *ctx, int nprof, int nview, int nchan, int
     if (!c) return null_ctx();
     const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
     return oe_step_dev_impl(c, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, Y, y_obs, x, xa, Sa, sa_per_profile, Se,
-                            se_kind, se_per_profile, gamma, x_new, post_var, avk_diag, chi2, status, gain_t, avk, post_cov, dofs, stream);
+                            se_kind, se_per_profile, gamma, x_new, post_var, avk_diag, chi2, status, gain_t, avk, post_cov, dofs, nullptr, nullptr, nullptr,
+                            stream);
 }
 
 int monortm_hip_oe_step(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
@@ -2920,6 +2931,156 @@ int monortm_hip_oe_step_full(void *ctx, int nprof, int nview, int nchan, int nla
                                             dv[i_se], se_kind, se_per_profile, dv[i_g], dv[o_x], dv[o_pv], dv[o_av], dv[o_c2], (int *)dv[o_st],
                                             dv[o_gn], dv[o_ak], dv[o_pc], dv[o_df], s->hs);
     });
+}
+
+// ---- the adaptive retrieval loop -------------------------------------------------------------------------
+int monortm_hip_oe_step_lm_dev(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                               const int *state_row, const void *K_T, const void *K_TZ, const void *K_W, const void *K_CLW, const void *K_SFC,
+                               const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa, int sa_per_profile,
+                               const void *Se, int se_kind, int se_per_profile, const void *gamma, void *x_new, void *post_var,
+                               void *avk_diag, void *chi2, int *status, void *gain_t, void *avk, void *post_cov, void *dofs, const void *c,
+                               void *c_new, void *cost, void *stream) {
+    Ctx *cx = static_cast<Ctx *>(ctx);
+    if (!cx) return null_ctx();
+    const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
+    return oe_step_dev_impl(cx, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, Y, y_obs, x, xa, Sa, sa_per_profile, Se,
+                            se_kind, se_per_profile, gamma, x_new, post_var, avk_diag, chi2, status, gain_t, avk, post_cov, dofs, c, c_new, cost,
+                            stream);
+}
+
+int monortm_hip_oe_step_lm(void *ctx, int nprof, int nview, int nchan, int nlay_max, int njac, int nstate, const int *state_kind,
+                           const int *state_row, const void *K_T, const void *K_TZ, const void *K_W, const void *K_CLW, const void *K_SFC,
+                           const void *Y, const void *y_obs, const void *x, const void *xa, const void *Sa, int sa_per_profile,
+                           const void *Se, int se_kind, int se_per_profile, const void *gamma, void *x_new, void *post_var, void *avk_diag,
+                           void *chi2, int *status, void *gain_t, void *avk, void *post_cov, void *dofs, const void *c, void *c_new,
+                           void *cost) {
+    Ctx *cx = static_cast<Ctx *>(ctx);
+    if (!cx) return null_ctx();
+    DeviceGuard guard;
+    const void *const K[5] = {K_T, K_TZ, K_W, K_CLW, K_SFC};
+    if (int rc = oe_check(cx, nprof, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, K, sa_per_profile, se_per_profile)) return rc;
+    if (int rc = oe_check_kind(cx, se_kind)) return rc;
+    if (!Y || !y_obs || !x || !xa || !Sa || !Se || !x_new || !status) { cx->err = "null array argument"; return MONORTM_EARG; }
+    if (c && c == c_new) { cx->err = "c_new must not be c itself (the cost reads c behind the stores to c_new)"; return MONORTM_EARG; }
+    long long rows[5];
+    oe_rows(nlay_max, njac, rows);
+    const size_t d = 8, m = (size_t)nview * nchan, y = m * d, n = (size_t)nstate * d, e = se_kind ? y * m : y;
+    HostCall hc(8);
+    int i_K[5];
+    for (int k = 0; k < 5; k++) i_K[k] = hc.in(K[k], y * rows[k]);
+    const int i_Y = hc.in(Y, y), i_yo = hc.in(y_obs, y), i_x = hc.in(x, n), i_xa = hc.in(xa, n),
+              i_Sa = sa_per_profile ? hc.in(Sa, n * nstate) : hc.in_shared(Sa, n * nstate), i_se = se_per_profile ? hc.in(Se, e) : hc.in_shared(Se, e),
+              i_g = hc.in(gamma, d), i_c = hc.in(c, n);
+    const int o_x = hc.out(x_new, n), o_pv = hc.out(post_var, n), o_av = hc.out(avk_diag, n), o_c2 = hc.out(chi2, d), o_st = hc.out(status, sizeof(int)),
+              o_gn = hc.out(gain_t, m * n), o_ak = hc.out(avk, n * nstate), o_pc = hc.out(post_cov, n * nstate), o_df = hc.out(dofs, d),
+              o_cn = hc.out(c_new, n), o_J = hc.out(cost, d);
+    return hc.run(cx, nprof, [&](Ctx *s, int, int np, char *const *dv) {
+        return monortm_hip_oe_step_lm_dev(s, np, nview, nchan, nlay_max, njac, nstate, state_kind, state_row, dv[i_K[0]], dv[i_K[1]], dv[i_K[2]],
+                                          dv[i_K[3]], dv[i_K[4]], dv[i_Y], dv[i_yo], dv[i_x], dv[i_xa], dv[i_Sa], sa_per_profile, dv[i_se],
+                                          se_kind, se_per_profile, dv[i_g], dv[o_x], dv[o_pv], dv[o_av], dv[o_c2], (int *)dv[o_st], dv[o_gn],
+                                          dv[o_ak], dv[o_pc], dv[o_df], dv[i_c], dv[o_cn], dv[o_J], s->hs);
+    });
+}
+
+int monortm_hip_oe_scatter_dev(void *ctx, int nprof, int nstate, const int *map_kind, const int *map_index, const int *map_mol,
+                               const void *x_src, const void *x_fallback, const int *done, const void *lo, const void *hi,
+                               int box_per_profile, const int *nlay, int nlay_max, int nmol, void *T, long long t_stride, void *TZ,
+                               long long tz_stride, void *WKL, long long wkl_stride, void *CLW, long long clw_stride, void *tmpsfc_a,
+                               void *tmpsfc_b, int *trial_ok, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (c->real_kind != 8) { c->err = "monortm_hip_oe_scatter_dev needs a real_kind = 8 context"; return MONORTM_EUNSUPPORTED; }
+    if (nprof < 1 || nlay_max < 1 || nlay_max > 603 || nmol < 0 || nmol > MXMOL) { c->err = "bad nprof/nlay_max/nmol"; return MONORTM_EARG; }
+    if (nstate < 1 || nstate > kOeMaxState) { c->err = "nstate outside 1.." + std::to_string(kOeMaxState); return MONORTM_EARG; }
+    if (box_per_profile != 0 && box_per_profile != 1) { c->err = "box_per_profile must be 0 or 1"; return MONORTM_EARG; }
+    if (!map_kind || !map_index || !map_mol) { c->err = "null write map"; return MONORTM_EARG; }
+    if (!x_src || !nlay) { c->err = "null array argument"; return MONORTM_EARG; }
+    // every store the kernel can make, checked here: the array is given, the element lies inside a profile's stride, and no two
+    // written columns share a target (the kernel's stores would race)
+    const void *arr[4] = {T, TZ, WKL, CLW};
+    const long long stride[4] = {t_stride, tz_stride, wkl_stride, clw_stride};
+    static const char *const names[4] = {"T", "TZ", "WKL", "CLW"};
+    std::vector<int> map(3 * (size_t)nstate);
+    std::vector<long long> targets;
+    for (int i = 0; i < nstate; i++) {
+        const int k = map_kind[i], ix = map_index[i];
+        const std::string who = "write map, column " + std::to_string(i);
+        if (k < -1 || k > 4) { c->err = who + ": kind " + std::to_string(k) + " outside -1..4"; return MONORTM_EARG; }
+        long long off = 0;
+        if (k == -1) {
+            if (ix < -1 || ix > nlay_max) { c->err = who + ": index outside -1.." + std::to_string(nlay_max); return MONORTM_EARG; }
+        } else if (k == 4) {
+            if (!tmpsfc_a && !tmpsfc_b) { c->err = who + " writes TMPSFC, and both pointers are null"; return MONORTM_EARG; }
+        } else {
+            if (ix < 0 || ix >= nlay_max + (k == 1)) { c->err = who + ": index " + std::to_string(ix) + " outside " + names[k]; return MONORTM_EARG; }
+            if (k == 2 && (map_mol[i] < 0 || map_mol[i] >= nmol)) { c->err = who + ": molecule outside 0.." + std::to_string(nmol - 1); return MONORTM_EARG; }
+            off = k == 2 ? (long long)ix * nmol + map_mol[i] : ix;
+            if (!arr[k]) { c->err = who + " writes " + names[k] + ", which is null"; return MONORTM_EARG; }
+            if (off >= stride[k]) { c->err = who + ": element " + std::to_string(off) + " outside the stride of " + names[k]; return MONORTM_EARG; }
+        }
+        if (k >= 0) targets.push_back(((long long)k << 40) + off);
+        map[i] = k; map[nstate + i] = ix; map[2 * (size_t)nstate + i] = k == 2 ? map_mol[i] : 0;
+    }
+    std::sort(targets.begin(), targets.end());
+    if (std::adjacent_find(targets.begin(), targets.end()) != targets.end()) {
+        c->err = "write map: two written columns share a target (give the earlier one kind -1)";
+        return MONORTM_EARG;
+    }
+    if (int rcd = check_device(c)) return rcd;
+    hipStream_t s = (hipStream_t)stream;
+    if (map != c->oe_wmap_host) {   // as the state map of monortm_hip_oe_step_dev travels
+        HIPCHK(c, hipStreamSynchronize(s));
+        c->oe_wmap_host.clear();
+        HIPCHK(c, grow(&c->oe_wmap, &c->oe_wmap_ints, map.size(), sizeof(int)));
+        HIPCHK(c, hipMemcpy(c->oe_wmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+        c->oe_wmap_host = map;
+    }
+    OeScatterArgs a{};
+    a.nprof = nprof; a.nstate = nstate; a.nmol = nmol; a.box_per_profile = box_per_profile;
+    a.wmap = static_cast<const int *>(c->oe_wmap); a.nlay = nlay; a.done = done;
+    a.x_src = (const double *)x_src; a.x_fallback = (const double *)x_fallback; a.lo = (const double *)lo; a.hi = (const double *)hi;
+    a.T = (double *)T; a.TZ = (double *)TZ; a.WKL = (double *)WKL; a.CLW = (double *)CLW; a.tmpsfc_a = (double *)tmpsfc_a; a.tmpsfc_b = (double *)tmpsfc_b;
+    a.t_stride = (size_t)t_stride; a.tz_stride = (size_t)tz_stride; a.wkl_stride = (size_t)wkl_stride; a.clw_stride = (size_t)clw_stride;
+    a.trial_ok = trial_ok;
+    HIPCHK(c, launch_oe_scatter(a, s));
+    return MONORTM_OK;
+}
+
+int monortm_hip_oe_accept_dev(void *ctx, int nprof, int nmeas, int nstate, const void *Y_trial, const void *y_obs, const void *Se,
+                              int se_kind, int se_per_profile, const void *x_trial, const void *c_trial, const void *xa,
+                              const int *step_status, const int *trial_ok, double up, double down, double gamma_first, double gamma_floor,
+                              double gamma_max, double conv, int last, void *x_cur, void *c_cur, void *J_cur, void *gamma, int *done,
+                              int *n_acc, int *n_rej, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return null_ctx();
+    if (!c->shards.empty()) return multi_only_host(c);
+    if (c->real_kind != 8) { c->err = "monortm_hip_oe_accept_dev needs a real_kind = 8 context"; return MONORTM_EUNSUPPORTED; }
+    if (nprof < 1) { c->err = "bad nprof"; return MONORTM_EARG; }
+    if (nmeas < 1 || nmeas > kOeMaxMeas) { c->err = "nmeas outside 1.." + std::to_string(kOeMaxMeas); return MONORTM_EARG; }
+    if (nstate < 1 || nstate > kOeMaxState) { c->err = "nstate outside 1.." + std::to_string(kOeMaxState); return MONORTM_EARG; }
+    if (int rc = oe_check_kind(c, se_kind)) return rc;
+    if (se_per_profile != 0 && se_per_profile != 1) { c->err = "se_per_profile must be 0 or 1"; return MONORTM_EARG; }
+    if (any_null({Y_trial, y_obs, Se, x_trial, c_trial, xa, step_status, trial_ok, x_cur, c_cur, J_cur, gamma, done, n_acc, n_rej})) {
+        c->err = "null array argument";
+        return MONORTM_EARG;
+    }
+    // (written so that a NaN fails every test)
+    if (!(up >= 1.) || !(down >= 0. && down <= 1.) || !(gamma_first > 0.) || !(gamma_floor >= 0.) || !(gamma_max >= 0.) || !(conv >= 0.) ||
+        !std::isfinite(up) || !std::isfinite(gamma_first)) {
+        c->err = "needs up >= 1, 0 <= down <= 1, gamma_first > 0, gamma_floor >= 0, gamma_max >= 0, conv >= 0";
+        return MONORTM_EARG;
+    }
+    if (int rcd = check_device(c)) return rcd;
+    OeAcceptArgs a{};
+    a.nprof = nprof; a.nmeas = nmeas; a.nstate = nstate; a.se_kind = se_kind; a.se_per_profile = se_per_profile; a.last = last != 0;
+    a.Y_trial = (const double *)Y_trial; a.y_obs = (const double *)y_obs; a.se = (const double *)Se; a.x_trial = (const double *)x_trial;
+    a.c_trial = (const double *)c_trial; a.xa = (const double *)xa; a.step_status = step_status; a.trial_ok = trial_ok;
+    a.up = up; a.down = down; a.gamma_first = gamma_first; a.gamma_floor = gamma_floor; a.gamma_max = gamma_max; a.conv = conv;
+    a.x_cur = (double *)x_cur; a.c_cur = (double *)c_cur; a.J_cur = (double *)J_cur; a.gamma = (double *)gamma;
+    a.done = done; a.n_acc = n_acc; a.n_rej = n_rej;
+    HIPCHK(c, launch_oe_accept(a, (hipStream_t)stream));
+    return MONORTM_OK;
 }
 
 }  // extern "C"

@@ -325,6 +325,36 @@ struct OeArgs {
     double *ws;
     int se_kind;
     double *gain_t, *dofs;
+    // the LM entries (section 3.15): any of the three not null selects the DUAL instantiations.  c [nprof][nstate] or null (0), the
+    // dual vector Sa^-1 (x - xa) of the iterate; c_new [nprof][nstate] (not c itself) and cost [nprof] may be null
+    const double *c;
+    double *c_new, *cost;
+};
+
+// oe_scatter_kernel (section 3.15): a state vector written into the resident arrays through a write map on the device, [3][nstate]
+// ints: kind (0 T, 1 TZ, 2 WKL, 3 CLW, 4 TMPSFC, -1 checked but not written), index (layer or level; a column of kind -1 is live where
+// index < nlay[p]: the host stores level - 1 for a level and -1 for TMPSFC), mol (0-based, WKL only).  All of it is checked on the host:
+// index < the rows of its array, mol < nmol, no two written columns with the same target.  Strides are elements per profile; WKL is
+// [nprof][..][nmol].  lo, hi [nstate] (x nprof with box_per_profile) or null; x_fallback, done, trial_ok, tmpsfc_a / _b may be null.
+struct OeScatterArgs {
+    int nprof, nstate, nmol, box_per_profile;
+    const int *wmap, *nlay, *done;
+    const double *x_src, *x_fallback, *lo, *hi;
+    double *T, *TZ, *WKL, *CLW, *tmpsfc_a, *tmpsfc_b;
+    size_t t_stride, tz_stride, wkl_stride, clw_stride;
+    int *trial_ok;
+};
+
+// oe_accept_kernel (section 3.15): the decision on a trial step, per profile.  Y_trial, y_obs [nprof][nmeas]; se as in OeArgs (se_kind,
+// se_per_profile); x_trial, c_trial, xa [nprof][nstate]; the loop state x_cur, c_cur [nprof][nstate], J_cur, gamma [nprof] and done,
+// n_acc, n_rej int [nprof] are updated in place.
+struct OeAcceptArgs {
+    int nprof, nmeas, nstate, se_kind, se_per_profile, last;
+    const double *Y_trial, *y_obs, *se, *x_trial, *c_trial, *xa;
+    const int *step_status, *trial_ok;
+    double up, down, gamma_first, gamma_floor, gamma_max, conv;
+    double *x_cur, *c_cur, *J_cur, *gamma;
+    int *done, *n_acc, *n_rej;
 };
 
 // oe_cov_kernel: avk = a^T b and post_cov = g Sa - a^T a, [nprof][nstate][nstate] each (one of them may be null), from the workspace
@@ -549,5 +579,8 @@ void launch_rtm_obs(const RtmObsArgs &a, int out_kind, hipStream_t s);
 hipError_t launch_oe_step(const OeArgs &a, hipStream_t s);
 // oe_kernel.hip: grid (output tiles, profiles); no launch when both matrices are null
 hipError_t launch_oe_cov(const OeCovArgs &a, hipStream_t s);
+// oe_kernel.hip: one launch each, one workgroup per profile (the accept kernel raises its bound on dynamic LDS like the step)
+hipError_t launch_oe_scatter(const OeScatterArgs &a, hipStream_t s);
+hipError_t launch_oe_accept(const OeAcceptArgs &a, hipStream_t s);
 
 }  // namespace monortm_dev

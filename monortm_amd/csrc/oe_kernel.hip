@@ -33,6 +33,14 @@
 // which fall into different bank pairs without the padding the [j][OE_ITP] tiles of phase 2 need.  Every element is one thread's sum in
 // ascending k, formed with the fused multiply-adds phase 4 compiles to: diag(post_cov) and diag(avk) are post_var and avk_diag bit for
 // bit.  post_cov is computed on and below the diagonal tiles and stored with its mirror image; Sa is read from its lower triangle.
+//
+// The adaptive loop (monortm_hip_oe_step_lm[_dev], monortm_hip_oe_scatter_dev, monortm_hip_oe_accept_dev):
+//   DUAL    the iterate carries c = Sa^-1 (x - xa).  Phase 4 accumulates one more dot product, q_i = b_i . u = (K^T M^-1 r)_i, in the
+//           order of the other three, and stores c_new_i = g (gamma c_i + q_i) = Sa^-1 (x_new - xa)_i; thread 0 stores the cost at x,
+//           chi2 + sum_i c_i (x_i - xa_i), i ascending, behind the barrier of dofs.  A failed profile: c_new = c, cost = 0.  The
+//           instantiations without DUAL compile from the expressions they had, in their order.
+// oe_scatter_kernel writes a state vector into the resident inputs through a write map, after a box test; oe_accept_kernel forms the
+// cost of the trial and decides per profile.  One workgroup per profile each, no atomics.
 #include <algorithm>
 
 #include "device_common.hpp"
@@ -69,7 +77,7 @@ __device__ __forceinline__ void oe_cholesky(double *sM, double *sU, int m, int t
     }
 }
 
-template <bool SEFULL, bool GAIN>
+template <bool SEFULL, bool GAIN, bool DUAL>
 __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
     extern __shared__ __attribute__((aligned(16))) double oe_lds[];
     __shared__ int sBad;
@@ -204,6 +212,7 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
     // ---- 3: Cholesky in place, u = L^-1 r as row m
     oe_cholesky(sM, sU, m, tid, tx, ty, &sBad);
     const bool bad = sBad != 0;
+    double c2cost = 0.;   // DUAL, thread 0: chi2 again, for the cost
     if (tid == 0) {
         double c2 = 0.;
         if constexpr (SEFULL) {
@@ -217,6 +226,7 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
         }
         if (a.chi2) a.chi2[p] = c2;
         a.status[p] = bad ? 1 : 0;
+        if constexpr (DUAL) c2cost = c2;
     }
 
     // ---- 4: the states
@@ -226,9 +236,12 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
             a.x_new[o] = x[i];
             if (a.post_var) a.post_var[o] = 0.;
             if (a.avk_diag) a.avk_diag[o] = 0.;
+            if constexpr (DUAL) {
+                if (a.c_new) a.c_new[o] = a.c ? a.c[o] : 0.;
+            }
             continue;
         }
-        double pv = 0., av = 0., dx = 0.;
+        double pv = 0., av = 0., dx = 0., q = 0.;   // (q: DUAL only)
         for (int kb = 0; kb < m; kb += OE_KB) {
             double aw[OE_KB], ab[OE_KB];
             int row[OE_KB];
@@ -265,12 +278,17 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
                     pv += aw[r] * aw[r];
                     av += aw[r] * ab[r];
                     dx += aw[r] * sU[kb + r];
+                    if constexpr (DUAL) q += ab[r] * sU[kb + r];
                 }
             }
         }
         a.x_new[o] = x[i] + (xa[i] - x[i]) * ginv + dx;
         if (a.post_var) a.post_var[o] = Sa[(size_t)i * n + i] * ginv - pv;
         if (a.avk_diag) a.avk_diag[o] = av;
+        if constexpr (DUAL) {
+            // c_new = Sa^-1 (x_new - xa) = g (gamma c + K^T M^-1 r), K^T M^-1 r = b . u
+            if (a.c_new) a.c_new[o] = ginv * ((a.c ? gam * a.c[o] : 0.) + q);
+        }
     }
 
     // ---- 5: the gain, G^T = L^-T a: back substitution from the last row up, OE_KB rows at a time (thread i reads the a[k][i] and the
@@ -307,12 +325,23 @@ __global__ __launch_bounds__(OE_THREADS) void oe_step_kernel(OeArgs a) {
     }
 
     // ---- the degrees of freedom for signal: avk_diag (not null with dofs: the entry sees to that) summed by one thread, i ascending
-    if (a.dofs) {
+    // DUAL: the cost of the iterate the step started from, chi2 + c . (x - xa), behind the same barrier, i ascending
+    if (a.dofs || (DUAL && a.cost)) {
         __syncthreads();   // the block's stores to avk_diag are visible to thread 0
         if (tid == 0) {
-            double sum = 0.;
-            for (int i = 0; i < n; i++) sum += a.avk_diag[(size_t)p * n + i];
-            a.dofs[p] = sum;
+            if (a.dofs) {
+                double sum = 0.;
+                for (int i = 0; i < n; i++) sum += a.avk_diag[(size_t)p * n + i];
+                a.dofs[p] = sum;
+            }
+            if constexpr (DUAL) {
+                if (a.cost) {
+                    double sum = 0.;
+                    if (a.c && !bad)
+                        for (int i = 0; i < n; i++) sum += a.c[(size_t)p * n + i] * (x[i] - xa[i]);
+                    a.cost[p] = bad ? 0. : c2cost + sum;
+                }
+            }
         }
     }
 }
@@ -418,6 +447,127 @@ __global__ __launch_bounds__(OE_THREADS) void oe_cov_kernel(OeCovArgs a, int p0)
         }
 }
 
+// ---- the adaptive loop ---------------------------------------------------------------------------------------
+// A state vector into the resident arrays.  Pass 1: ok = every live element of x_src is finite and inside [lo, hi], through one LDS flag
+// (every thread that finds a violation stores the same 0).  Pass 2: the live elements of the source - x_fallback where it is given and
+// the trial is not ok or the profile is done, x_src otherwise - are written, WKL as exp(x); nothing else is touched.  A column's target
+// is its own (the host refuses a map with two written columns on one target): no two threads store to one address.
+__global__ __launch_bounds__(OE_THREADS) void oe_scatter_kernel(OeScatterArgs a) {
+    __shared__ int sOk;
+    const int p = blockIdx.x, tid = threadIdx.x, n = a.nstate;
+    const int *kind = a.wmap, *index = a.wmap + n, *mol = a.wmap + 2 * n;
+    const int nl = a.nlay[p];
+    const double *xs = a.x_src + (size_t)p * n;
+    const double *lo = a.lo ? a.lo + (a.box_per_profile ? (size_t)p * n : 0) : nullptr;
+    const double *hi = a.hi ? a.hi + (a.box_per_profile ? (size_t)p * n : 0) : nullptr;
+    if (tid == 0) sOk = 1;
+    __syncthreads();
+    auto live = [&](int i) {
+        const int k = kind[i];
+        return k == 4 || (k == 1 ? index[i] <= nl : index[i] < nl);
+    };
+    bool out = false;
+    for (int i = tid; i < n; i += OE_THREADS) {
+        if (!live(i)) continue;
+        const double v = xs[i];
+        if (!isfinite(v) || (lo && !(v >= lo[i])) || (hi && !(v <= hi[i]))) out = true;
+    }
+    if (out) sOk = 0;
+    __syncthreads();
+    const bool ok = sOk != 0;
+    if (tid == 0 && a.trial_ok) a.trial_ok[p] = ok ? 1 : 0;
+    const bool fall = a.x_fallback && (!ok || (a.done && a.done[p] != 0));
+    const double *src = fall ? a.x_fallback + (size_t)p * n : xs;
+    for (int i = tid; i < n; i += OE_THREADS) {
+        const int k = kind[i];
+        if (k < 0 || !live(i)) continue;
+        const double v = src[i];
+        if (k == 0) a.T[(size_t)p * a.t_stride + index[i]] = v;
+        else if (k == 1) a.TZ[(size_t)p * a.tz_stride + index[i]] = v;
+        else if (k == 2) a.WKL[(size_t)p * a.wkl_stride + (size_t)index[i] * a.nmol + mol[i]] = exp(v);
+        else if (k == 3) a.CLW[(size_t)p * a.clw_stride + index[i]] = v;
+        else {
+            if (a.tmpsfc_a) a.tmpsfc_a[p] = v;
+            if (a.tmpsfc_b) a.tmpsfc_b[p] = v;
+        }
+    }
+}
+
+// The decision on a trial step.  J_trial = chi2(Y_trial) + sum_i c_trial_i (x_trial_i - xa_i): chi2 as the step kernel forms it (thread
+// 0 in ascending j; SEFULL: the Cholesky of Se in LDS with y - Y_trial as the extra row), the prior sum by thread 0 in ascending i.
+// Thread 0 decides and updates the profile's scalars; the block copies the trial into the iterate where it was accepted.  A profile
+// that is done returns before it has read anything else: nothing of it changes.
+template <bool SEFULL>
+__global__ __launch_bounds__(OE_THREADS) void oe_accept_kernel(OeAcceptArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double oe_lds[];
+    __shared__ int sBad, sAccept;
+    const int p = blockIdx.x, tid = threadIdx.x, m = a.nmeas, n = a.nstate;
+    if (a.done[p] != 0) return;   // (the whole workgroup: no barrier is left waiting)
+    if (a.step_status[p] == 1) {
+        if (tid == 0) a.done[p] = 2;
+        return;
+    }
+    const double *se = a.se + (a.se_per_profile ? (size_t)p * m * (SEFULL ? m : 1) : 0);
+    const double *Y = a.Y_trial + (size_t)p * m, *yo = a.y_obs + (size_t)p * m;
+    const double *xt = a.x_trial + (size_t)p * n, *ct = a.c_trial + (size_t)p * n, *xa = a.xa + (size_t)p * n;
+    if (tid == 0) sBad = 0, sAccept = 0;
+    __syncthreads();
+    if constexpr (SEFULL) {
+        double *sM = oe_lds, *sU = sM + tri(m);
+        for (int e = tid; e < m * m; e += OE_THREADS) {
+            const int j = e / m, jp = e - j * m;
+            if (jp <= j) sM[tri(j) + jp] = se[e];
+        }
+        if (tid < m) sU[tid] = yo[tid] - Y[tid];
+        __syncthreads();
+        oe_cholesky(sM, sU, m, tid, tid & 15, tid >> 4, &sBad);
+    }
+    if (tid == 0) {
+        int done = 0;
+        if (sBad) {
+            done = 2;
+        } else {
+            double c2 = 0.;
+            if constexpr (SEFULL) {
+                const double *sU = oe_lds + tri(m);
+                for (int j = 0; j < m; j++) c2 += sU[j] * sU[j];
+            } else {
+                for (int j = 0; j < m; j++) {
+                    const double dy = yo[j] - Y[j];
+                    c2 += dy * dy / se[j];
+                }
+            }
+            double pr = 0.;
+            for (int i = 0; i < n; i++) pr += ct[i] * (xt[i] - xa[i]);
+            const double Jt = c2 + pr, Jc = a.J_cur[p];
+            double gam = a.gamma[p];
+            if (a.trial_ok[p] != 0 && isfinite(Jt) && Jt <= Jc) {
+                sAccept = 1;
+                a.J_cur[p] = Jt;
+                gam *= a.down;
+                if (gam < a.gamma_floor) gam = 0.;
+                a.n_acc[p]++;
+                if (Jc - Jt <= a.conv * m) done = 1;
+            } else {
+                gam = fmax(gam * a.up, a.gamma_first);
+                a.n_rej[p]++;
+                if (gam > a.gamma_max) done = 4;
+            }
+            a.gamma[p] = gam;
+            if (a.last && done == 0) done = 3;
+        }
+        if (done) a.done[p] = done;
+    }
+    __syncthreads();
+    if (sAccept) {
+        double *xc = a.x_cur + (size_t)p * n, *cc = a.c_cur + (size_t)p * n;
+        for (int i = tid; i < n; i += OE_THREADS) {
+            xc[i] = xt[i];
+            cc[i] = ct[i];
+        }
+    }
+}
+
 }  // namespace
 
 namespace monortm_dev {
@@ -427,20 +577,44 @@ static size_t oe_lds_bytes(int nmeas) {
     return sizeof(double) * (std::max(std::max(m * (m + 1) / 2, 2 * m * OE_ITP), (5 * m + 1) / 2) + m);
 }
 
-template <bool SEFULL, bool GAIN>
+template <bool SEFULL, bool GAIN, bool DUAL>
 static hipError_t launch_oe_step_as(const OeArgs &a, hipStream_t s) {
     const size_t lds = oe_lds_bytes(a.nmeas);
     if (lds > (64u << 10)) {   // m >= 127: beyond the default bound of a launch's dynamic LDS
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(oe_step_kernel<SEFULL, GAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(oe_step_kernel<SEFULL, GAIN, DUAL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((oe_step_kernel<SEFULL, GAIN>), dim3((unsigned)a.nprof), dim3(OE_THREADS), lds, s, a);
+    hipLaunchKernelGGL((oe_step_kernel<SEFULL, GAIN, DUAL>), dim3((unsigned)a.nprof), dim3(OE_THREADS), lds, s, a);
     return hipGetLastError();
 }
 
+template <bool DUAL>
+static hipError_t launch_oe_step_dual(const OeArgs &a, hipStream_t s) {
+    if (a.se_kind) return a.gain_t ? launch_oe_step_as<true, true, DUAL>(a, s) : launch_oe_step_as<true, false, DUAL>(a, s);
+    return a.gain_t ? launch_oe_step_as<false, true, DUAL>(a, s) : launch_oe_step_as<false, false, DUAL>(a, s);
+}
+
 hipError_t launch_oe_step(const OeArgs &a, hipStream_t s) {
-    if (a.se_kind) return a.gain_t ? launch_oe_step_as<true, true>(a, s) : launch_oe_step_as<true, false>(a, s);
-    return a.gain_t ? launch_oe_step_as<false, true>(a, s) : launch_oe_step_as<false, false>(a, s);
+    return a.c || a.c_new || a.cost ? launch_oe_step_dual<true>(a, s) : launch_oe_step_dual<false>(a, s);
+}
+
+hipError_t launch_oe_scatter(const OeScatterArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(oe_scatter_kernel, dim3((unsigned)a.nprof), dim3(OE_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_oe_accept(const OeAcceptArgs &a, hipStream_t s) {
+    if (!a.se_kind) {
+        hipLaunchKernelGGL(oe_accept_kernel<false>, dim3((unsigned)a.nprof), dim3(OE_THREADS), 0, s, a);
+        return hipGetLastError();
+    }
+    const size_t m = (size_t)a.nmeas, lds = sizeof(double) * (m * (m + 1) / 2 + m);   // Se's triangle and y - Y_trial
+    if (lds > (64u << 10)) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(oe_accept_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(oe_accept_kernel<true>, dim3((unsigned)a.nprof), dim3(OE_THREADS), lds, s, a);
+    return hipGetLastError();
 }
 
 template <bool AVK, bool COV>

@@ -1,7 +1,7 @@
 """Time of the optimal-estimation step (monortm_hip_oe_step_dev) on the configs[3] shape
 (bench.build_workload("c4"): 1024 profiles x 64 layers x 50 channels x 500 lines, f64), against what surrounds and what replaces it.
 
-    python tools/oe_bench.py [--calls 20] [--warmup 3] [--full] [--out FILE]
+    python tools/oe_bench.py [--calls 20] [--warmup 3] [--full | --lm] [--out FILE]
 
 Operators of 14 channels (the 50 wavenumbers in runs of 3 or 4) and 1 or 6 views of 4 paths: m = 14 and 84 measurements.  States:
 n = 64 (T of every layer), 130 (T, ln H2O, TMPSFC, EMISS), 200 (T, TZ, ln H2O, 4 layers of CLW, TMPSFC, EMISS, REFLC).  Sa is
@@ -18,6 +18,13 @@ With --full (monortm_hip_oe_step_full_dev; Se = 0.25 exp
   c<n>   the full Se + avk + post_cov + dofs: the second launch, oe_cov_kernel;
   g<n>   the full Se + avk + post_cov + dofs + gain_t: the back substitution on top;
   u<n>   the algebra of c<n> in torch on a gathered K: cholesky, cholesky_solve of W^T, and the two matmul that form A and S_hat.
+With --lm (DeviceBatch.retrieve_lm) nothing of the above: per m and n, on two batches of the same profiles,
+  r<n>   one iteration of DeviceBatch.retrieve (gammas = (0,)): obs_jacobian, oe_step, the write-back in torch ops;
+  l<n>   one DeviceBatch.lm_iterate: obs_jacobian, oe_step_lm, scatter, obs, accept, scatter.
+The states are those retrieve can write back: n = 64 (T), 130 (T, ln H2O, one layer of CLW, TMPSFC), 200 (T, TZ, ln H2O, 6 layers of CLW,
+TMPSFC); xa is what the batch holds, y_obs the forward model there plus noise, so that every iterate stays physical.  Before every
+timed call the loop is restarted at xa (lm_start, outside the events): what is timed is the first iteration, in which all 1024 profiles
+are live; done_n<n> and accepted_rejected_n<n> record the state after the last one.
 Median / min / max / IQR of each, the largest difference of x_new between k and t relative to max |x_new - x|, and the number of
 profiles with status 1.  Prints one JSON line."""
 from __future__ import annotations
@@ -176,12 +183,84 @@ def run_case(api, rt, profs, nview, calls, warmup, full=False):
     return res
 
 
+def lm_specs(lm):
+    L = range(lm)
+    return {64: [("t", L)],
+            130: [("t", L), ("w", "H2O", L), ("clw", [0]), ("tmpsfc",)],
+            200: [("t", L), ("tz", range(lm + 1)), ("w", "H2O", L), ("clw", range(6)), ("tmpsfc",)]}
+
+
+def run_lm_case(api, rt, profs, nview, calls, warmup):
+    """One iteration of the adaptive loop against one iteration of retrieve, interleaved, device events."""
+    import torch
+
+    dbr, dbl = api.DeviceBatch(rt, profs), api.DeviceBatch(rt, profs)
+    dev, lm, nprof, nwn = dbl.dev, dbl.lm, dbl.nprof, dbl.nwn
+    npath = 4 * nview
+    chan = (np.arange(nwn) * NCHAN // nwn).astype(np.int32)
+    wchan = np.array([1.0 / np.sum(chan == c) for c in chan])
+    op = api.ObsOperator(np.arange(0, npath + 1, 4), np.full(npath, 0.25), chan, wchan, nchan=NCHAN)
+    h = rt.obs_create(op)
+    fd = torch.as_tensor(api.plane_parallel_path(np.linspace(0.0, 60.0, npath), lm)).to(dev).unsqueeze(0).expand(nprof, -1, -1).contiguous()
+    m = nview * NCHAN
+    rng = np.random.default_rng(5)
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    y_obs = dbl.obs(fd, h).clone() + up(rng.normal(0.0, 0.5, (nprof, nview, NCHAN)))
+    se = up(np.full(m, 0.25))
+    sigma = dict(t=1.0, tz=1.0, w=0.1, clw=1e-4, tmpsfc=1.0)
+    res = dict(nprof=nprof, nlay=lm, nwn=nwn, npath=npath, nview=nview, nchan=NCHAN, nmeas=m)
+    for n, spec in lm_specs(lm).items():
+        items = api._oe_items(spec, lm)
+        assert len(items) == n
+        Sa, o = np.zeros((n, n)), 0
+        for it in spec:
+            sz = len(it[-1]) if len(it) > 1 else 1
+            i = np.arange(sz)
+            Sa[o:o + sz, o:o + sz] = sigma[it[0]] ** 2 * np.exp(-np.abs(i[:, None] - i[None, :]) / 4.0)
+            o += sz
+        res_of = dict(t=dbl.T, tz=dbl.TZ, clw=dbl.CLW)
+        xa = torch.stack([dbl.tmpsfc0 if name == "tmpsfc" else torch.log(dbl.WKL[:, k, code - 1]) if name == "w" else res_of[name][:, k]
+                          for name, code, k in items], dim=1).contiguous()
+        Sa = up(Sa)
+        # the loop is restarted at xa before every timed iteration, outside the events: every profile is live in what is timed (the
+        # decision kernel of a finished profile returns at its first load, and its scatter takes the fallback path)
+        start = lambda: dbl.lm_start(y_obs, fd, h, spec, xa, Sa, se=se)  # noqa: E731
+        L = start()
+        variants = {f"r{n}": lambda spec=spec, xa=xa, Sa=Sa: dbr.retrieve(y_obs, fd, h, spec, xa, Sa, se, gammas=(0,)),
+                    f"l{n}": lambda L=L: dbl.lm_iterate(L, first=True)}
+        for _ in range(warmup):
+            for f in variants.values():
+                start()
+                f()
+        torch.cuda.synchronize()
+        dbr.check()
+        dbl.check()
+        ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)] for k in variants}
+        for i in range(calls):
+            for k, f in variants.items():
+                start()
+                a, b = ev[k][i]
+                a.record()
+                f()
+                b.record()
+        torch.cuda.synchronize()
+        dbr.check()
+        dbl.check()
+        res[f"retrieve_iteration_ms_n{n}"] = stats([a.elapsed_time(b) for a, b in ev[f"r{n}"]])
+        res[f"lm_iteration_ms_n{n}"] = stats([a.elapsed_time(b) for a, b in ev[f"l{n}"]])
+        res[f"done_n{n}"] = {str(k): int(v) for k, v in zip(*np.unique(L["done"].cpu().numpy(), return_counts=True))}
+        res[f"accepted_rejected_n{n}"] = [int(L["n_acc"].sum().item()), int(L["n_rej"].sum().item())]
+    rt.obs_destroy(h)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--views", default="1,6")
     ap.add_argument("--full", action="store_true", help="also time DeviceBatch.oe_step_full and the torch route to avk and post_cov")
+    ap.add_argument("--lm", action="store_true", help="time one DeviceBatch.lm_iterate against one iteration of DeviceBatch.retrieve instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -200,7 +279,11 @@ def main():
         tape3.write_tape3(t3, rec)
         rt = api.MonoRTM(t3, wn[0], wn[-1], device=0)
         for nview in (int(v) for v in args.views.split(",")):
-            res["cases"][str(nview * NCHAN)] = run_case(api, rt, profs, nview, args.calls, args.warmup, args.full)
+            if args.lm:
+                res["what"] = "one DeviceBatch.lm_iterate (l) vs one iteration of DeviceBatch.retrieve (r), interleaved, device events"
+                res["cases"][str(nview * NCHAN)] = run_lm_case(api, rt, profs, nview, args.calls, args.warmup)
+            else:
+                res["cases"][str(nview * NCHAN)] = run_case(api, rt, profs, nview, args.calls, args.warmup, args.full)
             torch.cuda.empty_cache()
         rt.close()
     line = json.dumps(res)
